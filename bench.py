@@ -1,7 +1,16 @@
 """Benchmark: Mrays/s of the sphere-cave frame fill on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs and nothing else: set-up, --settle, the W
+warm-up frames, the K timed frames, the result line (kernel_ms and the roofline entries come
+from HIP events inside those K frames and from committed profiles, no run of their own).
+--dump-outputs DIR then writes the last timed frame, as a caller of the timed path receives it
+(rank 0's assembled RGBA8 frame), to DIR/*.npy: see dump_outputs.  The scene, the camera and
+the texture are fixed, so two builds given the same arguments can be compared output for
+output.  Everything else described below -- the golden-frame checks, the lines under "also",
+the C-ABI multi-GPU line, the host-delivery line and the CPU baseline -- runs with --full only.
 
 A step is one full frame: every rank fills its row band of a 3840 x (2160*N)
 RGBA8 frame in HBM through libsfrt.so (64-sphere cave, BASELINE config 3),
@@ -19,7 +28,7 @@ last tiles drain (the throughput of a double-buffered display or offline loop).
 Before the W warm-up frames, --settle seconds of untimed frames let the chip
 reach its steady clock (it ramps over the first few hundred frames).
 
-Also reported under "also", each line with its own settle (--also-settle), warm-up
+With --full, also reported under "also", each line with its own settle (--also-settle), warm-up
 (--also-warmup) and timed frames (--also-steps, independent of --steps so that a short
 headline run still times every line over enough frames): the 7680x4320 frame row-tiled
 over the N ranks (BASELINE config 4; N = 1, 2, 4, 8) and the 16384x16384 frame at N = 1
@@ -116,6 +125,31 @@ def verify_frame(frame, section: str, key) -> dict:
     if want is None:
         return {"golden": None, "sha256": digest}
     return {"golden": f"{section}/{key}", "bit_identical": digest == want}
+
+
+DUMP_SAMPLE_PIXELS = 1 << 21  # x 4 channels x float32 = 32 MiB
+DUMP_SEED = 0x5F27
+
+
+def dump_outputs(out_dir: str, frame, width: int, height: int) -> list:
+    """--dump-outputs: the last timed frame (height x width RGBA8 on the device) as float
+    arrays.  The whole 4K frame as float32 would be 133 MB, so: frame_sample.npy, the RGBA
+    bytes of DUMP_SAMPLE_PIXELS pixels drawn without replacement by a fixed seed (float32
+    [K, 4]; frame_sample_index.npy holds their y * width + x as float64), and the exact
+    per-channel sums of every row and every column (frame_row_sums.npy [height, 4],
+    frame_col_sums.npy [width, 4], float64), which every byte of the frame enters."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = np.ascontiguousarray(frame.cpu().numpy()).reshape(height, width, 4)
+    px = host.reshape(-1, 4)
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.sort(rng.choice(px.shape[0], size=min(DUMP_SAMPLE_PIXELS, px.shape[0]), replace=False))
+    arrays = {"frame_sample": px[idx].astype(np.float32),
+              "frame_sample_index": idx.astype(np.float64),
+              "frame_row_sums": host.sum(axis=1, dtype=np.float64),
+              "frame_col_sums": host.sum(axis=0, dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return [name + ".npy" for name in arrays]
 
 
 def event_pair_ms(stream, n: int = 64) -> float:
@@ -730,6 +764,11 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--settle", type=float, default=0.3,
                     help="seconds of untimed frames before the warm-up (clock ramp)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also: the golden-frame checks, the lines under also, "
+                         "the C-ABI multi-GPU line, the host-delivery line and the CPU baseline")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write the last timed frame to DIR/*.npy (see dump_outputs)")
     ap.add_argument("--also-steps", type=int, default=200,
                     help="timed frames of every line under also (at least 20)")
     ap.add_argument("--also-warmup", type=int, default=20, help="warm-up frames of those lines")
@@ -747,12 +786,14 @@ def main() -> int:
                          "process group (RCCL refuses two ranks on one device), point-to-point "
                          "band transfers staged through host memory; runs the N > 1 body of "
                          "this script on a one-GPU box (tests/test_bench_rehearsal.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the 8K / 16K frames")
-    ap.add_argument("--no-f1f2", action="store_true", help="skip the GLSL-mode and voxel lines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the 8K / 16K frames")
+    ap.add_argument("--no-f1f2", action="store_true",
+                    help="--full without the GLSL-mode and voxel lines")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the headline workload (no also lines, no CPU baseline): the command "
-                         "whose rocprof kernel trace profiles/*_kernel_stats_by_grid.csv summarises")
+                    help="--full with only the headline workload and its golden-frame check (no also "
+                         "lines, no CPU baseline): the command whose rocprof kernel trace "
+                         "profiles/*_kernel_stats_by_grid.csv summarises")
     ap.add_argument("--time-limit", type=float, default=SUPERVISOR_TIME_LIMIT_S,
                     help="N > 1: seconds before the supervisor ends a rank's body and rank 0 "
                          "prints the line reached so far with an error field")
@@ -823,6 +864,9 @@ def main() -> int:
     total_rays = WIDTH * height * args.steps
     value = total_rays / wall / 1e6
     ms_per_step = wall / args.steps * 1e3
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, pipe.frame(args.steps - 1), WIDTH, height)
 
     result = None
     if rank == 0:
@@ -882,10 +926,13 @@ def main() -> int:
                     "valu_insts_per_launch": round(meas["SQ_INSTS_VALU"]),
                     "valu_insts_per_ray": round(meas["SQ_INSTS_VALU"] * 64 / rays_per_launch, 1),
                     "source": src}
+        if dumped:
+            result["outputs_dumped"] = {"dir": args.dump_outputs, "files": dumped}
+    if args.full and rank == 0:
         # the last timed frame (gathered on rank 0 at N > 1) against the golden frame
         result["frame_check"] = verify_frame(pipe.frame(args.steps - 1), "frames",
                                              scenes.golden_key(WIDTH, height, "lcg64"))
-    if world_size > 1 and rank == 0:
+    if args.full and world_size > 1 and rank == 0:
         # The last gathered frame must equal a single-GPU render of the whole frame.
         frame = pipe.frame(args.steps - 1)
         single = torch.empty_like(frame)
@@ -900,7 +947,8 @@ def main() -> int:
     # Larger frames of the BASELINE configs (strong scaling: the frame is fixed,
     # its rows split over the ranks), measured after the main line.
     extra = {}
-    if not (args.no_extra or args.headline_only):
+    headline_only = args.headline_only or not args.full  # a plain run ends with its headline
+    if not (args.no_extra or headline_only):
         for fw, fh, sname in EXTRA_FRAMES.get(world_size, []):
             sc_x = scene if sname == "lcg64" else scenes.SCENES[sname]()
             line = measure_frame(w, sc_x, fw, fh, rank, world_size, also_steps, also_warmup,
@@ -913,7 +961,7 @@ def main() -> int:
                 _partial_write(args.partial_out, dict(result, also=dict(extra),
                                                       _stage=f"after also/{fw}x{fh}_{sname}"))
         w.set_scene(scene, WIDTH, height)
-    if rank == 0:
+    if rank == 0 and args.full:
         result["also"] = dict(extra)
         result["also_timing"] = {"steps": also_steps, "warmup": also_warmup,
                                  "settle_s": args.also_settle}
@@ -923,14 +971,14 @@ def main() -> int:
         c_devs = [0] * world_size if args.rehearse else list(range(world_size))
     else:
         c_devs = []
-    if c_devs and not (args.no_extra or args.headline_only):
+    if c_devs and not (args.no_extra or headline_only):
         # the single-process multi-GPU path (C ABI), by rank 0 alone while the others wait
         if rank == 0:
             result["also"]["c_abi_multi"] = c_abi_multi_isolated(c_devs, max(20, also_steps // 4),
                                                                  also_warmup, args.also_settle)
         if host_group is not None:
             dist.barrier(group=host_group)
-    if world_size == 1 and not args.headline_only:
+    if world_size == 1 and not headline_only:
         def line(wx, fw, fh, name, per_frame=None, in_flight=1, golden=None, kernel="k_trace",
                  **info):
             """One N = 1 line under also: its own settle, warm-up and timed frames; its last
@@ -1039,7 +1087,7 @@ def main() -> int:
         if not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(scene, WIDTH, height, floor, gpu_frame)
     rc = 0
-    if rank == 0:
+    if rank == 0 and args.full:
         # every frame the line checked must be bit-identical to its golden / one-GPU frame; a line
         # with any that differs is marked invalid and the run exits 3 (after printing it)
         bad = [k for k, v in bit_identity_flags(result) if v is not True]
@@ -1047,6 +1095,7 @@ def main() -> int:
         if bad:
             result["invalid"] = {"frames_differ": bad}
             rc = 3
+    if rank == 0:
         print(json.dumps(result), flush=True)
     w.close()
     if world_size > 1:

@@ -53,3 +53,30 @@ def test_verify_frame_against_golden():
     assert bench.verify_frame(frame, "frames", "c1_320x240_one_sphere@0,0")["bit_identical"] is False
     none = bench.verify_frame(frame, "frames", None)
     assert none["golden"] is None and len(none["sha256"]) == 64
+
+
+def test_dump_outputs_is_a_fixed_view_of_the_frame(tmp_path):
+    """bench.py --dump-outputs: float arrays only, the same pixels sampled every time, every
+    byte of the frame in the row and column sums, and at most 64 MB for the 4K frame."""
+    import bench
+    g = GOLDEN["frames"]["c1_320x240_one_sphere@0,0"]
+    raw = zlib.decompress(open(os.path.join(ROOT, "tests", "golden", g["frame_file"]), "rb").read())
+    frame = torch.from_numpy(np.frombuffer(raw, np.uint8).copy()).reshape(240, 320 * 4)
+    names = bench.dump_outputs(str(tmp_path / "a"), frame, 320, 240)
+    assert sorted(names) == sorted(os.listdir(tmp_path / "a"))
+    a = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    px = frame.numpy().reshape(-1, 4)
+    idx = a["frame_sample_index.npy"].astype(np.int64)
+    assert idx.size == min(bench.DUMP_SAMPLE_PIXELS, px.shape[0]) == np.unique(idx).size
+    assert np.array_equal(a["frame_sample.npy"], px[idx].astype(np.float32))
+    assert a["frame_row_sums.npy"].shape == (240, 4) and a["frame_col_sums.npy"].shape == (320, 4)
+    assert a["frame_row_sums.npy"].sum() == a["frame_col_sums.npy"].sum() == float(px.sum(dtype=np.int64))
+    frame[17, 5] ^= 1  # one flipped byte shows in the sums, and the sampled pixels stay the same
+    bench.dump_outputs(str(tmp_path / "b"), frame, 320, 240)
+    b = {n: np.load(tmp_path / "b" / n) for n in names}
+    assert np.array_equal(a["frame_sample_index.npy"], b["frame_sample_index.npy"])
+    assert not np.array_equal(a["frame_row_sums.npy"], b["frame_row_sums.npy"])
+    assert not np.array_equal(a["frame_col_sums.npy"], b["frame_col_sums.npy"])
+    k = bench.DUMP_SAMPLE_PIXELS  # the 4K frame: sample, its index, the sums
+    assert k * 4 * 4 + k * 8 + (bench.WIDTH + bench.ROWS_PER_GPU * 8) * 4 * 8 <= 64e6

@@ -35,7 +35,7 @@ def _run(n, extra, timeout=240):
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            "bench.py", "--gpus", str(n), "--rehearse", "--steps", "10", "--warmup", "2",
            "--settle", "0", "--also-steps", "20", "--also-warmup", "5", "--also-settle", "0",
-           "--no-cpu-baseline"] + extra
+           "--full", "--no-cpu-baseline"] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)

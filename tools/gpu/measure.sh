@@ -8,7 +8,7 @@ T=${1:-measure}
 O=gpurun_out/$T/pass
 mkdir -p $O
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit 1
-timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 TAG=$T/prof bash tools/gpu/prof.sh || exit 1
 TAG=$T/glsl bash tools/gpu/prof_glsl.sh || exit 1
 TAG=$T/voxel bash tools/gpu/prof_voxel.sh || exit 1

@@ -8,7 +8,7 @@ mkdir -p $O
 timeout -k 10 ${TMO:-900} python -m torch.distributed.run --nnodes=1 --nproc-per-node=8 \
   --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 8 --rehearse --bands ${BANDS:-equal} \
   --steps 6 --warmup 2 --settle 0 --also-steps 20 --also-warmup 5 --also-settle 0 \
-  --no-cpu-baseline > $O/bench8.json 2> $O/bench8.err
+  --full --no-cpu-baseline > $O/bench8.json 2> $O/bench8.err
 rc=$?
 echo "exit $rc" >> $O/bench8.err
 exit $rc
