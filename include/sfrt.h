@@ -161,11 +161,31 @@ SFRT_API int sfrt_world_trace_points(sfrt_world* w, const int32_t* ij, int count
  * SFRT_OPT_TILE_ORDER (1 = default): sfrt_world_render_band dispatches the tiles
  * of a frame longest-first by the march steps an earlier render_band of the same
  * geometry recorded (two frames back; the sort runs inside the next launch);
- * 0 = row-major order.  Scheduling only: same bytes either way. */
+ * 0 = row-major order.  Scheduling only: same bytes either way.
+ * SFRT_OPT_SUPERSAMPLE (1 = default, today's frame byte for byte; 2 or 4; any other value
+ * returns SFRT_E_INVALID and changes nothing): S x S samples per pixel, box-filtered inside
+ * the frame-fill kernel.  The samples of output pixel (i, j) of the width x height frame are
+ * the pixels (S*i + k, S*j + l), 0 <= k, l < S, of the reference's frame fill at width
+ * S*width and height S*height (SphereWorld.cpp:85-106 evaluated with those sizes, so
+ * hIncreaseBy = cam.fovH / (S*width) * 2), each marched and shaded to RGBA8 as always (the
+ * texel rule and both status bits per sample); each of the four output bytes, alpha
+ * included, is (sum of the S*S sample bytes + S*S/2) >> log2(S*S), the round-half-up mean.
+ * Honoured by sfrt_world_update_image (its strides address output pixels; only those are
+ * written), sfrt_world_render_band (global output rows; bands tile the frame byte for
+ * byte) and sfrt_world_submit_frame: sizes, pitches, rows and buffers stay in output pixels,
+ * and only output pixels are stored and copied.  A frame call returns SFRT_E_INVALID when
+ * S*width, S*height or their tile grid exceed what one launch can take.
+ * sfrt_world_trace_points ignores the option: it dumps the 1x pixel.
+ * sfrt_world_row_costs returns one cost per output row (the sum over its S sample rows,
+ * constant over groups of 8 / S rows), and only for a fill made at the current factor.
+ * Averaged alphas are no longer 0 or 255: see sfrt_world_alpha_binary. */
 #define SFRT_OPT_CULL 1
 #define SFRT_OPT_RAYS_PER_LANE 2
 #define SFRT_OPT_TILE_ORDER 3
+#define SFRT_OPT_SUPERSAMPLE 4
 SFRT_API int sfrt_world_set_option(sfrt_world* w, int option, int value);
+/* The current value of any of the options above (SFRT_OPT_SUPERSAMPLE: the factor 1, 2 or 4). */
+SFRT_API int sfrt_world_get_option(const sfrt_world* w, int option, int* value);
 
 /* ---- stateless helpers ---- */
 /* UpdateSpheres ordering of an array in place (SphereWorld.cpp:199-212). */
@@ -201,7 +221,9 @@ SFRT_API int64_t sfrt_band_packed_bytes(int64_t pixels);  /* < 0: invalid */
 SFRT_API int sfrt_band_pack(const void* dev_rgba, int64_t pixels, void* dev_packed, void* hip_stream);
 SFRT_API int sfrt_band_unpack(const void* dev_packed, int64_t pixels, void* dev_rgba, void* hip_stream);
 /* 1 when at least one texture is loaded and every texel of every loaded texture has
- * alpha 0 or 255 (so every pixel the world renders does), else 0. */
+ * alpha 0 or 255 (so every pixel the world renders does), else 0.  With
+ * SFRT_OPT_SUPERSAMPLE 2 or 4 a pixel's alpha is a mean of texel alphas, so it is 1 only
+ * when, in addition, all those texels share one alpha (the mean of equal values). */
 SFRT_API int sfrt_world_alpha_binary(const sfrt_world* w, int* binary);
 
 /* ======================================================================
@@ -256,7 +278,8 @@ SFRT_API int sfrt_multi_set_option(sfrt_multi* m, int option, int value);
  * alpha-binary).  Packed bands travel by point-to-point transfers (RCCL) or peer
  * copies and are unpacked into the frame on devices[0]; the frame's bytes are the
  * same either way.  sfrt_multi_get_transfer: the setting and whether the last
- * render packed. */
+ * render packed.  A supersampled world (SFRT_OPT_SUPERSAMPLE) whose textures are not
+ * uniform in alpha is not alpha-binary: AUTO sends RGBA, PACKED fails the render. */
 #define SFRT_TRANSFER_AUTO 0
 #define SFRT_TRANSFER_RGBA 1
 #define SFRT_TRANSFER_PACKED 2

@@ -166,6 +166,16 @@ class SphereWorld {
           "render_band");
   }
   void Check(void* hip_stream = nullptr) { check(sfrt_world_check(w_, hip_stream), "check"); }
+  // SFRT_OPT_* (sfrt.h): SFRT_OPT_SUPERSAMPLE 2 or 4 box-filters S x S samples per pixel
+  // inside the frame-fill kernel; width, height and every buffer stay in output pixels.
+  void SetOption(int option, int value) { check(sfrt_world_set_option(w_, option, value), "set_option"); }
+  int GetOption(int option) const {
+    int v = 0;
+    check(sfrt_world_get_option(w_, option, &v), "get_option");
+    return v;
+  }
+  void SetSupersample(int factor) { SetOption(SFRT_OPT_SUPERSAMPLE, factor); }
+  int Supersample() const { return GetOption(SFRT_OPT_SUPERSAMPLE); }
   sfrt_world* handle() { return w_; }
 
  private:
@@ -231,6 +241,18 @@ class MultiSphereWorld {
   // Band transfer format: SFRT_TRANSFER_AUTO (default: packed RGB + alpha bit when every
   // texel's alpha is 0 or 255), SFRT_TRANSFER_RGBA or SFRT_TRANSFER_PACKED.
   void SetTransfer(int format) { check(sfrt_multi_set_transfer(m_, format), "set_transfer"); }
+  // SFRT_OPT_* on every GPU's world (sfrt_multi_set_option); read back from devices[0]'s.
+  // Supersampled bands pack only when every loaded texel has one alpha (sfrt_world_alpha_binary).
+  void SetOption(int option, int value) { check(sfrt_multi_set_option(m_, option, value), "set_option"); }
+  int GetOption(int option) const {
+    sfrt_world* w0 = nullptr;
+    check(sfrt_multi_world(m_, 0, &w0), "multi_world");
+    int v = 0;
+    check(sfrt_world_get_option(w0, option, &v), "get_option");
+    return v;
+  }
+  void SetSupersample(int factor) { SetOption(SFRT_OPT_SUPERSAMPLE, factor); }
+  int Supersample() const { return GetOption(SFRT_OPT_SUPERSAMPLE); }
   // The whole frame into a caller-owned sf::Uint8* RGBA8 buffer (width*height*4).
   void UpdateImage(uint8_t* pixels) {
     push_state();

@@ -57,6 +57,22 @@ __device__ __forceinline__ uint32_t wave_reduce_u32(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// Sum of v over the S x S pixel group of the lane (S = 1 << SS, 2 or 4), in every lane of
+// the group.  Lane l of a tile holds column l & 7 and row l >> 3 of an 8-column slot, so
+// the group's lanes differ in bits 0..SS-1 (columns) and 3..3+SS-1 (rows) of the lane id:
+// the partners lane ^ 1, ^ 2 and ^ 8 lie in the lane's row of 16 (DPP quad_perm and
+// row_ror:8), lane ^ 16 in its half of 32 (ds_swizzle, bit-mask mode: and 0x1f, xor 0x10;
+// no LDS is touched).  Call with the whole wave active, as for the reductions above.
+template <int SS>
+__device__ __forceinline__ uint32_t group_sum_u32(uint32_t v) {
+  static_assert(SS == 1 || SS == 2, "2x2 or 4x4 groups");
+  v += dpp_u32<0xB1, 0xf, 0u>(v);                  // quad_perm [1,0,3,2]: lane ^ 1
+  if constexpr (SS == 2) v += dpp_u32<0x4E, 0xf, 0u>(v);  // quad_perm [2,3,0,1]: lane ^ 2
+  v += dpp_u32<0x128, 0xf, 0u>(v);                 // row_ror:8: lane ^ 8
+  if constexpr (SS == 2) v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);  // lane ^ 16
+  return v;
+}
+
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return wave_reduce_u32<false>(v); }
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) { return wave_reduce_u32<true>(v); }
 

@@ -47,12 +47,17 @@ struct FrameRec {
   int xstart, xadd, ystart, yadd;   // UpdateImage pixel subset (SphereWorld.cpp:94,97)
   int sub_w;                        // columns in the subset
   int sub_row0, sub_rows;           // subset rows rendered by this launch
+  // Supersampled (ss > 0, below): h_inc / v_inc are those of the S*width x S*height sample
+  // frame, the subset is counted in samples (S per addressed output pixel, so sub_w, sub_row0
+  // and sub_rows are multiples of S), xstart / xadd / ystart / yadd are S times the caller's,
+  // and compact sample a is frame sample xstart + (a / S) * xadd + a % S (rows likewise).
   int tiles_x;                      // ceil(sub_w / 8)
   int cull;                         // 1: per-wave cone culling (default), 0: every sphere
   float cull_margin;                // absolute inflation of every sphere in the cone test
   int rays;                         // SFRT_OPT_RAYS_PER_LANE: 0 = the kernel table's choice, 1-4 forced
   long long out_pitch;              // output pitch in pixels
   uint32_t* out;                    // pixel (a, b) -> out[(b - sub_row0) * out_pitch + a]
+                                    // (ss > 0: out[((b - sub_row0) >> ss) * out_pitch + (a >> ss)])
   const uint32_t* tex;              // RGBA8 texture atlas (every loaded slot, back to back)
   const SphereRec* spheres;         // device copy (used when n > kInlineSpheres)
   int* status;                      // device word: bit 0 = march guard hit, bit 1 = bad texel
@@ -74,6 +79,10 @@ struct FrameRec {
   // tile_order's classes are the ones in tile_cost: store only changed classes (sfrt_device.h
   // store_cost, sfrt_sched.h TileSchedPtrs::cost_diff)
   int32_t cost_diff;
+  // SFRT_OPT_SUPERSAMPLE: log2 of the factor S (0, 1, 2).  Read by the host only (launch_trace
+  // picks the kernel instantiated for it, trace_tile_key carries it); the kernels take it as a
+  // template argument.
+  int32_t ss;
 };
 
 // Kernel argument for n <= kInlineSpheres: frame + spheres in the kernarg segment.
@@ -112,6 +121,10 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
 const char* trace_build_flavour();
 // Tile grid of the kernel launch_trace picks for f when that kernel takes part in
 // the adaptive tile order: a key naming the grid (> 0) and its tile count; else 0.
+// Bits 0-27 tiles_y, 28-55 tiles_x, 56-58 pixels per lane, 59-60 f.ss.
 long long trace_tile_key(const FrameRec& f, long long* tiles);
+// An upper bound of the workgroups launch_trace would launch for f in either tile order, so
+// that a caller can refuse a grid it cannot launch (> 0x7fffffff) before queuing anything.
+long long trace_blocks(const FrameRec& f);
 
 }  // namespace sfrt

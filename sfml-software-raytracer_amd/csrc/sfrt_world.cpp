@@ -122,10 +122,12 @@ struct sfrt_world {
   int tex_w[SFRT_TEXTURE_SLOTS] = {};
   int tex_h[SFRT_TEXTURE_SLOTS] = {};
   bool tex_alpha01[SFRT_TEXTURE_SLOTS] = {};  // every texel's alpha is 0 or 255
+  int tex_alpha_one[SFRT_TEXTURE_SLOTS] = {};  // the alpha every texel has, or -1
   uint32_t tex_off[SFRT_TEXTURE_SLOTS] = {};  // texel offset of each slot in the atlas
   int cull = 1;
   int rays = 0;           // SFRT_OPT_RAYS_PER_LANE (0 = automatic)
   int tile_order_on = 1;  // SFRT_OPT_TILE_ORDER
+  int ss = 0;             // SFRT_OPT_SUPERSAMPLE: log2 of the factor S (0, 1, 2)
   // --- device resources ---
   hipStream_t stream = nullptr;
   uint32_t* d_tex = nullptr;  // texture atlas: every loaded slot, back to back
@@ -219,13 +221,25 @@ struct sfrt_world {
     for (int32_t k : sphere_tex)
       if (tex_host[k].empty()) return SFRT_E_NO_TEXTURE;
     if (width <= 0 || height <= 0) return SFRT_E_INVALID;
+    // the sample frame's sizes are ints in the kernel (SFRT_OPT_SUPERSAMPLE)
+    if (ss && (width > (0x7fffffff >> ss) || height > (0x7fffffff >> ss))) return SFRT_E_INVALID;
     return SFRT_OK;
+  }
+
+  // A supersampled frame whose sample grid launch_trace cannot launch is refused before
+  // anything is queued (a plain frame that large fails in launch_trace, as it always has).
+  int launchable(const sfrt::FrameRec& f) const {
+    return f.ss && sfrt::trace_blocks(f) > 0x7fffffffLL ? SFRT_E_INVALID : SFRT_OK;
   }
 
   // Per-frame records: everything uniform over the frame, computed with the
   // reference's expressions (see sfrt_trace.h).
-  void prepare(sfrt::FrameRec& f, std::vector<sfrt::SphereRec>& recs) const {
+  // ss_log2 > 0: the frame is the S*width x S*height sample frame (SFRT_OPT_SUPERSAMPLE),
+  // i.e. :85-89 are evaluated with those sizes; the caller fills the subset in samples.
+  void prepare(sfrt::FrameRec& f, std::vector<sfrt::SphereRec>& recs, int ss_log2 = 0) const {
     std::memset(&f, 0, sizeof f);
+    const int width = this->width << ss_log2, height = this->height << ss_log2;
+    f.ss = ss_log2;
     const V3 campos{cam.pos[0], cam.pos[1], cam.pos[2]};
     f.cam[0] = campos.x; f.cam[1] = campos.y; f.cam[2] = campos.z;
     // SphereWorld.cpp:100-104
@@ -402,8 +416,8 @@ struct sfrt_world {
     if (sched.committed) {
       chain_cam[cur_chain] = ChainCam{true, cam, f.sub_row0};
       // that launch wrote its classes into cost[k % 2] before end() advanced k
-      last_fill = LastFill{true, f.sub_row0, f.sub_rows, f.sub_w, sched.key_prev,
-                           (int)((sched.k - 1) & 1), cur_chain};
+      last_fill = LastFill{true, f.sub_row0 >> f.ss, f.sub_rows >> f.ss, f.sub_w, sched.key_prev,
+                           (int)((sched.k - 1) & 1), cur_chain, f.ss};
     } else {
       last_fill.valid = false;  // this fill recorded no classes (tile order off, probe)
     }
@@ -413,10 +427,11 @@ struct sfrt_world {
   // The last launch that recorded its per-tile march-step classes (sfrt_world_row_costs).
   struct LastFill {
     bool valid = false;
-    int row0 = 0, rows = 0, width = 0;
-    long long key = 0;  // trace_tile_key: pixels per lane and the tile grid
+    int row0 = 0, rows = 0, width = 0;  // output rows; the grid's width (in samples when ss > 0)
+    long long key = 0;  // trace_tile_key: pixels per lane, the tile grid and the factor
     int buf = 0;        // scheds.chain[chain].cost[buf]
     int chain = -1;
+    int ss = 0;         // SFRT_OPT_SUPERSAMPLE (log2) of that fill: its tiles are of samples
   };
   LastFill last_fill;
 
@@ -474,10 +489,12 @@ int sfrt_world_row_costs(sfrt_world* w, float* costs, int capacity, int* row0, i
   *rows = 0;
   const auto& L = w->last_fill;
   if (!L.valid) return SFRT_E_INVALID;
-  const int tile_w = (int)((L.key >> 56) & 0x3f) * sfrt::kTile;
+  const int tile_w = (int)((L.key >> 56) & 0x7) * sfrt::kTile;
   const long long tiles_x = (L.key >> 28) & 0xfffffff, tiles_y = L.key & 0xfffffff;
   const sfrt::TileSched& sched = w->scheds.chain[L.chain];
   if (tile_w <= 0 || tiles_x * tiles_y > sched.cap) return SFRT_E_INVALID;
+  // a fill at one factor is never read back as another: the key carries the factor
+  if ((int)((L.key >> 59) & 3) != L.ss || L.ss != w->ss) return SFRT_E_INVALID;
   if (capacity < L.rows) return SFRT_E_INVALID;
   sfrt::DeviceGuard g(w->device);
   // the chain's last launch may still be running on a stream the caller has since destroyed
@@ -492,8 +509,11 @@ int sfrt_world_row_costs(sfrt_world* w, float* costs, int capacity, int* row0, i
       const long long px = std::min<long long>(tile_w, L.width - x0);
       c += (class_steps(cls[(size_t)(ty * tiles_x + tx)]) + kShadeSteps) * (double)px;
     }
-    for (int j = (int)ty * sfrt::kTile; j < std::min(L.rows, (int)(ty + 1) * sfrt::kTile); j++)
-      costs[j] = (float)c;
+    // Supersampled: the tile's 8 sample rows are 8 / S output rows, and an output row costs
+    // its S sample rows (all in this tile row: S divides 8 and the band starts on a group).
+    const int tile_rows = sfrt::kTile >> L.ss;
+    for (int j = (int)ty * tile_rows; j < std::min(L.rows, (int)(ty + 1) * tile_rows); j++)
+      costs[j] = (float)(c * (double)(1 << L.ss));
   }
   *row0 = L.row0;
   *rows = L.rows;
@@ -574,6 +594,9 @@ int sfrt_world_load_texture(sfrt_world* w, int slot, const uint8_t* rgba, int te
   bool a01 = true;
   for (size_t i = 3; i < bytes && a01; i += 4) a01 = rgba[i] == 0 || rgba[i] == 255;
   w->tex_alpha01[slot] = a01;
+  int one = rgba[3];
+  for (size_t i = 3; i < bytes && one >= 0; i += 4) one = rgba[i] == one ? one : -1;
+  w->tex_alpha_one[slot] = one;
   // Rebuild the device atlas: textures[0] (SphereWorld.cpp:376-377) first, then
   // the extension slots.  Draws on any stream may still read the old atlas.
   size_t total = 0;
@@ -617,13 +640,17 @@ int sfrt_world_load_texture(sfrt_world* w, int slot, const uint8_t* rgba, int te
 int sfrt_world_alpha_binary(const sfrt_world* w, int* binary) {
   if (!w || !binary) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
+  // Supersampled, a pixel's alpha is the rounded mean of S*S texel alphas: 0 or 255 for every
+  // pixel only if all loaded texels share one of the two (the mean of equal values is the value).
   bool any = false, all = true;
+  int one = -2;  // the alpha shared so far (-2: none seen, -1: they differ)
   for (int k = 0; k < SFRT_TEXTURE_SLOTS; k++) {
     if (w->tex_host[k].empty()) continue;
     any = true;
     all = all && w->tex_alpha01[k];
+    one = one == -2 || one == w->tex_alpha_one[k] ? w->tex_alpha_one[k] : -1;
   }
-  *binary = any && all ? 1 : 0;
+  *binary = any && all && (w->ss == 0 || one >= 0) ? 1 : 0;
   return SFRT_OK;
 }
 
@@ -717,7 +744,30 @@ int sfrt_world_set_option(sfrt_world* w, int option, int value) {
     w->tile_order_on = value == 2 ? 2 : value ? 1 : 0;  // 2: timing probe (see sched_begin)
     return SFRT_OK;
   }
+  if (option == SFRT_OPT_SUPERSAMPLE) {
+    if (value != 1 && value != 2 && value != 4) return SFRT_E_INVALID;
+    const int ss = value == 4 ? 2 : value == 2 ? 1 : 0;
+    if (ss != w->ss) {
+      // the last fill's tiles and the chains' recorded costs belong to the old sample grid
+      w->last_fill.valid = false;
+      for (auto& c : w->chain_cam) c.valid = false;
+    }
+    w->ss = ss;
+    return SFRT_OK;
+  }
   return SFRT_E_INVALID;
+}
+
+int sfrt_world_get_option(const sfrt_world* w, int option, int* value) {
+  if (!w || !value) return SFRT_E_INVALID;
+  std::lock_guard<std::mutex> lk(w->mu);
+  switch (option) {
+    case SFRT_OPT_CULL: *value = w->cull; return SFRT_OK;
+    case SFRT_OPT_RAYS_PER_LANE: *value = w->rays; return SFRT_OK;
+    case SFRT_OPT_TILE_ORDER: *value = w->tile_order_on; return SFRT_OK;
+    case SFRT_OPT_SUPERSAMPLE: *value = 1 << w->ss; return SFRT_OK;
+    default: return SFRT_E_INVALID;
+  }
 }
 
 int sfrt_world_update_image(sfrt_world* w, uint8_t* pixels, int ystart, int yadd, int xstart,
@@ -751,14 +801,21 @@ int sfrt_world_update_image(sfrt_world* w, uint8_t* pixels, int ystart, int yadd
   }
   sfrt::FrameRec f;
   std::vector<sfrt::SphereRec> recs;
-  w->prepare(f, recs);
-  f.xstart = xstart; f.xadd = xadd; f.ystart = ystart; f.yadd = yadd;
-  f.sub_w = sub_w;
+  // Supersampled (S = 1 << ss): S x S samples per addressed pixel, start and strides in samples
+  // (sfrt_trace.h FrameRec); d_frame and the scatter below stay in output pixels.
+  // A stride that addresses one pixel only is never applied (and may not fit once scaled); the
+  // others are below width / height, which validate() bounds.
+  const int ss = w->ss;
+  w->prepare(f, recs, ss);
+  f.xstart = xstart << ss; f.xadd = (ss && sub_w == 1 ? 1 : xadd) << ss;
+  f.ystart = ystart << ss; f.yadd = (ss && sub_h == 1 ? 1 : yadd) << ss;
+  f.sub_w = sub_w << ss;
   f.sub_row0 = 0;
-  f.sub_rows = sub_h;
-  f.tiles_x = (sub_w + sfrt::kTile - 1) / sfrt::kTile;
+  f.sub_rows = sub_h << ss;
+  f.tiles_x = (f.sub_w + sfrt::kTile - 1) / sfrt::kTile;
   f.out = w->d_frame;
   f.out_pitch = sub_w;
+  if ((rc = w->launchable(f))) return rc;
   rc = w->stage_spheres(f, recs, w->stream, false);
   if (rc) return rc;
   if (sfrt::launch_trace(f, recs.data(), w->stream, nullptr, w->ring_event())) return SFRT_E_HIP;
@@ -797,14 +854,16 @@ int sfrt_world_render_band(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes,
   hipStream_t s = (hipStream_t)hip_stream;  // HIP convention: NULL = the null stream
   sfrt::FrameRec f;
   std::vector<sfrt::SphereRec> recs;
-  w->prepare(f, recs);
-  f.xstart = 0; f.xadd = 1; f.ystart = 0; f.yadd = 1;
-  f.sub_w = w->width;
-  f.sub_row0 = row0;
-  f.sub_rows = rows;
-  f.tiles_x = (w->width + sfrt::kTile - 1) / sfrt::kTile;
+  const int ss = w->ss;  // supersampled: the band's S*rows sample rows of the S*width sample frame
+  w->prepare(f, recs, ss);
+  f.xstart = 0; f.xadd = 1 << ss; f.ystart = 0; f.yadd = 1 << ss;
+  f.sub_w = w->width << ss;
+  f.sub_row0 = row0 << ss;
+  f.sub_rows = rows << ss;
+  f.tiles_x = (f.sub_w + sfrt::kTile - 1) / sfrt::kTile;
   f.out = (uint32_t*)dev_pixels;
   f.out_pitch = pitch_bytes / 4;
+  if ((rc = w->launchable(f))) return rc;
   rc = w->stage_spheres(f, recs, s, false);
   if (rc) return rc;
   // after the last texture upload (queued on w->stream, where the other launches run)
@@ -951,15 +1010,17 @@ int sfrt_world_submit_frame(sfrt_world* w, uint8_t* pixels, int64_t* ticket) {
   HIP_TRY(hipMemsetAsync(slot.d_status, 0, sizeof(int), w->stream));
   sfrt::FrameRec f;
   std::vector<sfrt::SphereRec> recs;
-  w->prepare(f, recs);
-  f.xstart = 0; f.xadd = 1; f.ystart = 0; f.yadd = 1;
-  f.sub_w = w->width;
+  const int ss = w->ss;  // supersampled: the sample frame; d_buf and the copy stay width x height
+  w->prepare(f, recs, ss);
+  f.xstart = 0; f.xadd = 1 << ss; f.ystart = 0; f.yadd = 1 << ss;
+  f.sub_w = w->width << ss;
   f.sub_row0 = 0;
-  f.sub_rows = w->height;
-  f.tiles_x = (w->width + sfrt::kTile - 1) / sfrt::kTile;
+  f.sub_rows = w->height << ss;
+  f.tiles_x = (f.sub_w + sfrt::kTile - 1) / sfrt::kTile;
   f.out = slot.d_buf;
   f.out_pitch = w->width;
   f.status = slot.d_status;
+  if ((rc = w->launchable(f))) return rc;
   rc = w->stage_spheres(f, recs, w->stream, false);
   if (rc) return rc;
   if ((rc = w->sched_begin(f, w->stream))) return rc;  // adaptive tile order, as render_band

@@ -22,6 +22,8 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "sfrt_device.h"
 #include "sfrt_math.h"
 #include "sfrt_probe.h"
@@ -41,6 +43,22 @@ namespace {
 
 constexpr float kPI = 3.1415926535f;     // SphereWorld.h:6
 constexpr float kPI2 = 6.28318530718f;   // SphereWorld.h:7
+
+// Frame column (or row) of compact subset index a: start + a * add (SphereWorld.cpp:94,97).
+// Supersampled (S = 1 << SS samples per output pixel and axis; FrameRec): start and add are
+// in samples, S times the caller's, and sample a is sample a % S of addressed pixel a / S.
+template <int SS>
+__device__ __forceinline__ int subset_index(int start, int add, int a) {
+  if constexpr (SS == 0) return start + a * add;
+  else return start + (a >> SS) * add + (a & ((1 << SS) - 1));
+}
+// The stride of the compact index as a float, for the tile centre of the culling cone (an
+// axis only: the cone's half-angle is measured from the rays themselves).
+template <int SS>
+__device__ __forceinline__ float subset_stride(int add) {
+  if constexpr (SS == 0) return (float)add;
+  else return (float)add * (1.0f / (float)(1 << SS));
+}
 
 // Primary direction of pixel (i, j), normalised (SphereWorld.cpp:95-106, :358).
 __device__ __forceinline__ void primary_dir(const FrameRec& f, int i, int j, float& dx,
@@ -261,14 +279,14 @@ __device__ __forceinline__ float dist2(float px, float py, float pz, float cx, f
 }
 
 // Cone of an (8R)x8 tile whose lanes hold R rays each (columns c, c + 8, ...).
-template <int R>
+template <int R, int SS = 0>
 __device__ __forceinline__ Cone tile_cone_r(const FrameRec& f, int tile_x, int tile_y,
                                             const float (&dx)[R], const float (&dy)[R],
                                             const float (&dz)[R]) {
   const float ic = (float)f.xstart +
-                   ((float)(tile_x * R * kTile) + (0.5f * (float)(R * kTile) - 0.5f)) * (float)f.xadd;
+                   ((float)(tile_x * R * kTile) + (0.5f * (float)(R * kTile) - 0.5f)) * subset_stride<SS>(f.xadd);
   const float jc = (float)f.ystart +
-                   ((float)(f.sub_row0 + tile_y * kTile) + 3.5f) * (float)f.yadd;
+                   ((float)(f.sub_row0 + tile_y * kTile) + 3.5f) * subset_stride<SS>(f.yadd);
   const float h = f.h_start + f.h_inc * ic;
   const float v = f.v_start + jc * f.v_inc;
   float ax = (f.fwd[0] + f.right[0] * h) + f.up[0] * v;
@@ -302,12 +320,12 @@ __device__ __forceinline__ Cone tile_cone_r(const FrameRec& f, int tile_x, int t
 // within 60 degrees of the axis, so is every ray, and the largest corner sine plus the same
 // 1e-5 slack bounds every ray's (the slack covers the binary32 error of the corners' and of
 // the rays' directions, a few 1e-8); otherwise the tile is wide.  Lane l computes corner l % 4.
-template <int R>
+template <int R, int SS = 0>
 __device__ __forceinline__ Cone tile_cone_corners(const FrameRec& f, int tile_x, int tile_y, int lane) {
   const float ic = (float)f.xstart +
-                   ((float)(tile_x * R * kTile) + (0.5f * (float)(R * kTile) - 0.5f)) * (float)f.xadd;
+                   ((float)(tile_x * R * kTile) + (0.5f * (float)(R * kTile) - 0.5f)) * subset_stride<SS>(f.xadd);
   const float jc = (float)f.ystart +
-                   ((float)(f.sub_row0 + tile_y * kTile) + 3.5f) * (float)f.yadd;
+                   ((float)(f.sub_row0 + tile_y * kTile) + 3.5f) * subset_stride<SS>(f.yadd);
   const float hc = f.h_start + f.h_inc * ic;
   const float vc = f.v_start + jc * f.v_inc;
   float ax = (f.fwd[0] + f.right[0] * hc) + f.up[0] * vc;
@@ -320,8 +338,8 @@ __device__ __forceinline__ Cone tile_cone_corners(const FrameRec& f, int tile_x,
   const int b0 = f.sub_row0 + tile_y * kTile + ((lane & 2) ? kTile - 1 : 0);
   const int a = a0 < f.sub_w ? a0 : f.sub_w - 1;
   const int b = b0 < f.sub_row0 + f.sub_rows ? b0 : f.sub_row0 + f.sub_rows - 1;
-  const float h = f.h_start + f.h_inc * (float)(f.xstart + a * f.xadd);
-  const float v = f.v_start + (float)(f.ystart + b * f.yadd) * f.v_inc;
+  const float h = f.h_start + f.h_inc * (float)subset_index<SS>(f.xstart, f.xadd, a);
+  const float v = f.v_start + (float)subset_index<SS>(f.ystart, f.yadd, b) * f.v_inc;
   float x = (f.fwd[0] + f.right[0] * h) + f.up[0] * v;
   float y = (f.fwd[1] + f.right[1] * h) + f.up[1] * v;
   float z = (f.fwd[2] + f.right[2] * h) + f.up[2] * v;
@@ -405,10 +423,17 @@ __device__ __forceinline__ bool pass_body_r(const float (&ss)[R], float s_pass, 
 // DUMP (sfrt_world_trace_points only): the same march and shading, plus a per-ray
 // iteration count and an epilogue writing the float intermediates of listed pixels.
 // P: the probe hooks (sfrt_probe.h; NoProbe in the shipped library, all empty).
-template <int R, bool LIST, bool DUMP, class P>
+// SS (SFRT_OPT_SUPERSAMPLE, S = 1 << SS = 2 or 4): the tile is of sample pixels -- the
+// pixels of the S*width x S*height frame (FrameRec) -- cull, march and shading as for any
+// frame; the epilogue then box-filters each S x S group of samples, which sits in S x S
+// lanes of the wave (sfrt_device.h group_sum_u32), into the one output pixel its leader lane
+// stores.  S divides the tile's 8 rows and 8-column slots, and the subset's width and rows
+// are multiples of S, so a group is wholly inside the subset or wholly clamped duplicates.
+template <int R, bool LIST, bool DUMP, class P, int SS = 0>
 __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
                                                     const SphereRec* __restrict__ sph,
                                                     DumpArgs dmp) {
+  static_assert(SS == 0 || !DUMP, "trace_points dumps the 1x pixel");
   const int lane = threadIdx.x & 63;
   P probe;
   probe.wave_entry();
@@ -431,7 +456,7 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   const int b = f.sub_row0 + tile_y * kTile + (lane >> 3);
   const int b_end = f.sub_row0 + f.sub_rows;
   const int bc = b < b_end ? b : b_end - 1;
-  const int j = f.ystart + bc * f.yadd;
+  const int j = subset_index<SS>(f.ystart, f.yadd, bc);
   const float l0 = f.first_l;
   int draw[R];
   int iters[R];  // DUMP only: loop trips of :362 per ray, the host's first one included
@@ -443,7 +468,7 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   for (int r = 0; r < R; r++) {
     const int a = tile_x * R * kTile + r * kTile + (lane & 7);
     const int ac = a < f.sub_w ? a : f.sub_w - 1;
-    primary_dir(f, f.xstart + ac * f.xadd, j, dx[r], dy[r], dz[r]);
+    primary_dir(f, subset_index<SS>(f.xstart, f.xadd, ac), j, dx[r], dy[r], dz[r]);
     px[r] = f.cam[0] + dx[r] * l0;
     py[r] = f.cam[1] + dy[r] * l0;
     pz[r] = f.cam[2] + dz[r] * l0;
@@ -465,8 +490,8 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   int cidx = lane;        // sphere of culled-list entry `lane`
   if (windowed) {
     // R >= 3: four corner rays per wave are cheaper than R rays per lane (profiles/ab/r3_ab9)
-    const Cone cone = R >= 3 ? tile_cone_corners<R>(f, tile_x, tile_y, lane)
-                             : tile_cone_r<R>(f, tile_x, tile_y, dx, dy, dz);
+    const Cone cone = R >= 3 ? tile_cone_corners<R, SS>(f, tile_x, tile_y, lane)
+                             : tile_cone_r<R, SS>(f, tile_x, tile_y, dx, dy, dz);
     if (!LIST) {
       m = cull_window(f, sph, 0, cone, lo, hi);
     } else {
@@ -647,8 +672,9 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   auto valid = [&](int r) { return col(r) < f.sub_w && b_s < b_end; };
   // the row's first pixel, once per lane (inside each slot's store branch the compiler
   // recomputed the 64-bit row offset, three quarter-rate multiplies per slot)
-  uint32_t* const row_out = f.out + (long long)(b_s - f.sub_row0) * f.out_pitch;
-  auto px_out = [&](int r) { return row_out + col(r); };
+  // (SS > 0: the output pixel of sample (a, b) is (a >> SS, (b - sub_row0) >> SS))
+  uint32_t* const row_out = f.out + (long long)((b_s - f.sub_row0) >> SS) * f.out_pitch;
+  auto px_out = [&](int r) { return row_out + (col(r) >> SS); };
   if constexpr (!P::kShade) {  // timing probe (sfrt_probe.h): the march without the shading tail
 #pragma unroll
     for (int r = 0; r < R; r++)
@@ -671,28 +697,54 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
     uint32_t texel[R];
 #pragma unroll
     for (int r = 0; r < R; r++) texel[r] = f.tex[sh[r].tex];
+    if constexpr (SS > 0) {
+      // Box filter, out_c = (sum of the S*S samples' c + S*S/2) >> log2(S*S) for each of the
+      // four channels: every lane shades its sample (edge lanes their duplicates) with the
+      // status bit per sample as below, then the whole wave adds across each S x S group.
+      // A dword is split into two words of 16-bit fields (r, b and g, a: 16 * 255 fits), so
+      // two sums serve four channels; the shift moves a field's low bits into the field
+      // below, above its bit 8, where the mask drops them.
+      constexpr uint32_t kLow = (1u << SS) - 1u;
+      constexpr uint32_t kHalf = (1u << (2 * SS - 1)) * 0x00010001u;
+      const bool leader = ((lane_s & kLow) | ((lane_s >> 3) & kLow)) == 0;
+      uint32_t rgba[R];
 #pragma unroll
-    for (int r = 0; r < R; r++) {
-      if (valid(r)) {
-        if (sh[r].outside) atomicOr(f.status, 2);  // the reference would read outside the image
-        const uint32_t rgba = shade_rgba(sh[r].outside ? 0u : texel[r], sh[r].brightness);
-        if constexpr (!DUMP) {
-          *px_out(r) = rgba;
-        } else {  // the listed pixel's record, if it is listed (no frame store)
-          const long long pid = (long long)(b_s - f.sub_row0) * f.sub_w + col(r);
-          int q = 0, qe = dmp.npix;  // first entry >= pid
-          while (q < qe) {
-            const int mid = (q + qe) >> 1;
-            if (dmp.pix[mid] < pid) q = mid + 1;
-            else qe = mid;
-          }
-          if (q < dmp.npix && dmp.pix[q] == pid) {
-            PixelDump& o = dl[r];
-            o.pos[0] = px[r]; o.pos[1] = py[r]; o.pos[2] = pz[r];
-            o.draw = draw[r];
-            o.iters = iters[r];
-            o.rgba = rgba;
-            dmp.out[q] = o;
+      for (int r = 0; r < R; r++) {
+        if (valid(r) && sh[r].outside) atomicOr(f.status, 2);
+        rgba[r] = shade_rgba(sh[r].outside ? 0u : texel[r], sh[r].brightness);
+      }
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        const uint32_t rb = group_sum_u32<SS>(rgba[r] & 0x00ff00ffu);
+        const uint32_t ga = group_sum_u32<SS>((rgba[r] >> 8) & 0x00ff00ffu);
+        const uint32_t out = (((rb + kHalf) >> (2 * SS)) & 0x00ff00ffu) |
+                             ((((ga + kHalf) >> (2 * SS)) & 0x00ff00ffu) << 8);
+        if (leader && valid(r)) *px_out(r) = out;
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        if (valid(r)) {
+          if (sh[r].outside) atomicOr(f.status, 2);  // the reference would read outside the image
+          const uint32_t rgba = shade_rgba(sh[r].outside ? 0u : texel[r], sh[r].brightness);
+          if constexpr (!DUMP) {
+            *px_out(r) = rgba;
+          } else {  // the listed pixel's record, if it is listed (no frame store)
+            const long long pid = (long long)(b_s - f.sub_row0) * f.sub_w + col(r);
+            int q = 0, qe = dmp.npix;  // first entry >= pid
+            while (q < qe) {
+              const int mid = (q + qe) >> 1;
+              if (dmp.pix[mid] < pid) q = mid + 1;
+              else qe = mid;
+            }
+            if (q < dmp.npix && dmp.pix[q] == pid) {
+              PixelDump& o = dl[r];
+              o.pos[0] = px[r]; o.pos[1] = py[r]; o.pos[2] = pz[r];
+              o.draw = draw[r];
+              o.iters = iters[r];
+              o.rgba = rgba;
+              dmp.out[q] = o;
+            }
           }
         }
       }
@@ -713,6 +765,17 @@ __global__ __launch_bounds__(64, 8) void k_trace_window_r(InlineArgs args) {
 template <int R>
 __global__ __launch_bounds__(64) void k_trace_window_list(FrameRec f) {
   trace_tile_window_r<R, true, false, ActiveProbe>(f, f.spheres, DumpArgs{});
+}
+
+// The supersampling instantiations of both (SFRT_OPT_SUPERSAMPLE 2 and 4: SS = 1, 2), kernels
+// of their own so that the two above keep their names and their code.
+template <int R, int SS>
+__global__ __launch_bounds__(64, 8) void k_trace_window_r_ss(InlineArgs args) {
+  trace_tile_window_r<R, false, false, ActiveProbe, SS>(args.f, args.s, DumpArgs{});
+}
+template <int R, int SS>
+__global__ __launch_bounds__(64) void k_trace_window_list_ss(FrameRec f) {
+  trace_tile_window_r<R, true, false, ActiveProbe, SS>(f, f.spheres, DumpArgs{});
 }
 
 // The DUMP instantiations of both (sfrt_world_trace_points): the shipped march and
@@ -765,8 +828,43 @@ long long trace_tile_key(const FrameRec& f, long long* tiles) {
   const long long tiles_y = (f.sub_rows + kTile - 1) / kTile;
   if (tiles_x <= 0 || tiles_y <= 0) return 0;
   *tiles = tiles_x * tiles_y;
-  return (1ll << 62) | ((long long)rays << 56) | (tiles_x << 28) | tiles_y;
+  return (1ll << 62) | ((long long)(f.ss & 3) << 59) | ((long long)rays << 56) | (tiles_x << 28) |
+         tiles_y;
 }
+
+long long trace_blocks(const FrameRec& f) {
+  const long long tiles_y = (f.sub_rows + kTile - 1) / kTile;
+  if (tiles_y <= 0 || f.sub_w <= 0) return 0;
+  const int rays = std::min(trace_rays(f, false), trace_rays(f, true));  // the narrower tile
+  const long long tiles_x = (f.sub_w + rays * kTile - 1) / (rays * kTile);
+  return tiles_x * tiles_y + 1;  // + the tile-order sorter
+}
+
+namespace {
+
+// The supersampling kernels by (rays, ss); the launch itself as in launch_trace.
+template <int SS>
+void launch_inline_ss(int rays, dim3 gr, hipStream_t s, const InlineArgs& args) {
+  const dim3 b(64);
+  switch (rays) {
+    case 1: hipLaunchKernelGGL((k_trace_window_r_ss<1, SS>), gr, b, 0, s, args); break;
+    case 2: hipLaunchKernelGGL((k_trace_window_r_ss<2, SS>), gr, b, 0, s, args); break;
+    case 3: hipLaunchKernelGGL((k_trace_window_r_ss<3, SS>), gr, b, 0, s, args); break;
+    default: hipLaunchKernelGGL((k_trace_window_r_ss<4, SS>), gr, b, 0, s, args); break;
+  }
+}
+template <int SS>
+void launch_list_ss(int rays, dim3 gr, hipStream_t s, hipEvent_t ev, const FrameRec& g) {
+  const dim3 b(64);
+  switch (rays) {
+    case 1: hipExtLaunchKernelGGL((k_trace_window_list_ss<1, SS>), gr, b, 0, s, nullptr, ev, 0, g); break;
+    case 2: hipExtLaunchKernelGGL((k_trace_window_list_ss<2, SS>), gr, b, 0, s, nullptr, ev, 0, g); break;
+    case 3: hipExtLaunchKernelGGL((k_trace_window_list_ss<3, SS>), gr, b, 0, s, nullptr, ev, 0, g); break;
+    default: hipExtLaunchKernelGGL((k_trace_window_list_ss<4, SS>), gr, b, 0, s, nullptr, ev, 0, g); break;
+  }
+}
+
+}  // namespace
 
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump, void* done_event) {
@@ -787,11 +885,16 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
   const long long blocks = tiles + (g.prev_cost ? 1 : 0);
   if (blocks > 0x7fffffffLL) return -1;
   const dim3 gr((unsigned)blocks), b(64);
+  if (f.ss < 0 || f.ss > 2 || (f.ss && dump)) return -1;  // trace_points dumps the 1x pixel
+  if (f.ss && (f.sub_w | f.sub_row0 | f.sub_rows) & ((1 << f.ss) - 1)) return -1;  // whole groups
   if (f.n <= kInlineSpheres) {
     InlineArgs args;
     args.f = g;
     for (int k = 0; k < f.n; k++) args.s[k] = host_spheres[k];
-    if (dump) {
+    if (f.ss) {
+      if (f.ss == 1) launch_inline_ss<1>(rays, gr, s, args);
+      else launch_inline_ss<2>(rays, gr, s, args);
+    } else if (dump) {
       switch (rays) {
         case 1: hipLaunchKernelGGL(k_trace_window_r_dump<1>, gr, b, 0, s, args, *dump); break;
         case 2: hipLaunchKernelGGL(k_trace_window_r_dump<2>, gr, b, 0, s, args, *dump); break;
@@ -808,6 +911,10 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
     }
   } else if (f.n < 64) {
     return -1;  // the list kernel's lookahead reads culled-list lane 63 (a sphere index < n)
+  } else if (f.ss) {
+    const hipEvent_t ev = (hipEvent_t)done_event;
+    if (f.ss == 1) launch_list_ss<1>(rays, gr, s, ev, g);
+    else launch_list_ss<2>(rays, gr, s, ev, g);
   } else if (dump) {
     switch (rays) {
       case 1: hipLaunchKernelGGL(k_trace_window_list_dump<1>, gr, b, 0, s, g, *dump); break;

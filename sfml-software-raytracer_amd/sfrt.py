@@ -23,6 +23,7 @@ LIB_PATH = os.environ.get("SFRT_LIB") or os.path.join(HERE, "libsfrt.so")
 SFRT_OPT_CULL = 1
 SFRT_OPT_RAYS_PER_LANE = 2
 SFRT_OPT_TILE_ORDER = 3
+SFRT_OPT_SUPERSAMPLE = 4  # 1 (default), 2 or 4: S x S samples per pixel, box-filtered in the kernel
 ERRORS = {
     0: "SFRT_OK", -1: "SFRT_E_INVALID", -2: "SFRT_E_EMPTY", -3: "SFRT_E_NO_TEXTURE",
     -4: "SFRT_E_TOO_MANY", -5: "SFRT_E_HIP", -6: "SFRT_E_MARCH_LIMIT", -7: "SFRT_E_TEXEL",
@@ -57,7 +58,7 @@ ABI_SYMBOLS = (
     "sfrt_world_row_costs", "sfrt_multi_cost_bands", "sfrt_multi_row_costs", "sfrt_multi_balance",
     "sfrt_multi_set_transfer", "sfrt_multi_get_transfer", "sfrt_band_packed_bytes", "sfrt_band_pack",
     "sfrt_band_unpack", "sfrt_world_alpha_binary", "sfrt_multi_transport_library",
-    "sfrt_multi_use_test_transport",
+    "sfrt_multi_use_test_transport", "sfrt_world_get_option",
 )
 
 SFRT_MULTI_AUTO, SFRT_MULTI_RCCL, SFRT_MULTI_PEER = 0, 1, 2
@@ -132,6 +133,7 @@ def lib() -> ctypes.CDLL:
         "sfrt_multi_balance": ([vp, c_float], c_int),
         "sfrt_world_trace_points": ([W, vp, c_int, vp], c_int),
         "sfrt_world_set_option": ([W, c_int, c_int], c_int),
+        "sfrt_world_get_option": ([W, c_int, P(c_int)], c_int),
         "sfrt_world_submit_frame": ([W, vp, P(ctypes.c_int64)], c_int),
         "sfrt_world_wait_frame": ([W, ctypes.c_int64], c_int),
         "sfrt_host_alloc": ([P(vp), ctypes.c_int64], c_int),
@@ -198,6 +200,8 @@ def lib() -> ctypes.CDLL:
         "sfrt_multi_use_test_transport": ([ctypes.c_char_p], c_int),
     }
     for name, (args, res) in sig.items():
+        if os.environ.get("SFRT_LIB") and not hasattr(L, name):
+            continue  # an older build under A/B (tools/ab_libs.py) lacks the newer entry points
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res
@@ -355,6 +359,11 @@ class World:
 
     def set_option(self, option: int, value: int) -> None:
         _check(lib().sfrt_world_set_option(self._h, option, value), "set_option")
+
+    def get_option(self, option: int) -> int:
+        v = ctypes.c_int()
+        _check(lib().sfrt_world_get_option(self._h, option, ctypes.byref(v)), "get_option")
+        return v.value
 
     def set_scene(self, scene, width: int, height: int) -> None:
         """Load a scenes.Scene (spheres verbatim, camera pose) at width x height."""

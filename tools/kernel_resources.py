@@ -1,0 +1,80 @@
+"""Resource usage of the sphere frame-fill kernels, read from the gfx950 code object's metadata.
+
+    python tools/kernel_resources.py [--tree DIR] [--match k_trace_window] [--json]
+
+Compiles csrc/sphere_trace.hip of the source tree DIR (default: this one) for the device only,
+with the release flags of the Makefile, and prints one row per kernel whose name matches: VGPRs,
+SGPRs, scratch bytes per lane, LDS bytes per workgroup (the .vgpr_count, .sgpr_count,
+.private_segment_fixed_size and .group_segment_fixed_size of the amdhsa.kernels note) and the
+waves per SIMD those VGPRs allow (gfx950: 512 VGPRs per SIMD lane, allocated in blocks of 8,
+at most 8 waves).  Run it on two trees to compare a change's kernels with its parent's.
+"""
+import argparse
+import json
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LLVM = "/opt/rocm/lib/llvm/bin"
+FLAGS = ["-DSFRT_BUILD_FLAVOUR=\"release\"", "-O3", "-fno-slp-vectorize", "-std=c++17", "-fPIC",
+         "-fvisibility=hidden", "-ffp-contract=off", "-fno-fast-math", "-I../include", "-Icsrc"]
+
+
+def occupancy(vgprs: int) -> int:
+    blocks = max(1, (vgprs + 7) // 8) * 8
+    return min(8, 512 // blocks)
+
+
+def kernels(tree: str, match: str):
+    pkg = os.path.join(tree, "sfml-software-raytracer_amd")
+    with tempfile.TemporaryDirectory() as tmp:
+        co = os.path.join(tmp, "sphere_trace.co")
+        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950"] + FLAGS +
+                       ["-x", "hip", "--offload-device-only", "--no-gpu-bundle-output", "-c", "-o",
+                        co, os.path.join(pkg, "csrc", "sphere_trace.hip")], cwd=pkg, check=True,
+                       stderr=subprocess.DEVNULL)
+        notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", co], capture_output=True,
+                               text=True, check=True).stdout
+    rows = []
+    # one "  - .agpr_count: ..." mapping per kernel, keys in alphabetical order
+    for block in re.split(r"\n\s+- (?=\.agpr_count:|\.args:)", notes):
+        name = re.search(r"^\s*\.name:\s+(\S+)", block, re.M)
+        if not name or match not in name.group(1):
+            continue
+
+        def field(key):
+            m = re.search(rf"^\s*\.{key}:\s+(\d+)", block, re.M)
+            return int(m.group(1)) if m else 0
+        sym = name.group(1)
+        filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt", path=LLVM)
+        pretty = sym if not filt else (subprocess.run([filt, sym], capture_output=True,
+                                                      text=True).stdout.strip() or sym)
+        pretty = re.sub(r"^void sfrt::\(anonymous namespace\)::|\(.*$", "", pretty)
+        v = field("vgpr_count")
+        rows.append({"kernel": pretty, "vgprs": v, "sgprs": field("sgpr_count"),
+                     "scratch": field("private_segment_fixed_size"),
+                     "lds": field("group_segment_fixed_size"), "waves_per_simd": occupancy(v)})
+    return sorted(rows, key=lambda r: r["kernel"])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tree", default=ROOT)
+    ap.add_argument("--match", default="k_trace_window")
+    ap.add_argument("--json", action="store_true")
+    a = ap.parse_args()
+    rows = kernels(os.path.abspath(a.tree), a.match)
+    if a.json:
+        print(json.dumps(rows, indent=1))
+        return
+    print(f"{'kernel':40s} {'VGPRs':>5s} {'SGPRs':>5s} {'scratch':>7s} {'LDS':>5s} {'waves/SIMD':>10s}")
+    for r in rows:
+        print(f"{r['kernel']:40s} {r['vgprs']:5d} {r['sgprs']:5d} {r['scratch']:7d} {r['lds']:5d} "
+              f"{r['waves_per_simd']:10d}")
+
+
+if __name__ == "__main__":
+    main()
