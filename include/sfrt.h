@@ -383,8 +383,24 @@ SFRT_API int sfrt_voxel_render_band(sfrt_voxel* v, void* dev_pixels, int64_t pit
 SFRT_API int sfrt_voxel_check(sfrt_voxel* v, void* hip_stream);
 /* SFRT_OPT_TILE_ORDER as for sfrt_world, but off (0) by default here: render_band with 1
  * dispatches 8x8 tiles longest-first by the DDA + shadow steps of two frames back (same
- * bytes; measured 1-6% slower on the voxel worlds). */
+ * bytes; measured 1-6% slower on the voxel worlds).
+ * SFRT_OPT_SUPERSAMPLE (1 = default, today's frame byte for byte; 2 or 4; any other value
+ * returns SFRT_E_INVALID and changes nothing): S x S samples per pixel, box-filtered inside the
+ * kernel by the rule stated for sfrt_world (each of the four output bytes, alpha included, is
+ * (sum of the S*S sample bytes + S*S/2) >> log2(S*S)).  The samples of output pixel (i, j) are
+ * the pixels (S*i + k, S*j + l), 0 <= k, l < S, of World::UpdateImage at width S*width and
+ * height S*height (World.cpp:64-87 evaluated with those sizes: hIncreaseBy = cam.fovH /
+ * (S*width), vIncreaseBy = cam.fovV / (S*height)), each traced and shaded to RGBA8 as always
+ * (Raycast, LRaycast, billboards, lights; the texel status bit per sample).  The strides of
+ * sfrt_voxel_update_image address output pixels and only those are written; row0, rows, the
+ * pitch and the buffer of sfrt_voxel_render_band are in output pixels and bands tile the frame
+ * byte for byte.  Voxel frames hold alpha 0 as well as 255, so averaged alphas take values in
+ * between.  A frame call returns SFRT_E_INVALID, with nothing queued or written, when S*width
+ * or S*height does not fit an int or the sample grid has more tiles than one launch takes. */
 SFRT_API int sfrt_voxel_set_option(sfrt_voxel* v, int option, int value);
+/* The stored SFRT_OPT_TILE_ORDER (0, 1 or 2) or SFRT_OPT_SUPERSAMPLE (the factor 1, 2 or 4);
+ * any other option returns SFRT_E_INVALID. */
+SFRT_API int sfrt_voxel_get_option(const sfrt_voxel* v, int option, int* value);
 
 /* ======================================================================
  * GLSL renderer: drop-in for the live GPU path
@@ -436,8 +452,20 @@ SFRT_API int sfrt_glsl_draw_image(sfrt_glsl* g, uint8_t* pixels, int width, int 
 SFRT_API int sfrt_glsl_check(sfrt_glsl* g, void* hip_stream);
 /* SFRT_OPT_TILE_ORDER as for sfrt_world, on (1) by default: sfrt_glsl_draw dispatches 8x8
  * tiles longest-first by the metaball-march steps of two frames back (same bytes; 1-6 % faster
- * on the round-4 kernel); 0 = row-major.  sfrt_glsl_draw_image is row-major. */
+ * on the round-4 kernel); 0 = row-major.  sfrt_glsl_draw_image is row-major.
+ * SFRT_OPT_SUPERSAMPLE (1 = default, today's frame byte for byte; 2 or 4; any other value
+ * returns SFRT_E_INVALID and changes nothing): S x S samples per pixel, box-filtered inside the
+ * kernel by the rule stated for sfrt_world.  The samples are the fragments of an S*width x
+ * S*height render target: the `size` uniform is replaced by (S*size[0], S*size[1]) (exact in
+ * binary32), every other uniform is unchanged, and sample (a, b), b counted from the top, has
+ * gl_FragCoord = (a + 0.5, (S*height - 1 - b) + 0.5).  width, height, row0, rows and the pitch
+ * of sfrt_glsl_draw and sfrt_glsl_draw_image stay in output pixels; output alpha stays 255.
+ * A draw returns SFRT_E_INVALID, with nothing queued or written, when S*width or S*height
+ * reaches 2^24 or S*size is beyond the uniforms' bound. */
 SFRT_API int sfrt_glsl_set_option(sfrt_glsl* g, int option, int value);
+/* The stored SFRT_OPT_TILE_ORDER (0, 1 or 2) or SFRT_OPT_SUPERSAMPLE (the factor 1, 2 or 4);
+ * any other option returns SFRT_E_INVALID. */
+SFRT_API int sfrt_glsl_get_option(const sfrt_glsl* g, int option, int* value);
 
 /* ======================================================================
  * Asset pipeline: PNG -> RGBA8 as sf::Image::loadFromFile

@@ -330,6 +330,16 @@ class VoxelWorld {
           "render_band");
   }
   void Check(void* hip_stream = nullptr) { check(sfrt_voxel_check(v_, hip_stream), "check"); }
+  // SFRT_OPT_TILE_ORDER, SFRT_OPT_SUPERSAMPLE (sfrt.h): the latter, 2 or 4, box-filters S x S
+  // samples per pixel inside the kernel; width, height and every buffer stay in output pixels.
+  void SetOption(int option, int value) { check(sfrt_voxel_set_option(v_, option, value), "set_option"); }
+  int GetOption(int option) const {
+    int v = 0;
+    check(sfrt_voxel_get_option(v_, option, &v), "get_option");
+    return v;
+  }
+  void SetSupersample(int factor) { SetOption(SFRT_OPT_SUPERSAMPLE, factor); }
+  int Supersample() const { return GetOption(SFRT_OPT_SUPERSAMPLE); }
 
  private:
   void push_state() {
@@ -382,6 +392,16 @@ class Shader {
   void drawImage(uint8_t* pixels, int width, int height) {
     check(sfrt_glsl_draw_image(g_, pixels, width, height), "draw_image");
   }
+  // SFRT_OPT_TILE_ORDER, SFRT_OPT_SUPERSAMPLE (sfrt.h): the latter, 2 or 4, box-filters the
+  // fragments of the S*width x S*height target inside the kernel; draw's sizes stay in output pixels.
+  void SetOption(int option, int value) { check(sfrt_glsl_set_option(g_, option, value), "set_option"); }
+  int GetOption(int option) const {
+    int v = 0;
+    check(sfrt_glsl_get_option(g_, option, &v), "get_option");
+    return v;
+  }
+  void SetSupersample(int factor) { SetOption(SFRT_OPT_SUPERSAMPLE, factor); }
+  int Supersample() const { return GetOption(SFRT_OPT_SUPERSAMPLE); }
   sfrt_glsl* handle() { return g_; }
 
  private:

@@ -77,6 +77,11 @@ struct GlslFrame {
   // tile_order's classes are the ones in tile_cost: store only changed classes (sfrt_device.h
   // store_cost, sfrt_sched.h TileSchedPtrs::cost_diff)
   int32_t cost_diff;
+  // SFRT_OPT_SUPERSAMPLE: log2 of the factor S (0, 1, 2).  Read by the host only (launch_glsl
+  // picks the kernel, glsl_tile_key carries it).  When > 0 the frame is the S * width x S * height
+  // render target: width / height / row0 / rows / tiles_x / hk / vk are of the sample grid, out
+  // and out_pitch in output pixels (glsl_trace.hip fragment).
+  int32_t ss;
 };
 
 // Tile grid of the ordered GLSL kernel for f: key (> 0) and tile count.

@@ -130,7 +130,15 @@ __device__ __forceinline__ uint64_t wall_mask(const GlslFrame& f, float dx, floa
   return __builtin_amdgcn_ballot_w64(keep);
 }
 
-template <bool CULL>
+// SS (SFRT_OPT_SUPERSAMPLE, S = 1 << SS = 2 or 4): f is the S * width x S * height render target
+// (width, height, row0, rows, tiles_x, hk and vk of the sample grid: the host, sfrt_glsl.cpp), the
+// lane's fragment one of its samples; the tile's samples are box-filtered over each S x S group
+// of lanes (sfrt_device.h group_box_rgba8) and the group's leader lane stores the output pixel,
+// out and out_pitch being in output pixels.  Every lane of the wave must run the fragment (edge
+// lanes a clamped duplicate, store false): the filter's adds read the lanes of the lane's own
+// group, and width and rows being multiples of S and tiles starting at multiples of 8, a group
+// is wholly inside the frame or wholly duplicates.
+template <bool CULL, int SS = 0>
 __device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall> walls,
                                          const_ptr<GlslBall> balls, int i, int row,
                                          uint32_t& work, bool store = true) {
@@ -413,9 +421,19 @@ __device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall>
   cr *= fog;
   cg *= fog;
   cbl *= fog;
-  if (store)
-    f.out[(long long)(row - f.row0) * f.out_pitch + i] =
-        unorm8(cr) | (unorm8(cg) << 8) | (unorm8(cbl) << 16) | (255u << 24);
+  if constexpr (SS == 0) {
+    if (store)
+      f.out[(long long)(row - f.row0) * f.out_pitch + i] =
+          unorm8(cr) | (unorm8(cg) << 8) | (unorm8(cbl) << 16) | (255u << 24);
+  } else {
+    // the wave has reconverged (every branch above is wave-uniform or rejoins); alpha 255 in
+    // every sample stays 255
+    const uint32_t px =
+        group_box_rgba8<SS>(unorm8(cr) | (unorm8(cg) << 8) | (unorm8(cbl) << 16) | (255u << 24));
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    if (group_leader<SS>(lane) && store)
+      f.out[(long long)((row - f.row0) >> SS) * f.out_pitch + (i >> SS)] = px;
+  }
 }
 
 // Wall and ball records are read once per visit by every wave with scalar loads
@@ -436,30 +454,74 @@ __global__ __launch_bounds__(256) void k_glsl(GlslFrame f) {
 // One 8x8 tile per one-wave workgroup in the adaptive tile order (sfrt_device.h
 // sort_tiles; workgroup 0 is the sorter when prev_cost is set).  Edge lanes run
 // no fragment but stay for the wave's reduction.
-__global__ __launch_bounds__(64) void k_glsl_ordered(GlslFrame f, int ntiles) {
+//
+// glsl_ordered_tile is the workgroup's part of the launch up to the tile's stores, for the plain
+// kernel (SS = 0) and the supersampling ones: false for the sorter, else the tile, its class in
+// the order (sfrt_device.h slot_tile) and its lanes' march steps.  The cost record that follows
+// stays in the kernels' own bodies: inlined through here the compiler turned tile_bucket's chain
+// into other scalar code, and k_glsl_ordered is to compile to what it did before the
+// supersampling kernels came.
+template <int SS>
+__device__ __forceinline__ bool glsl_ordered_tile(const GlslFrame& f, int ntiles, int& tile,
+                                                  uint32_t& cls, uint32_t& work) {
   const int lane = threadIdx.x & 63;
   int slot = (int)blockIdx.x;
   if (f.prev_cost) {
     if (slot == 0) {
       sort_tiles(f.prev_cost, ntiles, f.next_order);
-      return;
+      return false;
     }
     slot -= 1;
   }
-  uint32_t cls;  // the tile's class in the order (sfrt_device.h slot_tile)
-  const int tile = slot_tile(f.tile_order, slot, ntiles, cls);
+  tile = slot_tile(f.tile_order, slot, ntiles, cls);
   const int tx = tile % f.tiles_x, ty = tile / f.tiles_x;
   const int i = tx * 8 + (lane & 7);
   const int r = ty * 8 + (lane >> 3);
   // Edge lanes shade a clamped duplicate pixel and store nothing: a divergent
   // branch around fragment() would cost its wave-uniform skips their uniformity.
   const bool in = i < f.width && r < f.rows;
-  uint32_t work = 0;
-  fragment<true>(f, as_const(f.walls), as_const(f.balls), i < f.width ? i : f.width - 1,
-                  f.row0 + (r < f.rows ? r : f.rows - 1), work, in);
+  work = 0;
+  fragment<true, SS>(f, as_const(f.walls), as_const(f.balls), i < f.width ? i : f.width - 1,
+                      f.row0 + (r < f.rows ? r : f.rows - 1), work, in);
+  return true;
+}
+
+__global__ __launch_bounds__(64) void k_glsl_ordered(GlslFrame f, int ntiles) {
+  int tile;
+  uint32_t cls, work;
+  if (!glsl_ordered_tile<0>(f, ntiles, tile, cls, work)) return;
   if (f.tile_cost) {
     const uint32_t w = wave_max_u32(work);  // the tile's longest march
-    if (lane == 0) store_cost(f.tile_cost, tile, tile_bucket(w), cls, f.cost_diff);
+    if ((threadIdx.x & 63) == 0) store_cost(f.tile_cost, tile, tile_bucket(w), cls, f.cost_diff);
+  }
+}
+
+// The supersampling instantiations (SS = 1, 2), kernels of their own: k_glsl and k_glsl_ordered
+// compile to what they did without them.  k_glsl_ss keeps its edge lanes as clamped duplicates
+// (k_glsl retires them): the filter needs the whole wave.  A wave past the last tile (the
+// workgroup's tail) retires whole.
+template <int SS>
+__global__ __launch_bounds__(256) void k_glsl_ss(GlslFrame f) {
+  const int lane = threadIdx.x & 63;
+  const int tile = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  const int tx = tile % f.tiles_x, ty = tile / f.tiles_x;
+  if (ty * 8 >= f.rows) return;  // wave-uniform
+  const int i = tx * 8 + (lane & 7);
+  const int r = ty * 8 + (lane >> 3);
+  const bool in = i < f.width && r < f.rows;
+  uint32_t work = 0;
+  fragment<false, SS>(f, as_const(f.walls), as_const(f.balls), i < f.width ? i : f.width - 1,
+                      f.row0 + (r < f.rows ? r : f.rows - 1), work, in);
+}
+
+template <int SS>
+__global__ __launch_bounds__(64) void k_glsl_ordered_ss(GlslFrame f, int ntiles) {
+  int tile;
+  uint32_t cls, work;
+  if (!glsl_ordered_tile<SS>(f, ntiles, tile, cls, work)) return;
+  if (f.tile_cost) {  // as k_glsl_ordered: the sample tile's longest march
+    const uint32_t w = wave_max_u32(work);
+    if ((threadIdx.x & 63) == 0) store_cost(f.tile_cost, tile, tile_bucket(w), cls, f.cost_diff);
   }
 }
 
@@ -470,21 +532,41 @@ long long glsl_tile_key(const GlslFrame& f, long long* tiles) {
   if (f.tiles_x <= 0 || f.rows <= 0) return 0;
   const long long ty = (f.rows + 7) / 8;
   *tiles = (long long)f.tiles_x * ty;
-  return (1ll << 62) | ((long long)f.tiles_x << 28) | ty;
+  return (1ll << 62) | ((long long)(f.ss & 3) << 59) | ((long long)f.tiles_x << 28) | ty;
 }
 
 int launch_glsl(const GlslFrame& f, void* stream, void* done_event) {
   const int tiles_y = (f.rows + 7) / 8;
   const long long tiles = (long long)f.tiles_x * tiles_y;
   if (tiles == 0) return 0;
+  if (f.ss < 0 || f.ss > 2) return -1;
+  // whole S x S groups: the filter's cross-lane adds rely on it
+  if (f.ss && ((f.width | f.row0 | f.rows) & ((1 << f.ss) - 1))) return -1;
   if (f.tile_cost) {  // adaptive tile order (the host linked this launch into its chain)
     if (tiles > 0x7ffffffeLL) return -1;
+    if (f.ss) {
+      const dim3 grid((unsigned)(tiles + (f.prev_cost ? 1 : 0)));
+      if (f.ss == 1)
+        hipExtLaunchKernelGGL(k_glsl_ordered_ss<1>, grid, dim3(64), 0, (hipStream_t)stream, nullptr,
+                              (hipEvent_t)done_event, 0, f, (int)tiles);
+      else
+        hipExtLaunchKernelGGL(k_glsl_ordered_ss<2>, grid, dim3(64), 0, (hipStream_t)stream, nullptr,
+                              (hipEvent_t)done_event, 0, f, (int)tiles);
+      return hipGetLastError() != hipSuccess;
+    }
     hipExtLaunchKernelGGL(k_glsl_ordered, dim3((unsigned)(tiles + (f.prev_cost ? 1 : 0))), dim3(64), 0,
                           (hipStream_t)stream, nullptr, (hipEvent_t)done_event, 0, f, (int)tiles);
     return hipGetLastError() != hipSuccess;
   }
-  hipExtLaunchKernelGGL(k_glsl, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                        nullptr, (hipEvent_t)done_event, 0, f);
+  if (f.ss == 1)
+    hipExtLaunchKernelGGL(k_glsl_ss<1>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0,
+                          (hipStream_t)stream, nullptr, (hipEvent_t)done_event, 0, f);
+  else if (f.ss == 2)
+    hipExtLaunchKernelGGL(k_glsl_ss<2>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0,
+                          (hipStream_t)stream, nullptr, (hipEvent_t)done_event, 0, f);
+  else
+    hipExtLaunchKernelGGL(k_glsl, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                          nullptr, (hipEvent_t)done_event, 0, f);
   return hipGetLastError() != hipSuccess;
 }
 

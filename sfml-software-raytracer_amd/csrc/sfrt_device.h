@@ -73,6 +73,34 @@ __device__ __forceinline__ uint32_t group_sum_u32(uint32_t v) {
   return v;
 }
 
+// Frame column (or row) of compact subset index a of a strided frame fill: start + a * add
+// (SphereWorld.cpp:94,97; World.cpp:72,79).  Supersampled (S = 1 << SS samples per output pixel
+// and axis): start and add are in samples, S times the caller's, and sample a is sample a % S of
+// addressed pixel a / S.
+template <int SS>
+__device__ __forceinline__ int subset_index(int start, int add, int a) {
+  if constexpr (SS == 0) return start + a * add;
+  else return start + (a >> SS) * add + (a & ((1 << SS) - 1));
+}
+
+// The box filter of SFRT_OPT_SUPERSAMPLE over the lane's S x S group (S = 1 << SS), in every lane
+// of the group: out_c = (sum of the S * S samples' c + S * S / 2) >> (2 * SS) for each of the four
+// bytes of an RGBA8 dword.  The dword is split into two words of 16-bit fields (r, b and g, a:
+// 16 * 255 fits), so two sums serve four channels; the shift moves a field's low bits into the
+// field below, above its bit 8, where the mask drops them.  Whole wave active (group_sum_u32).
+template <int SS>
+__device__ __forceinline__ uint32_t group_box_rgba8(uint32_t rgba) {
+  constexpr uint32_t kHalf = (1u << (2 * SS - 1)) * 0x00010001u;
+  const uint32_t rb = group_sum_u32<SS>(rgba & 0x00ff00ffu);
+  const uint32_t ga = group_sum_u32<SS>((rgba >> 8) & 0x00ff00ffu);
+  return (((rb + kHalf) >> (2 * SS)) & 0x00ff00ffu) | ((((ga + kHalf) >> (2 * SS)) & 0x00ff00ffu) << 8);
+}
+// The lane of a group that stores its pixel: lane-id bits 0..SS-1 (column) and 3..3+SS-1 (row) zero.
+template <int SS>
+__device__ __forceinline__ bool group_leader(int lane) {
+  return (lane & (((1 << SS) - 1) * 9)) == 0;
+}
+
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return wave_reduce_u32<false>(v); }
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) { return wave_reduce_u32<true>(v); }
 

@@ -96,6 +96,9 @@ struct sfrt_glsl {
   // SFRT_OPT_TILE_ORDER (sfrt_glsl_draw): on by default since round 4 (1080p -6 %, 4K -1 %, also
   // with the world moving every frame: profiles/ab/r4_ab9); draw_image stays row-major
   int tile_order_on = 1;
+  // SFRT_OPT_SUPERSAMPLE: log2 of the factor S (0, 1, 2).  S > 1: a draw renders the S * width x
+  // S * height target with `size` scaled by S (exact in binary32) and box-filters it in the kernel
+  int ss = 0;
   // adaptive tile order (sfrt_sched.h), one chain per stream: draws on two streams share no order
   // or cost buffer, so neither waits on the host for the other (as the sphere world, since round 6)
   sfrt::TileChains scheds;
@@ -126,7 +129,7 @@ struct sfrt_glsl {
   uint32_t* d_frame = nullptr;
   size_t d_frame_px = 0;
   sfrt::Relay relay;         // events recorded on callers' streams, relayed (sfrt_host.h)
-  std::mutex mu;
+  mutable std::mutex mu;
 
   sfrt_glsl() {
     for (auto& t : slots) t.relay = &relay;
@@ -157,6 +160,9 @@ struct sfrt_glsl {
                     v.fov[1]})
       if (!bounded(c)) return SFRT_E_INVALID;
     if (!(v.size[0] > 0.0f && v.size[1] > 0.0f && bounded(v.size[0]) && bounded(v.size[1])))
+      return SFRT_E_INVALID;
+    // the `size` the supersampled fragments see
+    if (!bounded(v.size[0] * (float)(1 << ss)) || !bounded(v.size[1] * (float)(1 << ss)))
       return SFRT_E_INVALID;
     for (int k = 0; k < v.all_spheres_count; k++)
       for (int c = 0; c < 4; c++)
@@ -197,8 +203,10 @@ struct sfrt_glsl {
     for (int c = 0; c < 3; c++) f.campos[c] = v.campos[c];
     f.fov_x = v.fov[0];
     f.fov_y = v.fov[1];
-    f.hk = v.fov[0] / v.size[0] * 2.0f;
-    f.vk = v.fov[1] / v.size[1] * 2.0f;
+    // size of the S * width x S * height target when supersampled (a power of two: exact)
+    f.ss = ss;
+    f.hk = v.fov[0] / (v.size[0] * (float)(1 << ss)) * 2.0f;
+    f.vk = v.fov[1] / (v.size[1] * (float)(1 << ss)) * 2.0f;
     f.sc = sc;
     f.lc = lc;
     f.all = all;
@@ -479,17 +487,20 @@ int sfrt_glsl_draw(sfrt_glsl* g, void* dev_pixels, int width, int height, int64_
       height >= (1 << 24) || width >= (1 << 24))
     return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(g->mu);
+  // supersampled: the fragments of the S * width x S * height target, gl_FragCoord exact below 2^24
+  const int ss = g->ss;
+  if ((height << ss) >= (1 << 24) || (width << ss) >= (1 << 24)) return SFRT_E_INVALID;
   sfrt::DeviceGuard dg(g->device);
   hipStream_t s = (hipStream_t)hip_stream;
   sfrt::GlslFrame f;
   if (rows == 0) return SFRT_OK;
   const int rc = g->prepare(f, s);
   if (rc) return rc;
-  f.width = width;
-  f.height = height;
-  f.row0 = row0;
-  f.rows = rows;
-  f.tiles_x = (width + 7) / 8;
+  f.width = width << ss;
+  f.height = height << ss;
+  f.row0 = row0 << ss;
+  f.rows = rows << ss;
+  f.tiles_x = (f.width + 7) / 8;
   f.out = (uint32_t*)dev_pixels;
   f.out_pitch = pitch_bytes / 4;
   long long tiles = 0;
@@ -513,6 +524,8 @@ int sfrt_glsl_draw_image(sfrt_glsl* g, uint8_t* pixels, int width, int height) {
   if (!g || !pixels || width <= 0 || height <= 0 || height >= (1 << 24) || width >= (1 << 24))
     return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(g->mu);
+  const int ss = g->ss;  // supersampled: the sample grid; d_frame and the copy stay width x height
+  if ((height << ss) >= (1 << 24) || (width << ss) >= (1 << 24)) return SFRT_E_INVALID;
   sfrt::DeviceGuard dg(g->device);
   const size_t px = (size_t)width * height;
   if (g->d_frame_px < px) {  // stream-ordered behind the last draw_image on the object's stream
@@ -525,11 +538,11 @@ int sfrt_glsl_draw_image(sfrt_glsl* g, uint8_t* pixels, int width, int height) {
   sfrt::GlslFrame f;
   int rc = g->prepare(f, g->stream);
   if (rc) return rc;
-  f.width = width;
-  f.height = height;
+  f.width = width << ss;
+  f.height = height << ss;
   f.row0 = 0;
-  f.rows = height;
-  f.tiles_x = (width + 7) / 8;
+  f.rows = f.height;
+  f.tiles_x = (f.width + 7) / 8;
   f.out = g->d_frame;
   f.out_pitch = width;
   if (sfrt::launch_glsl(f, g->stream, g->launch_event())) return SFRT_E_HIP;
@@ -545,7 +558,24 @@ int sfrt_glsl_set_option(sfrt_glsl* g, int option, int value) {
     g->tile_order_on = value == 2 ? 2 : value ? 1 : 0;
     return SFRT_OK;
   }
+  if (option == SFRT_OPT_SUPERSAMPLE) {
+    if (value != 1 && value != 2 && value != 4) return SFRT_E_INVALID;
+    const int ss = value == 4 ? 2 : value == 2 ? 1 : 0;
+    if (ss != g->ss) g->u_version++;  // the next draw stages its tables afresh
+    g->ss = ss;
+    return SFRT_OK;
+  }
   return SFRT_E_INVALID;
+}
+
+int sfrt_glsl_get_option(const sfrt_glsl* g, int option, int* value) {
+  if (!g || !value) return SFRT_E_INVALID;
+  std::lock_guard<std::mutex> lk(g->mu);
+  switch (option) {
+    case SFRT_OPT_TILE_ORDER: *value = g->tile_order_on; return SFRT_OK;
+    case SFRT_OPT_SUPERSAMPLE: *value = 1 << g->ss; return SFRT_OK;
+    default: return SFRT_E_INVALID;
+  }
 }
 
 int sfrt_glsl_check(sfrt_glsl* g, void* hip_stream) {

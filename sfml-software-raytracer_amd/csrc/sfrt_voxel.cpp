@@ -153,9 +153,13 @@ struct sfrt_voxel {
   uint32_t* d_frame = nullptr;
   size_t d_frame_px = 0;
   int tile_order_on = 0;     // SFRT_OPT_TILE_ORDER: off by default here (slower)
+  // SFRT_OPT_SUPERSAMPLE: log2 of the factor S (0, 1, 2).  S > 1: the frame's samples are the
+  // pixels of World::UpdateImage at S * width x S * height (prepare() builds the tables for that
+  // size), box-filtered in the kernel
+  int ss = 0;
   sfrt::TileChains scheds;   // adaptive tile order (sfrt_sched.h), render_band; one chain per stream
   sfrt::Relay relay;         // events recorded on callers' streams, relayed (sfrt_host.h)
-  std::mutex mu;
+  mutable std::mutex mu;
 
   sfrt_voxel() {
     for (auto& t : slots) t.relay = &relay;
@@ -192,17 +196,20 @@ struct sfrt_voxel {
   int prepare(sfrt::VoxFrame& f, hipStream_t s) {
     if (blocks.empty()) return SFRT_E_EMPTY;
     if (width <= 0 || height <= 0) return SFRT_E_INVALID;
+    // World.cpp:64-87 is evaluated at the sample size (ints: the frame calls checked sample_grid_ok)
+    const int W = width << ss, H = height << ss;
     std::memset(&f, 0, sizeof f);
+    f.ss = ss;
     f.cam[0] = cam.pos[0]; f.cam[1] = cam.pos[1]; f.cam[2] = cam.pos[2];
     f.view_distance = view_distance;
     f.shadow_distance = shadow_distance;
     f.maxiter = to_u32(view_distance * 1.5f);                       // World.cpp:322
     // World.cpp:64-87
     const float vStart = cam.fov_v / 2;
-    const float vIncreaseBy = cam.fov_v / height;
+    const float vIncreaseBy = cam.fov_v / H;
     const float vOff = std::sin(cam.hrotation);
     const float hStart = cam.rotation - cam.fov_h / 2;
-    const float hIncreaseBy = cam.fov_h / width;
+    const float hIncreaseBy = cam.fov_h / W;
     if (staged_version == tables_version && cur_slot >= 0) {
       sfrt::TableSlot& t = slots[cur_slot];  // still holds this scene's tables; launched() re-marks it
       const int rc = blocks_upload(s);  // first: fill_frame reads d_cells
@@ -212,9 +219,9 @@ struct sfrt_voxel {
       fill_frame(f, (uint8_t*)t.d, staged_off);
       return SFRT_OK;
     }
-    std::vector<float> col((size_t)width * 3), row((size_t)height * 2);
+    std::vector<float> col((size_t)W * 3), row((size_t)H * 2);
     float xmax = 0.0f;
-    for (int i = 0; i < width; i++) {
+    for (int i = 0; i < W; i++) {
       const float hray = (hStart + hIncreaseBy * i);
       const float fix = std::cos(cam.rotation - hray);
       const float dx = std::sin(hray) / fix, dz = std::cos(hray) / fix;
@@ -224,7 +231,7 @@ struct sfrt_voxel {
       for (float c : {dx, dz})
         if (std::isfinite(c)) xmax = std::max(xmax, std::fabs(c));
     }
-    for (int j = 0; j < height; j++) {
+    for (int j = 0; j < H; j++) {
       const float vray = (vStart - j * vIncreaseBy);
       row[2 * (size_t)j] = (vOff + std::sin(vray));
       row[2 * (size_t)j + 1] = std::cos(cam.hrotation + vray);   // r->yscale
@@ -385,6 +392,14 @@ struct sfrt_voxel {
     f.status = d_status;
   }
 
+  // A sub_w x sub_rows fill's sample grid (SFRT_OPT_SUPERSAMPLE) must fit the kernel's ints and
+  // launch_voxel's grid; checked before anything is allocated, queued or written.
+  bool sample_grid_ok(int sub_w, int sub_rows) const {
+    if (width > (0x7fffffff >> ss) || height > (0x7fffffff >> ss)) return false;
+    const long long tx = (((long long)sub_w << ss) + 7) / 8, ty = (((long long)sub_rows << ss) + 7) / 8;
+    return !ss || tx * ty <= 0x7ffffffeLL;
+  }
+
   // The current table slot's event, for the launch that reads it to record (its stop event), and
   // the slot marked busy once that launch is queued on s (the event also covers the launch's
   // read of the grid: SharedBuffer).
@@ -527,6 +542,7 @@ int sfrt_voxel_update_image(sfrt_voxel* v, uint8_t* pixels, int ystart, int yadd
   const int sub_h = ystart < v->height ? (v->height - ystart + yadd - 1) / yadd : 0;
   if (v->blocks.empty()) return SFRT_E_EMPTY;
   if (sub_w == 0 || sub_h == 0) return SFRT_OK;
+  if (!v->sample_grid_ok(sub_w, sub_h)) return SFRT_E_INVALID;
   sfrt::DeviceGuard g(v->device);
   const size_t px = (size_t)sub_w * sub_h;
   if (v->d_frame_px < px) {  // the last update_image finished with it (it waits for its copy)
@@ -539,10 +555,16 @@ int sfrt_voxel_update_image(sfrt_voxel* v, uint8_t* pixels, int ystart, int yadd
   sfrt::VoxFrame f;
   int rc = v->prepare(f, v->stream);
   if (rc) return rc;
-  f.xstart = xstart; f.xadd = xadd; f.ystart = ystart; f.yadd = yadd;
-  f.sub_w = sub_w;
+  // Supersampled (S = 1 << ss): S x S samples per addressed pixel, start and strides in samples
+  // (sfrt_device.h subset_index); d_frame, the copy and the scatter stay at output size.  A
+  // subset of one column (row) never steps, so its stride, which may exceed the frame, is not
+  // scaled up.
+  const int ss = v->ss;
+  f.xstart = xstart << ss; f.xadd = (ss && sub_w == 1 ? 1 : xadd) << ss;
+  f.ystart = ystart << ss; f.yadd = (ss && sub_h == 1 ? 1 : yadd) << ss;
+  f.sub_w = sub_w << ss;
   f.sub_row0 = 0;
-  f.sub_rows = sub_h;
+  f.sub_rows = sub_h << ss;
   f.out = v->d_frame;
   f.out_pitch = sub_w;
   if (sfrt::launch_voxel(f, v->stream, v->launch_event())) return SFRT_E_HIP;
@@ -566,15 +588,19 @@ int sfrt_voxel_render_band(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes,
   std::lock_guard<std::mutex> lk(v->mu);
   if (pitch_bytes < (int64_t)v->width * 4 || row0 + rows > v->height) return SFRT_E_INVALID;
   if (rows == 0) return SFRT_OK;
+  if (!v->sample_grid_ok(v->width, rows)) return SFRT_E_INVALID;
   sfrt::DeviceGuard g(v->device);
   hipStream_t s = (hipStream_t)hip_stream;
   sfrt::VoxFrame f;
   int rc = v->prepare(f, s);
   if (rc) return rc;
-  f.xstart = 0; f.xadd = 1; f.ystart = 0; f.yadd = 1;
-  f.sub_w = v->width;
-  f.sub_row0 = row0;
-  f.sub_rows = rows;
+  // supersampled: the band's S * rows sample rows of the S * width sample frame (rays by the
+  // global sample row: bands tile the frame); the buffer and its pitch in output pixels
+  const int ss = v->ss;
+  f.xstart = 0; f.xadd = 1 << ss; f.ystart = 0; f.yadd = 1 << ss;
+  f.sub_w = v->width << ss;
+  f.sub_row0 = row0 << ss;
+  f.sub_rows = rows << ss;
   f.out = (uint32_t*)dev_pixels;
   f.out_pitch = pitch_bytes / 4;
   long long tiles = 0;
@@ -601,7 +627,24 @@ int sfrt_voxel_set_option(sfrt_voxel* v, int option, int value) {
     v->tile_order_on = value == 2 ? 2 : value ? 1 : 0;
     return SFRT_OK;
   }
+  if (option == SFRT_OPT_SUPERSAMPLE) {
+    if (value != 1 && value != 2 && value != 4) return SFRT_E_INVALID;
+    const int ss = value == 4 ? 2 : value == 2 ? 1 : 0;
+    if (ss != v->ss) v->tables_version++;  // the col / row tables (and dda_qlim's xmax) are per sample
+    v->ss = ss;
+    return SFRT_OK;
+  }
   return SFRT_E_INVALID;
+}
+
+int sfrt_voxel_get_option(const sfrt_voxel* v, int option, int* value) {
+  if (!v || !value) return SFRT_E_INVALID;
+  std::lock_guard<std::mutex> lk(v->mu);
+  switch (option) {
+    case SFRT_OPT_TILE_ORDER: *value = v->tile_order_on; return SFRT_OK;
+    case SFRT_OPT_SUPERSAMPLE: *value = 1 << v->ss; return SFRT_OK;
+    default: return SFRT_E_INVALID;
+  }
 }
 
 int sfrt_voxel_check(sfrt_voxel* v, void* hip_stream) {

@@ -1087,7 +1087,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 3; }
+int sfrt_version(void) { return 4; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

@@ -44,14 +44,7 @@ namespace {
 constexpr float kPI = 3.1415926535f;     // SphereWorld.h:6
 constexpr float kPI2 = 6.28318530718f;   // SphereWorld.h:7
 
-// Frame column (or row) of compact subset index a: start + a * add (SphereWorld.cpp:94,97).
-// Supersampled (S = 1 << SS samples per output pixel and axis; FrameRec): start and add are
-// in samples, S times the caller's, and sample a is sample a % S of addressed pixel a / S.
-template <int SS>
-__device__ __forceinline__ int subset_index(int start, int add, int a) {
-  if constexpr (SS == 0) return start + a * add;
-  else return start + (a >> SS) * add + (a & ((1 << SS) - 1));
-}
+// subset_index<SS> (compact subset index -> frame column or row) is in sfrt_device.h.
 // The stride of the compact index as a float, for the tile centre of the culling cone (an
 // axis only: the cone's half-angle is measured from the rays themselves).
 template <int SS>

@@ -88,9 +88,14 @@ struct VoxFrame {
   // tile_order's classes are the ones in tile_cost: store only changed classes (sfrt_device.h
   // store_cost, sfrt_sched.h TileSchedPtrs::cost_diff)
   int32_t cost_diff;
+  // SFRT_OPT_SUPERSAMPLE: log2 of the factor S (0, 1, 2).  Read by the host only (launch_voxel
+  // picks the kernel, voxel_tile_key carries it).  When > 0 the frame is the S * width x S * height
+  // sample frame: xstart / xadd / ystart / yadd / sub_w / sub_row0 / sub_rows and the col / row
+  // tables are in samples, out and out_pitch in output pixels (voxel_trace.hip voxel_tile).
+  int32_t ss;
 };
 
-// Tile grid of launch_voxel for f (8x8 tiles): key (> 0) and tile count.
+// Tile grid of launch_voxel for f (8x8 tiles, of samples when f.ss > 0): key (> 0) and tile count.
 long long voxel_tile_key(const VoxFrame& f, long long* tiles);
 // done_event (hipEvent_t, may be null): recorded by the launch's own completion (its stop event).
 int launch_voxel(const VoxFrame& f, void* stream, void* done_event = nullptr);

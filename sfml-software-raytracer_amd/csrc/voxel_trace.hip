@@ -401,21 +401,32 @@ __device__ uint32_t raycast(const VoxFrame& f, V3 dir, float yscale,
 #ifndef SFRT_VOX_WAVES
 #define SFRT_VOX_WAVES 8
 #endif
-// COST: record the tile's cost for the adaptive order (f.tile_cost set); without it the step
-// counters are dead code and compiled out (one VALU per DDA and shadow-ray step)
-template <bool COST>
-__global__ __launch_bounds__(64, SFRT_VOX_WAVES) void k_voxel_ordered(VoxFrame f, int tiles_x, int ntiles) {
+// SS (SFRT_OPT_SUPERSAMPLE, S = 1 << SS = 2 or 4): the tile is of samples -- the pixels of
+// World::UpdateImage at S * width x S * height, f's subset, tables and strides in samples (the
+// host, sfrt_voxel.cpp) -- traced and shaded as always, then box-filtered over each S x S group of
+// lanes (sfrt_device.h group_box_rgba8) into the one output pixel its leader lane stores.  The
+// subset's width and rows are multiples of S and tiles start at multiples of 8, so a group is
+// wholly inside the subset or wholly clamped duplicates, and the adds cross no group.  The order,
+// the sorter, the fast-DDA choice and the cost record run on the sample grid unchanged.
+//
+// voxel_tile is the workgroup's part of the launch up to the tile's stores: false for the sorter,
+// else the tile, its class in the order (sfrt_device.h slot_tile) and its lanes' step counts.  The
+// cost record that follows stays in the kernels' own bodies: inlined through here the compiler
+// turned tile_bucket's chain into other scalar code, and k_voxel_ordered<true> is to compile to
+// what it did before the supersampling kernels came.
+template <int SS>
+__device__ __forceinline__ bool voxel_tile(const VoxFrame& f, int tiles_x, int ntiles, int& tile,
+                                           uint32_t& cls, uint32_t& work) {
   const int lane = threadIdx.x & 63;
   int slot = (int)blockIdx.x;
   if (f.prev_cost) {
     if (slot == 0) {
       sort_tiles(f.prev_cost, ntiles, f.next_order);
-      return;
+      return false;
     }
     slot -= 1;
   }
-  uint32_t cls;  // the tile's class in the order (sfrt_device.h slot_tile)
-  const int tile = slot_tile(f.tile_order, slot, ntiles, cls);
+  tile = slot_tile(f.tile_order, slot, ntiles, cls);
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int a = tx * 8 + (lane & 7);
   const int b = f.sub_row0 + ty * 8 + (lane >> 3);
@@ -423,20 +434,51 @@ __global__ __launch_bounds__(64, SFRT_VOX_WAVES) void k_voxel_ordered(VoxFrame f
   // branch around raycast() would make its wave-uniform choices divergent).
   const int ac = a < f.sub_w ? a : f.sub_w - 1;
   const int bc = b < f.sub_row0 + f.sub_rows ? b : f.sub_row0 + f.sub_rows - 1;
-  uint32_t work = 0;
-  const int i = f.xstart + ac * f.xadd;
-  const int j = f.ystart + bc * f.yadd;
+  const int i = subset_index<SS>(f.xstart, f.xadd, ac);
+  const int j = subset_index<SS>(f.ystart, f.yadd, bc);
+  work = 0;
   const V3 dir{f.col[3 * i], f.row[2 * j], f.col[3 * i + 1]};
   const uint32_t rgba = raycast(f, dir, f.row[2 * j + 1], f.col[3 * i + 2], work);
   // The store's pixel from the lane id again (mbcnt, not threadIdx): kept live across
   // raycast(), a, b and `in` were spilled to scratch (16 bytes per lane).
   const int lane2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   const int a2 = tx * 8 + (lane2 & 7), r2 = ty * 8 + (lane2 >> 3);
-  if (a2 < f.sub_w && r2 < f.sub_rows) f.out[(long long)r2 * f.out_pitch + a2] = rgba;
+  if constexpr (SS == 0) {
+    if (a2 < f.sub_w && r2 < f.sub_rows) f.out[(long long)r2 * f.out_pitch + a2] = rgba;
+  } else {
+    // every lane has its sample (edge lanes their duplicates) and the wave has reconverged
+    // (raycast()'s branches are wave-uniform): the output pixel of sample (a2, r2) of the band is
+    // (a2 >> SS, r2 >> SS), out and its pitch in output pixels
+    const uint32_t px = group_box_rgba8<SS>(rgba);
+    if (group_leader<SS>(lane2) && a2 < f.sub_w && r2 < f.sub_rows)
+      f.out[(long long)(r2 >> SS) * f.out_pitch + (a2 >> SS)] = px;
+  }
+  return true;
+}
+
+// COST: record the tile's cost for the adaptive order (f.tile_cost set); without it the step
+// counters are dead code and compiled out (one VALU per DDA and shadow-ray step)
+template <bool COST>
+__global__ __launch_bounds__(64, SFRT_VOX_WAVES) void k_voxel_ordered(VoxFrame f, int tiles_x, int ntiles) {
+  int tile;
+  uint32_t cls, work;
+  if (!voxel_tile<0>(f, tiles_x, ntiles, tile, cls, work)) return;
   if (COST) {
     // the tile's slowest ray, in DDA + shadow steps / 4 (the classes' scale)
     const uint32_t w = wave_max_u32(work);
-    if (lane == 0) store_cost(f.tile_cost, tile, tile_bucket(w >> 2), cls, f.cost_diff);
+    if ((threadIdx.x & 63) == 0) store_cost(f.tile_cost, tile, tile_bucket(w >> 2), cls, f.cost_diff);
+  }
+}
+// The supersampling instantiations (SS = 1, 2), kernels of their own: k_voxel_ordered compiles to
+// what it did without them.
+template <bool COST, int SS>
+__global__ __launch_bounds__(64, SFRT_VOX_WAVES) void k_voxel_ordered_ss(VoxFrame f, int tiles_x, int ntiles) {
+  int tile;
+  uint32_t cls, work;
+  if (!voxel_tile<SS>(f, tiles_x, ntiles, tile, cls, work)) return;
+  if (COST) {  // as k_voxel_ordered: the sample tile's slowest ray
+    const uint32_t w = wave_max_u32(work);
+    if ((threadIdx.x & 63) == 0) store_cost(f.tile_cost, tile, tile_bucket(w >> 2), cls, f.cost_diff);
   }
 }
 
@@ -470,8 +512,16 @@ long long voxel_tile_key(const VoxFrame& f, long long* tiles) {
   if (f.sub_w <= 0 || f.sub_rows <= 0) return 0;
   const long long tx = (f.sub_w + 7) / 8, ty = (f.sub_rows + 7) / 8;
   *tiles = tx * ty;
-  return (1ll << 62) | (tx << 28) | ty;
+  return (1ll << 62) | ((long long)(f.ss & 3) << 59) | (tx << 28) | ty;
 }
+
+namespace {
+template <bool COST, int SS>
+void launch_voxel_ss(const VoxFrame& f, dim3 grid, long long tiles, void* stream, void* done_event) {
+  hipExtLaunchKernelGGL((k_voxel_ordered_ss<COST, SS>), grid, dim3(64), 0, (hipStream_t)stream, nullptr,
+                        (hipEvent_t)done_event, 0, f, (int)((f.sub_w + 7) / 8), (int)tiles);
+}
+}  // namespace
 
 int launch_voxel(const VoxFrame& f, void* stream, void* done_event) {
   long long tiles = 0;
@@ -484,7 +534,16 @@ int launch_voxel(const VoxFrame& f, void* stream, void* done_event) {
   if (tiles > 0x7ffffffeLL) return -1;
   // row-major unless the host linked this launch into its tile-order chain
   const dim3 grid((unsigned)(tiles + (f.prev_cost ? 1 : 0)));
-  if (f.tile_cost)
+  if (f.ss < 0 || f.ss > 2) return -1;
+  // whole S x S groups: the filter's cross-lane adds rely on it
+  if (f.ss && ((f.sub_w | f.sub_row0 | f.sub_rows) & ((1 << f.ss) - 1))) return -1;
+  if (f.ss == 1) {
+    if (f.tile_cost) launch_voxel_ss<true, 1>(f, grid, tiles, stream, done_event);
+    else launch_voxel_ss<false, 1>(f, grid, tiles, stream, done_event);
+  } else if (f.ss == 2) {
+    if (f.tile_cost) launch_voxel_ss<true, 2>(f, grid, tiles, stream, done_event);
+    else launch_voxel_ss<false, 2>(f, grid, tiles, stream, done_event);
+  } else if (f.tile_cost)
     hipExtLaunchKernelGGL(k_voxel_ordered<true>, grid, dim3(64), 0, (hipStream_t)stream, nullptr,
                           (hipEvent_t)done_event, 0, f, (int)((f.sub_w + 7) / 8), (int)tiles);
   else

@@ -59,6 +59,7 @@ ABI_SYMBOLS = (
     "sfrt_multi_set_transfer", "sfrt_multi_get_transfer", "sfrt_band_packed_bytes", "sfrt_band_pack",
     "sfrt_band_unpack", "sfrt_world_alpha_binary", "sfrt_multi_transport_library",
     "sfrt_multi_use_test_transport", "sfrt_world_get_option",
+    "sfrt_voxel_get_option", "sfrt_glsl_get_option",
 )
 
 SFRT_MULTI_AUTO, SFRT_MULTI_RCCL, SFRT_MULTI_PEER = 0, 1, 2
@@ -160,6 +161,7 @@ def lib() -> ctypes.CDLL:
         "sfrt_voxel_render_band": ([vp, vp, ctypes.c_int64, c_int, c_int, vp], c_int),
         "sfrt_voxel_check": ([vp, vp], c_int),
         "sfrt_voxel_set_option": ([vp, c_int, c_int], c_int),
+        "sfrt_voxel_get_option": ([vp, c_int, P(c_int)], c_int),
         "sfrt_glsl_create": ([c_int, P(vp)], c_int),
         "sfrt_glsl_destroy": ([vp], None),
         "sfrt_glsl_set_ground": ([vp, vp, c_int, c_int], c_int),
@@ -171,6 +173,7 @@ def lib() -> ctypes.CDLL:
         "sfrt_glsl_draw_image": ([vp, vp, c_int, c_int], c_int),
         "sfrt_glsl_check": ([vp, vp], c_int),
         "sfrt_glsl_set_option": ([vp, c_int, c_int], c_int),
+        "sfrt_glsl_get_option": ([vp, c_int, P(c_int)], c_int),
         "sfrt_png_info": ([vp, ctypes.c_int64, P(c_int), P(c_int)], c_int),
         "sfrt_png_decode": ([vp, ctypes.c_int64, vp, ctypes.c_int64, P(c_int), P(c_int)], c_int),
         "sfrt_multi_create": ([vp, c_int, c_int, P(vp)], c_int),
@@ -523,6 +526,12 @@ class VoxelWorld:
     def set_option(self, option: int, value: int) -> None:
         _check(lib().sfrt_voxel_set_option(self._h, option, value), "voxel_set_option")
 
+    def get_option(self, option: int) -> int:
+        """SFRT_OPT_TILE_ORDER (0/1/2) or SFRT_OPT_SUPERSAMPLE (the factor 1, 2 or 4)."""
+        v = ctypes.c_int(0)
+        _check(lib().sfrt_voxel_get_option(self._h, option, ctypes.byref(v)), "voxel_get_option")
+        return int(v.value)
+
 
 def band_packed_bytes(pixels: int) -> int:
     """sfrt_band_packed_bytes: bytes of a packed band of `pixels` pixels (3.125 B each)."""
@@ -773,3 +782,9 @@ class GlslShader:
 
     def set_option(self, option: int, value: int) -> None:
         _check(lib().sfrt_glsl_set_option(self._h, option, value), "glsl_set_option")
+
+    def get_option(self, option: int) -> int:
+        """SFRT_OPT_TILE_ORDER (0/1/2) or SFRT_OPT_SUPERSAMPLE (the factor 1, 2 or 4)."""
+        v = ctypes.c_int(0)
+        _check(lib().sfrt_glsl_get_option(self._h, option, ctypes.byref(v)), "glsl_get_option")
+        return int(v.value)

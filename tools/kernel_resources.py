@@ -1,8 +1,9 @@
-"""Resource usage of the sphere frame-fill kernels, read from the gfx950 code object's metadata.
+"""Resource usage of the frame-fill kernels, read from the gfx950 code object's metadata.
 
-    python tools/kernel_resources.py [--tree DIR] [--match k_trace_window] [--json]
+    python tools/kernel_resources.py [--tree DIR] [--source sphere_trace.hip] [--match k_] [--json]
 
-Compiles csrc/sphere_trace.hip of the source tree DIR (default: this one) for the device only,
+Compiles csrc/SOURCE (sphere_trace.hip by default; voxel_trace.hip, glsl_trace.hip) of the source
+tree DIR (default: this one) for the device only,
 with the release flags of the Makefile, and prints one row per kernel whose name matches: VGPRs,
 SGPRs, scratch bytes per lane, LDS bytes per workgroup (the .vgpr_count, .sgpr_count,
 .private_segment_fixed_size and .group_segment_fixed_size of the amdhsa.kernels note) and the
@@ -28,13 +29,13 @@ def occupancy(vgprs: int) -> int:
     return min(8, 512 // blocks)
 
 
-def kernels(tree: str, match: str):
+def kernels(tree: str, match: str, source: str = "sphere_trace.hip"):
     pkg = os.path.join(tree, "sfml-software-raytracer_amd")
     with tempfile.TemporaryDirectory() as tmp:
-        co = os.path.join(tmp, "sphere_trace.co")
+        co = os.path.join(tmp, os.path.splitext(source)[0] + ".co")
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950"] + FLAGS +
                        ["-x", "hip", "--offload-device-only", "--no-gpu-bundle-output", "-c", "-o",
-                        co, os.path.join(pkg, "csrc", "sphere_trace.hip")], cwd=pkg, check=True,
+                        co, os.path.join(pkg, "csrc", source)], cwd=pkg, check=True,
                        stderr=subprocess.DEVNULL)
         notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", co], capture_output=True,
                                text=True, check=True).stdout
@@ -52,7 +53,8 @@ def kernels(tree: str, match: str):
         filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt", path=LLVM)
         pretty = sym if not filt else (subprocess.run([filt, sym], capture_output=True,
                                                       text=True).stdout.strip() or sym)
-        pretty = re.sub(r"^void sfrt::\(anonymous namespace\)::|\(.*$", "", pretty)
+        pretty = re.sub(r"^(void )?sfrt::\(anonymous namespace\)::", "", pretty)
+        pretty = re.sub(r"\(.*$", "", pretty)  # the parameter list
         v = field("vgpr_count")
         rows.append({"kernel": pretty, "vgprs": v, "sgprs": field("sgpr_count"),
                      "scratch": field("private_segment_fixed_size"),
@@ -63,10 +65,15 @@ def kernels(tree: str, match: str):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tree", default=ROOT)
-    ap.add_argument("--match", default="k_trace_window")
+    ap.add_argument("--source", default="sphere_trace.hip",
+                    choices=["sphere_trace.hip", "voxel_trace.hip", "glsl_trace.hip"])
+    ap.add_argument("--match", default=None,
+                    help="substring of the kernel names (default: k_trace_window for the sphere "
+                         "file, k_ for the others)")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
-    rows = kernels(os.path.abspath(a.tree), a.match)
+    match = a.match or ("k_trace_window" if a.source == "sphere_trace.hip" else "k_")
+    rows = kernels(os.path.abspath(a.tree), match, a.source)
     if a.json:
         print(json.dumps(rows, indent=1))
         return
