@@ -178,14 +178,32 @@ SFRT_API int sfrt_world_trace_points(sfrt_world* w, const int32_t* ij, int count
  * sfrt_world_trace_points ignores the option: it dumps the 1x pixel.
  * sfrt_world_row_costs returns one cost per output row (the sum over its S sample rows,
  * constant over groups of 8 / S rows), and only for a fill made at the current factor.
- * Averaged alphas are no longer 0 or 255: see sfrt_world_alpha_binary. */
+ * Averaged alphas are no longer 0 or 255: see sfrt_world_alpha_binary.
+ * SFRT_OPT_RAY_CACHE_MB (512 = default; 0 = off; negative values return SFRT_E_INVALID): the
+ * device memory, in MiB per world, that the world may spend on caching primary ray directions.
+ * The direction of a pixel's ray does not depend on the camera position, the spheres or the
+ * textures, only on the view rotation, the fields of view, the frame, band and subset
+ * geometry, the supersampling factor and the tile shape.  When a stream's second consecutive
+ * sfrt_world_render_band / sfrt_world_submit_frame keeps all of those, the directions are
+ * written once (12 bytes per ray, 95 MiB for a 4K frame) and later launches load them and
+ * skip the ray setup; any launch that changes one of them renders as without the cache, so a
+ * camera that turns every frame never fills.  Same bytes either way.  A cache that would
+ * take the world past the limit is not created; lowering the limit below what is held waits
+ * for the device and frees every cache.  See sfrt_world_ray_cache_stats. */
 #define SFRT_OPT_CULL 1
 #define SFRT_OPT_RAYS_PER_LANE 2
 #define SFRT_OPT_TILE_ORDER 3
 #define SFRT_OPT_SUPERSAMPLE 4
+#define SFRT_OPT_RAY_CACHE_MB 5
 SFRT_API int sfrt_world_set_option(sfrt_world* w, int option, int value);
 /* The current value of any of the options above (SFRT_OPT_SUPERSAMPLE: the factor 1, 2 or 4). */
 SFRT_API int sfrt_world_get_option(const sfrt_world* w, int option, int* value);
+/* The ray cache's counters since the world was created (SFRT_OPT_RAY_CACHE_MB):
+ * *cached_frames = launches that loaded their directions from a cache (the launch that
+ * filled it included), *fills = launches preceded by a fill, *bytes = device memory the
+ * world's caches hold now. */
+SFRT_API int sfrt_world_ray_cache_stats(const sfrt_world* w, int64_t* cached_frames, int64_t* fills,
+                                        int64_t* bytes);
 
 /* ---- stateless helpers ---- */
 /* UpdateSpheres ordering of an array in place (SphereWorld.cpp:199-212). */

@@ -176,6 +176,17 @@ class SphereWorld {
   }
   void SetSupersample(int factor) { SetOption(SFRT_OPT_SUPERSAMPLE, factor); }
   int Supersample() const { return GetOption(SFRT_OPT_SUPERSAMPLE); }
+  // SFRT_OPT_RAY_CACHE_MB (sfrt.h): MiB this world may spend on cached ray directions, 0 = off.
+  void SetRayCacheMB(int mib) { SetOption(SFRT_OPT_RAY_CACHE_MB, mib); }
+  int RayCacheMB() const { return GetOption(SFRT_OPT_RAY_CACHE_MB); }
+  struct RayCacheStats {
+    int64_t cached_frames, fills, bytes;
+  };
+  RayCacheStats GetRayCacheStats() const {
+    RayCacheStats s{};
+    check(sfrt_world_ray_cache_stats(w_, &s.cached_frames, &s.fills, &s.bytes), "ray_cache_stats");
+    return s;
+  }
   sfrt_world* handle() { return w_; }
 
  private:

@@ -16,6 +16,8 @@
 
 #include <cstdint>
 
+#include "sfrt_raycache.h"
+
 namespace sfrt {
 
 // Entries of an n-tile order array: its slot layout (sfrt_device.h order_index) maps the n slots
@@ -49,8 +51,18 @@ struct TileSched {
   bool have_last = false;
   uint64_t used = 0;             // TileChains: when the chain last took a launch
   bool probed = false;           // a timing-probe launch rewrote cost[k % 2] since k last moved
+  // The chain's primary-ray-direction cache (sfrt_raycache.h; the sphere renderer only): a
+  // stream-ordered buffer like order[] and cost[], used by the chain's own launches alone.  A
+  // takeover by another stream keeps it (begin() has waited for the device by then).
+  RayCachePolicy ray_policy;
+  float* ray_buf = nullptr;
+  long long ray_bytes = 0;
 
   void release() {
+    (void)hipFree(ray_buf);
+    ray_buf = nullptr;
+    ray_bytes = 0;
+    ray_policy.invalidate();
     for (int q = 0; q < 2; q++) {
       (void)hipFree(order[q]);
       (void)hipFree(cost[q]);
@@ -122,6 +134,7 @@ struct TileSched {
     if (!p.tile_cost) return hipSuccess;
     if (!queued) {
       reset();
+      ray_policy.invalidate();
       return hipSuccess;
     }
     committed = pending_key != 0;

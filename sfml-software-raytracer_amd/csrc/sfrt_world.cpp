@@ -128,6 +128,7 @@ struct sfrt_world {
   int rays = 0;           // SFRT_OPT_RAYS_PER_LANE (0 = automatic)
   int tile_order_on = 1;  // SFRT_OPT_TILE_ORDER
   int ss = 0;             // SFRT_OPT_SUPERSAMPLE: log2 of the factor S (0, 1, 2)
+  int ray_cache_mb = 512;  // SFRT_OPT_RAY_CACHE_MB: MiB of ray caches over all chains (0: off)
   // --- device resources ---
   hipStream_t stream = nullptr;
   uint32_t* d_tex = nullptr;  // texture atlas: every loaded slot, back to back
@@ -145,6 +146,13 @@ struct sfrt_world {
   sfrt::TileChains scheds;  // adaptive tile order (sfrt_sched.h), one chain per stream
   sfrt::TileSched dump_sched;  // sfrt_world_trace_points' own chain (never the frames')
   int cur_chain = 0;        // the chain of the launch between sched_begin and sched_end
+  // The ray cache (sfrt_raycache.h) of that launch: what its chain's policy decided, and the
+  // buffer launch_trace reads (null: today's kernel).  Counters: sfrt_world_ray_cache_stats.
+  bool ray_active = false;  // the launch takes part in the policy (an ordered, committing one)
+  sfrt::RayKey ray_key{};
+  sfrt::RayAction ray_action = sfrt::RayAction::kTrace;
+  const float* ray_cache = nullptr;
+  int64_t ray_cached_frames = 0, ray_fills = 0;
   // Device copies of the sphere records for launches that read them from memory
   // (> 64 spheres, trace_points): a ring of slots, each with pinned staging and
   // the event of the last launch that read it, so a slot is never overwritten
@@ -399,6 +407,78 @@ struct sfrt_world {
     // a moving camera: the recorded classes are a frame or two off
     f.order_dilate = p.prev_cost && chain_last.valid &&
                      std::memcmp(&chain_last.cam, &cam, sizeof cam) != 0;
+    ray_active = false;
+    ray_cache = nullptr;
+    ray_action = sfrt::RayAction::kTrace;
+    if (tile_order_on == 1 && p.tile_cost && sched.pending_key != 0) {
+      ray_active = true;
+      ray_key = make_ray_key(f, key);
+      const long long bytes = sfrt::ray_cache_bytes(tiles, (int)((key >> 56) & 7));
+      ray_action = sched.ray_policy.decide(ray_key, bytes, sched.ray_bytes,
+                                           ray_bytes_held() - sched.ray_bytes,
+                                           (long long)ray_cache_mb << 20);
+      if (ray_action == sfrt::RayAction::kFill && !ray_fill(sched, f, bytes, s)) {
+        sched.ray_policy.invalidate();  // the buffer may be gone or half written
+        ray_action = sfrt::RayAction::kTrace;
+      }
+      if (ray_action != sfrt::RayAction::kTrace) ray_cache = sched.ray_buf;
+    }
+    return SFRT_OK;
+  }
+
+  static sfrt::RayKey make_ray_key(const sfrt::FrameRec& f, long long tile_key) {
+    sfrt::RayKey k{};
+    for (int q = 0; q < 3; q++) {
+      k.fwd[q] = sfrt::ray_key_bits(f.fwd[q]);
+      k.right[q] = sfrt::ray_key_bits(f.right[q]);
+      k.up[q] = sfrt::ray_key_bits(f.up[q]);
+    }
+    k.h_start = sfrt::ray_key_bits(f.h_start); k.h_inc = sfrt::ray_key_bits(f.h_inc);
+    k.v_start = sfrt::ray_key_bits(f.v_start); k.v_inc = sfrt::ray_key_bits(f.v_inc);
+    k.xstart = f.xstart; k.xadd = f.xadd; k.ystart = f.ystart; k.yadd = f.yadd;
+    k.sub_w = f.sub_w; k.sub_row0 = f.sub_row0; k.sub_rows = f.sub_rows;
+    k.tile_key = tile_key;
+    return k;
+  }
+
+  long long ray_bytes_held() const {
+    long long held = 0;
+    for (const sfrt::TileSched& c : scheds.chain) held += c.ray_bytes;
+    return held;
+  }
+
+  // The chain's cache, grown if need be, filled for f on s (where the chain's launches run:
+  // sched.begin has waited for the device if another stream ran the last one).  false: the
+  // frame renders with today's kernel.
+  static bool ray_fill(sfrt::TileSched& sched, const sfrt::FrameRec& f, long long bytes,
+                       hipStream_t s) {
+    if (bytes > sched.ray_bytes) {
+      if (sched.ray_buf && hipFreeAsync(sched.ray_buf, s) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+      }
+      sched.ray_buf = nullptr;
+      sched.ray_bytes = 0;
+      if (hipMallocAsync((void**)&sched.ray_buf, (size_t)bytes, s) != hipSuccess) {
+        (void)hipGetLastError();  // no memory for it: not an error of the frame
+        sched.ray_buf = nullptr;
+        return false;
+      }
+      sched.ray_bytes = bytes;
+    }
+    return sfrt::launch_ray_fill(f, sched.ray_buf, s) == 0;
+  }
+
+  // SFRT_OPT_RAY_CACHE_MB lowered below what the chains hold: every cache goes.  The chains'
+  // streams may be gone (sfrt_sched.h), so the host waits for the device.
+  int ray_release_all() {
+    HIP_TRY(hipDeviceSynchronize());
+    for (sfrt::TileSched& c : scheds.chain) {
+      (void)hipFree(c.ray_buf);
+      c.ray_buf = nullptr;
+      c.ray_bytes = 0;
+      c.ray_policy.invalidate();
+    }
     return SFRT_OK;
   }
 
@@ -412,6 +492,11 @@ struct sfrt_world {
       chain_cam[cur_chain].valid = false;
       if (last_fill.chain == cur_chain) last_fill.valid = false;
       return SFRT_E_HIP;
+    }
+    if (ray_active) {
+      sched.ray_policy.commit(ray_key, ray_action, true);
+      if (ray_action == sfrt::RayAction::kFill) ray_fills++;
+      if (ray_action != sfrt::RayAction::kTrace) ray_cached_frames++;
     }
     if (sched.committed) {
       chain_cam[cur_chain] = ChainCam{true, cam, f.sub_row0};
@@ -755,7 +840,29 @@ int sfrt_world_set_option(sfrt_world* w, int option, int value) {
     w->ss = ss;
     return SFRT_OK;
   }
+  if (option == SFRT_OPT_RAY_CACHE_MB) {
+    if (value < 0) return SFRT_E_INVALID;
+    if (((long long)value << 20) < w->ray_bytes_held()) {
+      sfrt::DeviceGuard g(w->device);
+      const int rc = w->ray_release_all();
+      if (rc) return rc;
+    }
+    if (value == 0)
+      for (sfrt::TileSched& c : w->scheds.chain) c.ray_policy.invalidate();
+    w->ray_cache_mb = value;
+    return SFRT_OK;
+  }
   return SFRT_E_INVALID;
+}
+
+int sfrt_world_ray_cache_stats(const sfrt_world* w, int64_t* cached_frames, int64_t* fills,
+                               int64_t* bytes) {
+  if (!w || !cached_frames || !fills || !bytes) return SFRT_E_INVALID;
+  std::lock_guard<std::mutex> lk(w->mu);
+  *cached_frames = w->ray_cached_frames;
+  *fills = w->ray_fills;
+  *bytes = w->ray_bytes_held();
+  return SFRT_OK;
 }
 
 int sfrt_world_get_option(const sfrt_world* w, int option, int* value) {
@@ -766,6 +873,7 @@ int sfrt_world_get_option(const sfrt_world* w, int option, int* value) {
     case SFRT_OPT_RAYS_PER_LANE: *value = w->rays; return SFRT_OK;
     case SFRT_OPT_TILE_ORDER: *value = w->tile_order_on; return SFRT_OK;
     case SFRT_OPT_SUPERSAMPLE: *value = 1 << w->ss; return SFRT_OK;
+    case SFRT_OPT_RAY_CACHE_MB: *value = w->ray_cache_mb; return SFRT_OK;
     default: return SFRT_E_INVALID;
   }
 }
@@ -869,7 +977,8 @@ int sfrt_world_render_band(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes,
   // after the last texture upload (queued on w->stream, where the other launches run)
   HIP_TRY(w->tex_written.before_read(s));
   if ((rc = w->sched_begin(f, s))) return rc;
-  if ((rc = w->sched_end(f, s, sfrt::launch_trace(f, recs.data(), s, nullptr, w->ring_event()) == 0)))
+  if ((rc = w->sched_end(f, s, sfrt::launch_trace(f, recs.data(), s, nullptr, w->ring_event(),
+                                                  w->ray_cache) == 0)))
     return rc;
   if ((rc = w->launched_with())) return rc;
   return SFRT_OK;
@@ -1025,7 +1134,8 @@ int sfrt_world_submit_frame(sfrt_world* w, uint8_t* pixels, int64_t* ticket) {
   if (rc) return rc;
   if ((rc = w->sched_begin(f, w->stream))) return rc;  // adaptive tile order, as render_band
   if ((rc = w->sched_end(f, w->stream,
-                         sfrt::launch_trace(f, recs.data(), w->stream, nullptr, w->ring_event()) == 0)))
+                         sfrt::launch_trace(f, recs.data(), w->stream, nullptr, w->ring_event(),
+                                            w->ray_cache) == 0)))
     return rc;
   if ((rc = w->launched_with())) return rc;
   HIP_TRY(hipEventRecord(slot.rendered, w->stream));
@@ -1087,7 +1197,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 4; }
+int sfrt_version(void) { return 5; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

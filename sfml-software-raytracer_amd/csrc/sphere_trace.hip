@@ -78,6 +78,67 @@ __device__ __forceinline__ void primary_dir(const FrameRec& f, int i, int j, flo
   }
 }
 
+// The ray cache (sfrt_raycache.h; DESIGN.md 5 "Ray cache"): the directions primary_dir gives a
+// tile's rays, tile-major in the kernel's own tile / lane / slot mapping, clamped edge
+// duplicates included -- [tile][component x, y, z][lane][r] binary32, so a wave reads (and
+// k_ray_fill writes) three contiguous runs of 256 R bytes, R dwords per lane and component
+// (R = 4: one 16-byte access, the buffer and every run being 16-byte aligned).
+template <int R>
+struct RaySlots {
+  float v[R];
+};
+template <int R>
+__device__ __forceinline__ size_t ray_cache_at(int tile, int component, int lane) {
+  return ((size_t)tile * 3u + (size_t)component) * (size_t)(64 * R) + (size_t)(lane * R);
+}
+template <int R>
+__device__ __forceinline__ void ray_cache_load(const float* __restrict__ rc, int tile, int lane,
+                                               float (&dx)[R], float (&dy)[R], float (&dz)[R]) {
+  typedef RaySlots<R> __attribute__((aligned(R == 4 ? 16 : R == 2 ? 8 : 4))) Slots;
+  const Slots x = *(const Slots*)(rc + ray_cache_at<R>(tile, 0, lane));
+  const Slots y = *(const Slots*)(rc + ray_cache_at<R>(tile, 1, lane));
+  const Slots z = *(const Slots*)(rc + ray_cache_at<R>(tile, 2, lane));
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    dx[r] = x.v[r];
+    dy[r] = y.v[r];
+    dz[r] = z.v[r];
+  }
+}
+template <int R>
+__device__ __forceinline__ void ray_cache_store(float* __restrict__ rc, int tile, int lane,
+                                                const float (&dx)[R], const float (&dy)[R],
+                                                const float (&dz)[R]) {
+  typedef RaySlots<R> __attribute__((aligned(R == 4 ? 16 : R == 2 ? 8 : 4))) Slots;
+  Slots x, y, z;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    x.v[r] = dx[r];
+    y.v[r] = dy[r];
+    z.v[r] = dz[r];
+  }
+  *(Slots*)(rc + ray_cache_at<R>(tile, 0, lane)) = x;
+  *(Slots*)(rc + ray_cache_at<R>(tile, 1, lane)) = y;
+  *(Slots*)(rc + ray_cache_at<R>(tile, 2, lane)) = z;
+}
+
+// The directions of tile `tile`'s rays as the march takes them: lane l holds columns
+// (l & 7) + 8 r of tile row l >> 3, clamped to the subset (edge lanes trace a duplicate).
+template <int R, int SS>
+__device__ __forceinline__ void tile_dirs(const FrameRec& f, int tile_x, int tile_y, int lane,
+                                          float (&dx)[R], float (&dy)[R], float (&dz)[R]) {
+  const int b = f.sub_row0 + tile_y * kTile + (lane >> 3);
+  const int b_end = f.sub_row0 + f.sub_rows;
+  const int bc = b < b_end ? b : b_end - 1;
+  const int j = subset_index<SS>(f.ystart, f.yadd, bc);
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int a = tile_x * R * kTile + r * kTile + (lane & 7);
+    const int ac = a < f.sub_w ? a : f.sub_w - 1;
+    primary_dir(f, subset_index<SS>(f.xstart, f.xadd, ac), j, dx[r], dy[r], dz[r]);
+  }
+}
+
 // Shading tail, SphereWorld.cpp:373-381, in two parts so that a lane's R pixels
 // can issue their texel loads together: shade_texel computes the texel index --
 // `tex` indexes f.tex (the sphere's first texel when the index falls outside the
@@ -422,11 +483,15 @@ __device__ __forceinline__ bool pass_body_r(const float (&ss)[R], float s_pass, 
 // lanes of the wave (sfrt_device.h group_sum_u32), into the one output pixel its leader lane
 // stores.  S divides the tile's 8 rows and 8-column slots, and the subset's width and rows
 // are multiples of S, so a group is wholly inside the subset or wholly clamped duplicates.
-template <int R, bool LIST, bool DUMP, class P, int SS = 0>
+// CACHED: the rays' directions are loaded from the chain's ray cache rc (filled by k_ray_fill
+// for this launch's RayKey: the bits primary_dir gives) and not computed; all else is the same.
+template <int R, bool LIST, bool DUMP, class P, int SS = 0, bool CACHED = false>
 __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
                                                     const SphereRec* __restrict__ sph,
-                                                    DumpArgs dmp) {
+                                                    DumpArgs dmp,
+                                                    const float* __restrict__ rc = nullptr) {
   static_assert(SS == 0 || !DUMP, "trace_points dumps the 1x pixel");
+  static_assert(!CACHED || !DUMP, "the DUMP kernels compute their directions");
   const int lane = threadIdx.x & 63;
   P probe;
   probe.wave_entry();
@@ -446,10 +511,10 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   const int tile_x = tile - tile_y * f.tiles_x;
   if (tile_y * kTile >= f.sub_rows) return;  // grid rounding; uniform per wave
   probe.tile_begin();
-  const int b = f.sub_row0 + tile_y * kTile + (lane >> 3);
+  [[maybe_unused]] const int b = f.sub_row0 + tile_y * kTile + (lane >> 3);
   const int b_end = f.sub_row0 + f.sub_rows;
-  const int bc = b < b_end ? b : b_end - 1;
-  const int j = subset_index<SS>(f.ystart, f.yadd, bc);
+  [[maybe_unused]] const int bc = b < b_end ? b : b_end - 1;
+  [[maybe_unused]] const int j = CACHED ? 0 : subset_index<SS>(f.ystart, f.yadd, bc);
   const float l0 = f.first_l;
   int draw[R];
   int iters[R];  // DUMP only: loop trips of :362 per ray, the host's first one included
@@ -457,11 +522,14 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   // mv: the ray's last step length (> 0 while it marches, +0 once it stopped);
   // `mv > 0` is one compare per step, where a loop-carried bool would be
   // rematerialised through VGPRs.
+  if constexpr (CACHED) ray_cache_load<R>(rc, tile, lane, dx, dy, dz);
 #pragma unroll
   for (int r = 0; r < R; r++) {
-    const int a = tile_x * R * kTile + r * kTile + (lane & 7);
-    const int ac = a < f.sub_w ? a : f.sub_w - 1;
-    primary_dir(f, subset_index<SS>(f.xstart, f.xadd, ac), j, dx[r], dy[r], dz[r]);
+    if constexpr (!CACHED) {
+      const int a = tile_x * R * kTile + r * kTile + (lane & 7);
+      const int ac = a < f.sub_w ? a : f.sub_w - 1;
+      primary_dir(f, subset_index<SS>(f.xstart, f.xadd, ac), j, dx[r], dy[r], dz[r]);
+    }
     px[r] = f.cam[0] + dx[r] * l0;
     py[r] = f.cam[1] + dy[r] * l0;
     pz[r] = f.cam[2] + dz[r] * l0;
@@ -771,6 +839,32 @@ __global__ __launch_bounds__(64) void k_trace_window_list_ss(FrameRec f) {
   trace_tile_window_r<R, true, false, ActiveProbe, SS>(f, f.spheres, DumpArgs{});
 }
 
+// The ray cache's kernels (sfrt_raycache.h), again of their own.  k_ray_fill: one wave per tile
+// of the grid f.tiles_x x ceil(sub_rows / 8), row-major, stores the directions the kernels
+// above compute for that tile (the same primary_dir on the same indices under the same flags:
+// the same bits).  The _rc kernels are the four above with the directions loaded from rc.
+template <int R, int SS>
+__global__ __launch_bounds__(64) void k_ray_fill(FrameRec f, float* __restrict__ rc) {
+  const int lane = threadIdx.x & 63;
+  const int tile = (int)blockIdx.x;
+  const int tile_y = tile / f.tiles_x;
+  const int tile_x = tile - tile_y * f.tiles_x;
+  if (tile_y * kTile >= f.sub_rows) return;
+  float dx[R], dy[R], dz[R];
+  tile_dirs<R, SS>(f, tile_x, tile_y, lane, dx, dy, dz);
+  ray_cache_store<R>(rc, tile, lane, dx, dy, dz);
+}
+template <int R, int SS>
+__global__ __launch_bounds__(64, 8) void k_trace_window_r_rc(InlineArgs args,
+                                                             const float* __restrict__ rc) {
+  trace_tile_window_r<R, false, false, ActiveProbe, SS, true>(args.f, args.s, DumpArgs{}, rc);
+}
+template <int R, int SS>
+__global__ __launch_bounds__(64) void k_trace_window_list_rc(FrameRec f,
+                                                             const float* __restrict__ rc) {
+  trace_tile_window_r<R, true, false, ActiveProbe, SS, true>(f, f.spheres, DumpArgs{}, rc);
+}
+
 // The DUMP instantiations of both (sfrt_world_trace_points): the shipped march and
 // shading, with the float intermediates of listed pixels written out (never probed).
 template <int R>
@@ -857,10 +951,58 @@ void launch_list_ss(int rays, dim3 gr, hipStream_t s, hipEvent_t ev, const Frame
   }
 }
 
+// The ray-cache kernels by (rays, ss).
+template <int SS>
+void launch_inline_rc(int rays, dim3 gr, hipStream_t s, const InlineArgs& args, const float* rc) {
+  const dim3 b(64);
+  switch (rays) {
+    case 1: hipLaunchKernelGGL((k_trace_window_r_rc<1, SS>), gr, b, 0, s, args, rc); break;
+    case 2: hipLaunchKernelGGL((k_trace_window_r_rc<2, SS>), gr, b, 0, s, args, rc); break;
+    case 3: hipLaunchKernelGGL((k_trace_window_r_rc<3, SS>), gr, b, 0, s, args, rc); break;
+    default: hipLaunchKernelGGL((k_trace_window_r_rc<4, SS>), gr, b, 0, s, args, rc); break;
+  }
+}
+template <int SS>
+void launch_list_rc(int rays, dim3 gr, hipStream_t s, hipEvent_t ev, const FrameRec& g,
+                    const float* rc) {
+  const dim3 b(64);
+  switch (rays) {
+    case 1: hipExtLaunchKernelGGL((k_trace_window_list_rc<1, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc); break;
+    case 2: hipExtLaunchKernelGGL((k_trace_window_list_rc<2, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc); break;
+    case 3: hipExtLaunchKernelGGL((k_trace_window_list_rc<3, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc); break;
+    default: hipExtLaunchKernelGGL((k_trace_window_list_rc<4, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc); break;
+  }
+}
+template <int SS>
+void launch_fill(int rays, dim3 gr, hipStream_t s, const FrameRec& g, float* rc) {
+  const dim3 b(64);
+  switch (rays) {
+    case 1: hipLaunchKernelGGL((k_ray_fill<1, SS>), gr, b, 0, s, g, rc); break;
+    case 2: hipLaunchKernelGGL((k_ray_fill<2, SS>), gr, b, 0, s, g, rc); break;
+    case 3: hipLaunchKernelGGL((k_ray_fill<3, SS>), gr, b, 0, s, g, rc); break;
+    default: hipLaunchKernelGGL((k_ray_fill<4, SS>), gr, b, 0, s, g, rc); break;
+  }
+}
+
 }  // namespace
 
+int launch_ray_fill(const FrameRec& f, float* ray_cache, void* stream) {
+  long long tiles = 0;
+  if (!ray_cache || f.ss < 0 || f.ss > 2 || trace_tile_key(f, &tiles) == 0 || tiles > 0x7fffffffLL)
+    return -1;
+  const int rays = trace_rays(f, true);
+  FrameRec g = f;
+  g.tiles_x = (f.sub_w + rays * kTile - 1) / (rays * kTile);
+  const dim3 gr((unsigned)tiles);
+  hipStream_t s = (hipStream_t)stream;
+  if (f.ss == 0) launch_fill<0>(rays, gr, s, g, ray_cache);
+  else if (f.ss == 1) launch_fill<1>(rays, gr, s, g, ray_cache);
+  else launch_fill<2>(rays, gr, s, g, ray_cache);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
-                 const DumpArgs* dump, void* done_event) {
+                 const DumpArgs* dump, void* done_event, const float* ray_cache) {
   const long long tiles_y = (f.sub_rows + kTile - 1) / kTile;
   if (tiles_y <= 0 || f.sub_w <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
@@ -880,11 +1022,17 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
   const dim3 gr((unsigned)blocks), b(64);
   if (f.ss < 0 || f.ss > 2 || (f.ss && dump)) return -1;  // trace_points dumps the 1x pixel
   if (f.ss && (f.sub_w | f.sub_row0 | f.sub_rows) & ((1 << f.ss) - 1)) return -1;  // whole groups
+  // the cache is laid out for the ordered kernel's grid (launch_ray_fill), never dumped
+  if (ray_cache && (!ordered || !g.tile_cost || dump)) return -1;
   if (f.n <= kInlineSpheres) {
     InlineArgs args;
     args.f = g;
     for (int k = 0; k < f.n; k++) args.s[k] = host_spheres[k];
-    if (f.ss) {
+    if (ray_cache) {
+      if (f.ss == 0) launch_inline_rc<0>(rays, gr, s, args, ray_cache);
+      else if (f.ss == 1) launch_inline_rc<1>(rays, gr, s, args, ray_cache);
+      else launch_inline_rc<2>(rays, gr, s, args, ray_cache);
+    } else if (f.ss) {
       if (f.ss == 1) launch_inline_ss<1>(rays, gr, s, args);
       else launch_inline_ss<2>(rays, gr, s, args);
     } else if (dump) {
@@ -904,6 +1052,11 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
     }
   } else if (f.n < 64) {
     return -1;  // the list kernel's lookahead reads culled-list lane 63 (a sphere index < n)
+  } else if (ray_cache) {
+    const hipEvent_t ev = (hipEvent_t)done_event;
+    if (f.ss == 0) launch_list_rc<0>(rays, gr, s, ev, g, ray_cache);
+    else if (f.ss == 1) launch_list_rc<1>(rays, gr, s, ev, g, ray_cache);
+    else launch_list_rc<2>(rays, gr, s, ev, g, ray_cache);
   } else if (f.ss) {
     const hipEvent_t ev = (hipEvent_t)done_event;
     if (f.ss == 1) launch_list_ss<1>(rays, gr, s, ev, g);

@@ -24,6 +24,7 @@ SFRT_OPT_CULL = 1
 SFRT_OPT_RAYS_PER_LANE = 2
 SFRT_OPT_TILE_ORDER = 3
 SFRT_OPT_SUPERSAMPLE = 4  # 1 (default), 2 or 4: S x S samples per pixel, box-filtered in the kernel
+SFRT_OPT_RAY_CACHE_MB = 5  # MiB per world for cached primary ray directions (512 default, 0 off)
 ERRORS = {
     0: "SFRT_OK", -1: "SFRT_E_INVALID", -2: "SFRT_E_EMPTY", -3: "SFRT_E_NO_TEXTURE",
     -4: "SFRT_E_TOO_MANY", -5: "SFRT_E_HIP", -6: "SFRT_E_MARCH_LIMIT", -7: "SFRT_E_TEXEL",
@@ -59,7 +60,7 @@ ABI_SYMBOLS = (
     "sfrt_multi_set_transfer", "sfrt_multi_get_transfer", "sfrt_band_packed_bytes", "sfrt_band_pack",
     "sfrt_band_unpack", "sfrt_world_alpha_binary", "sfrt_multi_transport_library",
     "sfrt_multi_use_test_transport", "sfrt_world_get_option",
-    "sfrt_voxel_get_option", "sfrt_glsl_get_option",
+    "sfrt_voxel_get_option", "sfrt_glsl_get_option", "sfrt_world_ray_cache_stats",
 )
 
 SFRT_MULTI_AUTO, SFRT_MULTI_RCCL, SFRT_MULTI_PEER = 0, 1, 2
@@ -135,6 +136,8 @@ def lib() -> ctypes.CDLL:
         "sfrt_world_trace_points": ([W, vp, c_int, vp], c_int),
         "sfrt_world_set_option": ([W, c_int, c_int], c_int),
         "sfrt_world_get_option": ([W, c_int, P(c_int)], c_int),
+        "sfrt_world_ray_cache_stats": ([W, P(ctypes.c_int64), P(ctypes.c_int64),
+                                        P(ctypes.c_int64)], c_int),
         "sfrt_world_submit_frame": ([W, vp, P(ctypes.c_int64)], c_int),
         "sfrt_world_wait_frame": ([W, ctypes.c_int64], c_int),
         "sfrt_host_alloc": ([P(vp), ctypes.c_int64], c_int),
@@ -367,6 +370,14 @@ class World:
         v = ctypes.c_int()
         _check(lib().sfrt_world_get_option(self._h, option, ctypes.byref(v)), "get_option")
         return v.value
+
+    def ray_cache_stats(self) -> dict:
+        """The ray cache's counters (sfrt_world_ray_cache_stats): launches that read a cache
+        (the filling one included), fills, and the device bytes the caches hold now."""
+        c, f, b = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().sfrt_world_ray_cache_stats(self._h, ctypes.byref(c), ctypes.byref(f),
+                                                ctypes.byref(b)), "ray_cache_stats")
+        return {"cached_frames": c.value, "fills": f.value, "bytes": b.value}
 
     def set_scene(self, scene, width: int, height: int) -> None:
         """Load a scenes.Scene (spheres verbatim, camera pose) at width x height."""

@@ -8,7 +8,7 @@ experimental build that reads it -- r2_ab28 read it as SFRT_SPLIT; the product r
 Each round starts one process per library (SFRT_LIB=<lib>, the same sfrt.py), which
 times every case with HIP events (median kernel time, event-pair overhead subtracted;
 adaptive tile order, frames back to back on one stream, camera turning in the *_turn
-cases) and hashes one frame per case.  The parent prints per-case medians over rounds
+cases, walking in *_walk) and hashes one frame per case.  The parent prints per-case medians over rounds
 and fails if any library's frame hash differs from the first library's.
 """
 import argparse
@@ -23,6 +23,9 @@ CASES = {
     "4k": (3840, 2160, "lcg64", (0.0, 0.0), False),
     "4k_rot": (3840, 2160, "lcg64", (1.1, -0.2), False),
     "4k_turn": (3840, 2160, "lcg64", (0.0, 0.0), True),
+    # a walking camera: the position moves 0.01 per frame, the rotation stays (the ray cache,
+    # SFRT_OPT_RAY_CACHE_MB, serves such frames; a turning camera never fills it)
+    "4k_walk": (3840, 2160, "lcg64", (0.0, 0.0), "walk"),
     "8k": (7680, 4320, "lcg64", (0.0, 0.0), False),
     "1080": (1920, 1080, "default10", (0.0, 0.0), False),
     "4k_256": (3840, 2160, "lcg256", (0.0, 0.0), False),
@@ -109,16 +112,20 @@ def child(cases, reps, rays):
             sc = scenes.SCENES[sname]().posed(*pose)
             w.set_scene(sc, width, height)
         cam_pos = sc.cam_pos if sc is not None else None
+
+        def move(k):  # frame k's camera
+            if turn == "walk":
+                w.set_camera((cam_pos[0] + 0.01 * k, cam_pos[1], cam_pos[2]), *pose)
+            elif turn:
+                w.set_camera(cam_pos, 0.004 * k, 0.0)
         buf = torch.empty(height, width * 4, dtype=torch.uint8, device="cuda")
         for k in range(20):  # warm-up (clock ramp, tile-order chain)
-            if turn:
-                w.set_camera(cam_pos, 0.004 * k, 0.0)
+            move(k)
             w.render_band(buf.data_ptr(), width * 4, 0, height, stream.cuda_stream)
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
               for _ in range(reps)]
         for k, (a, b) in enumerate(ev):
-            if turn:
-                w.set_camera(cam_pos, 0.004 * (20 + k), 0.0)
+            move(20 + k)
             a.record(stream)
             w.render_band(buf.data_ptr(), width * 4, 0, height, stream.cuda_stream)
             b.record(stream)
@@ -130,8 +137,7 @@ def child(cases, reps, rays):
         import time
         t0 = time.perf_counter()
         for k in range(reps):
-            if turn:
-                w.set_camera(cam_pos, 0.004 * (20 + reps + k), 0.0)
+            move(20 + reps + k)
             w.render_band(buf.data_ptr(), width * 4, 0, height, stream.cuda_stream)
         torch.cuda.synchronize()
         wall = (time.perf_counter() - t0) / reps
