@@ -189,7 +189,12 @@ SFRT_API int sfrt_world_trace_points(sfrt_world* w, const int32_t* ij, int count
  * skip the ray setup; any launch that changes one of them renders as without the cache, so a
  * camera that turns every frame never fills.  Same bytes either way.  A cache that would
  * take the world past the limit is not created; lowering the limit below what is held waits
- * for the device and frees every cache.  See sfrt_world_ray_cache_stats. */
+ * for the device and frees every cache.  See sfrt_world_ray_cache_stats.
+ * The option also governs the tile records that ride with the directions: one 32-byte record
+ * per tile (the tile's culling cone and grid position, which depend on the same things),
+ * written by the same fill, read by the same launches and freed with the directions.  They
+ * are not counted against the limit (0.3 % of the directions' size at 4K); 0 turns both off.
+ * See sfrt_world_tile_record_bytes. */
 #define SFRT_OPT_CULL 1
 #define SFRT_OPT_RAYS_PER_LANE 2
 #define SFRT_OPT_TILE_ORDER 3
@@ -204,6 +209,9 @@ SFRT_API int sfrt_world_get_option(const sfrt_world* w, int option, int* value);
  * world's caches hold now. */
 SFRT_API int sfrt_world_ray_cache_stats(const sfrt_world* w, int64_t* cached_frames, int64_t* fills,
                                         int64_t* bytes);
+/* *bytes = device memory the world's tile records hold now (32 bytes per tile of every filled
+ * cache; 0 while SFRT_OPT_RAY_CACHE_MB is 0).  Not part of sfrt_world_ray_cache_stats' bytes. */
+SFRT_API int sfrt_world_tile_record_bytes(const sfrt_world* w, int64_t* bytes);
 
 /* ---- stateless helpers ---- */
 /* UpdateSpheres ordering of an array in place (SphereWorld.cpp:199-212). */

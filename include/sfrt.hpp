@@ -187,6 +187,12 @@ class SphereWorld {
     check(sfrt_world_ray_cache_stats(w_, &s.cached_frames, &s.fills, &s.bytes), "ray_cache_stats");
     return s;
   }
+  // Device bytes of the tile records that ride with the cached directions (sfrt.h).
+  int64_t TileRecordBytes() const {
+    int64_t b = 0;
+    check(sfrt_world_tile_record_bytes(w_, &b), "tile_record_bytes");
+    return b;
+  }
   sfrt_world* handle() { return w_; }
 
  private:

@@ -5,7 +5,9 @@
 // the textures or the march.  A tile-order chain (sfrt_sched.h) whose launches keep all of
 // those (RayKey) fills a tile-major buffer of directions once and reads it from then on
 // (sphere_trace.hip: k_ray_fill, the CACHED kernels).  This header decides when; it makes no
-// HIP call, so the policy is tested on the host (tests/native/raycache_check.cpp).
+// HIP call, so the policy is tested on the host (tests/native/raycache_check.cpp).  The tile
+// records (TileRec, below) are filled, read and dropped by the same decisions; their layout and
+// the chain's buffer bookkeeping (CacheBuf) are tested in tests/native/tilerec_check.cpp.
 #pragma once
 
 #include <cstdint>
@@ -40,6 +42,55 @@ inline uint32_t ray_key_bits(float v) {
 // Bytes of the cache of a grid of `tiles` tiles at `rays` pixels per lane: three binary32
 // components per ray, clamped edge duplicates included.
 inline long long ray_cache_bytes(long long tiles, int rays) { return tiles * rays * 64 * 12; }
+
+// The tile record: the other view-only part of a wave's prologue, cached beside the directions
+// under the same RayKey (DESIGN.md 5 "Ray cache").  One per tile, indexed by the tile number
+// sfrt_device.h slot_tile returns: the culling cone sphere_trace.hip tile_cone gives the tile
+// (unit axis, sine and cosine of the half-angle, the wide flag) and the tile's column and row
+// in the grid.  32 bytes, 32-byte aligned: a wave reads its record with one scalar 8-dword load
+// that never straddles a 64-byte line; k_ray_fill's lane 0 writes it.
+struct alignas(32) TileRec {
+  float ax, ay, az;      // Cone::ax, ay, az
+  float sin_t, cos_t;    // Cone::sin_t, cos_t
+  uint32_t wide;         // Cone::wide (0 or 1)
+  uint32_t tile_x, tile_y;
+};
+static_assert(sizeof(TileRec) == 32 && alignof(TileRec) == 32, "one s_load_dwordx8 per tile");
+
+// Bytes of the records of a grid of `tiles` tiles.  They ride with the directions -- filled,
+// kept and dropped with them -- and are not counted against SFRT_OPT_RAY_CACHE_MB (0.3 % of
+// the directions' size at four pixels per lane, 1 % at one).
+inline long long tile_rec_bytes(long long tiles) { return tiles * (long long)sizeof(TileRec); }
+
+// One grow-only device buffer of a chain's cache and its size, without a HIP call of its own:
+// the caller passes how to free and how to allocate (sfrt_world.cpp: stream-ordered, on the
+// chain's stream; tests/native/tilerec_check.cpp: counters).
+struct CacheBuf {
+  void* ptr = nullptr;
+  long long bytes = 0;
+
+  // Room for `need` bytes: a buffer that is large enough stays (its contents too), a smaller
+  // one is freed (free_fn(ptr) -> bool) and replaced (alloc_fn(need) -> pointer or null).
+  // false: the buffer may be gone (bytes == 0) and nothing may be read from it.
+  template <class Free, class Alloc>
+  bool reserve(long long need, Free&& free_fn, Alloc&& alloc_fn) {
+    if (need <= 0) return false;
+    if (need <= bytes) return true;
+    if (ptr && !free_fn(ptr)) return false;
+    ptr = nullptr;
+    bytes = 0;
+    ptr = alloc_fn(need);
+    if (!ptr) return false;
+    bytes = need;
+    return true;
+  }
+  template <class Free>
+  void release(Free&& free_fn) {
+    if (ptr) (void)free_fn(ptr);
+    ptr = nullptr;
+    bytes = 0;
+  }
+};
 
 enum class RayAction {
   kTrace,  // today's kernel; the cache is neither read nor written

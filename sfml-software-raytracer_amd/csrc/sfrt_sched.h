@@ -53,16 +53,22 @@ struct TileSched {
   bool probed = false;           // a timing-probe launch rewrote cost[k % 2] since k last moved
   // The chain's primary-ray-direction cache (sfrt_raycache.h; the sphere renderer only): a
   // stream-ordered buffer like order[] and cost[], used by the chain's own launches alone.  A
-  // takeover by another stream keeps it (begin() has waited for the device by then).
+  // takeover by another stream keeps it (begin() has waited for the device by then).  The tile
+  // records (TileRec) live and die with the directions: one policy, one key, two buffers.
   RayCachePolicy ray_policy;
-  float* ray_buf = nullptr;
-  long long ray_bytes = 0;
+  CacheBuf ray_dirs;  // the directions (ray_cache_bytes)
+  CacheBuf ray_recs;  // the tile records (tile_rec_bytes)
+
+  // Both buffers freed by the host (the device has drained, or the chain is going away).
+  void release_ray_cache() {
+    const auto free_now = [](void* p) { return hipFree(p) == hipSuccess; };
+    ray_dirs.release(free_now);
+    ray_recs.release(free_now);
+    ray_policy.invalidate();
+  }
 
   void release() {
-    (void)hipFree(ray_buf);
-    ray_buf = nullptr;
-    ray_bytes = 0;
-    ray_policy.invalidate();
+    release_ray_cache();
     for (int q = 0; q < 2; q++) {
       (void)hipFree(order[q]);
       (void)hipFree(cost[q]);

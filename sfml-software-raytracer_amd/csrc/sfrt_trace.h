@@ -91,6 +91,8 @@ struct InlineArgs {
   SphereRec s[kInlineSpheres];
 };
 
+struct TileRec;  // sfrt_raycache.h
+
 struct PixelDump {
   float pos[3];
   int draw;
@@ -114,15 +116,17 @@ struct DumpArgs {
 // sphere_trace.hip.  dump != nullptr: the DUMP instantiation of the kernel the table picks.
 // done_event (hipEvent_t, may be null): recorded by the list kernel's own completion (its stop
 // event; the inline kernel, which reads no device records, takes none).
-// ray_cache (may be null): the chain's ray cache, filled for this very f by launch_ray_fill
-// earlier on the same stream -- the launch then loads its directions from it (an ordered,
+// ray_cache, tile_recs (both null, or both set): the chain's ray cache and tile records, filled
+// for this very f by launch_ray_fill earlier on the same stream -- the launch then loads its
+// directions, its tiles' culling cones and their grid positions from them (an ordered,
 // non-dump launch only).
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump = nullptr, void* done_event = nullptr,
-                 const float* ray_cache = nullptr);
+                 const float* ray_cache = nullptr, const TileRec* tile_recs = nullptr);
 // Fills ray_cache (ray_cache_bytes(tiles, rays) bytes, sfrt_raycache.h, of the grid
-// trace_tile_key names) with the primary directions of f's rays, tile-major.
-int launch_ray_fill(const FrameRec& f, float* ray_cache, void* stream);
+// trace_tile_key names) with the primary directions of f's rays, tile-major, and tile_recs
+// (tile_rec_bytes(tiles) bytes) with the tiles' records.
+int launch_ray_fill(const FrameRec& f, float* ray_cache, TileRec* tile_recs, void* stream);
 // "release" for the shipped build; "diagnostic" (-DSFRT_EXP: wrong bytes by design) or
 // "ab" (EXTRA build flags, tools/ab_libs.py) otherwise.
 const char* trace_build_flavour();

@@ -152,6 +152,7 @@ struct sfrt_world {
   sfrt::RayKey ray_key{};
   sfrt::RayAction ray_action = sfrt::RayAction::kTrace;
   const float* ray_cache = nullptr;
+  const sfrt::TileRec* tile_recs = nullptr;  // the tile records that go with ray_cache
   int64_t ray_cached_frames = 0, ray_fills = 0;
   // Device copies of the sphere records for launches that read them from memory
   // (> 64 spheres, trace_points): a ring of slots, each with pinned staging and
@@ -409,19 +410,24 @@ struct sfrt_world {
                      std::memcmp(&chain_last.cam, &cam, sizeof cam) != 0;
     ray_active = false;
     ray_cache = nullptr;
+    tile_recs = nullptr;
     ray_action = sfrt::RayAction::kTrace;
     if (tile_order_on == 1 && p.tile_cost && sched.pending_key != 0) {
       ray_active = true;
       ray_key = make_ray_key(f, key);
       const long long bytes = sfrt::ray_cache_bytes(tiles, (int)((key >> 56) & 7));
-      ray_action = sched.ray_policy.decide(ray_key, bytes, sched.ray_bytes,
-                                           ray_bytes_held() - sched.ray_bytes,
+      ray_action = sched.ray_policy.decide(ray_key, bytes, sched.ray_dirs.bytes,
+                                           ray_bytes_held() - sched.ray_dirs.bytes,
                                            (long long)ray_cache_mb << 20);
-      if (ray_action == sfrt::RayAction::kFill && !ray_fill(sched, f, bytes, s)) {
-        sched.ray_policy.invalidate();  // the buffer may be gone or half written
+      if (ray_action == sfrt::RayAction::kFill &&
+          !ray_fill(sched, f, bytes, sfrt::tile_rec_bytes(tiles), s)) {
+        sched.ray_policy.invalidate();  // the buffers may be gone or half written
         ray_action = sfrt::RayAction::kTrace;
       }
-      if (ray_action != sfrt::RayAction::kTrace) ray_cache = sched.ray_buf;
+      if (ray_action != sfrt::RayAction::kTrace) {
+        ray_cache = (const float*)sched.ray_dirs.ptr;
+        tile_recs = (const sfrt::TileRec*)sched.ray_recs.ptr;
+      }
     }
     return SFRT_OK;
   }
@@ -443,42 +449,45 @@ struct sfrt_world {
 
   long long ray_bytes_held() const {
     long long held = 0;
-    for (const sfrt::TileSched& c : scheds.chain) held += c.ray_bytes;
+    for (const sfrt::TileSched& c : scheds.chain) held += c.ray_dirs.bytes;
+    return held;
+  }
+  // The tile records' bytes: reported on their own, never counted against the budget.
+  long long tile_rec_bytes_held() const {
+    long long held = 0;
+    for (const sfrt::TileSched& c : scheds.chain) held += c.ray_recs.bytes;
     return held;
   }
 
-  // The chain's cache, grown if need be, filled for f on s (where the chain's launches run:
-  // sched.begin has waited for the device if another stream ran the last one).  false: the
-  // frame renders with today's kernel.
+  // The chain's cache -- directions and tile records --, each buffer grown if need be in the
+  // order of s, filled for f on s (where the chain's launches run: sched.begin has waited for
+  // the device if another stream ran the last one).  false: the frame renders with today's
+  // kernel.
   static bool ray_fill(sfrt::TileSched& sched, const sfrt::FrameRec& f, long long bytes,
-                       hipStream_t s) {
-    if (bytes > sched.ray_bytes) {
-      if (sched.ray_buf && hipFreeAsync(sched.ray_buf, s) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-      }
-      sched.ray_buf = nullptr;
-      sched.ray_bytes = 0;
-      if (hipMallocAsync((void**)&sched.ray_buf, (size_t)bytes, s) != hipSuccess) {
-        (void)hipGetLastError();  // no memory for it: not an error of the frame
-        sched.ray_buf = nullptr;
-        return false;
-      }
-      sched.ray_bytes = bytes;
-    }
-    return sfrt::launch_ray_fill(f, sched.ray_buf, s) == 0;
+                       long long rec_bytes, hipStream_t s) {
+    const auto free_on_s = [s](void* p) {
+      if (hipFreeAsync(p, s) == hipSuccess) return true;
+      (void)hipGetLastError();
+      return false;
+    };
+    const auto alloc_on_s = [s](long long n) -> void* {
+      void* p = nullptr;
+      if (hipMallocAsync(&p, (size_t)n, s) == hipSuccess) return p;
+      (void)hipGetLastError();  // no memory for it: not an error of the frame
+      return nullptr;
+    };
+    if (!sched.ray_dirs.reserve(bytes, free_on_s, alloc_on_s) ||
+        !sched.ray_recs.reserve(rec_bytes, free_on_s, alloc_on_s))
+      return false;
+    return sfrt::launch_ray_fill(f, (float*)sched.ray_dirs.ptr,
+                                 (sfrt::TileRec*)sched.ray_recs.ptr, s) == 0;
   }
 
   // SFRT_OPT_RAY_CACHE_MB lowered below what the chains hold: every cache goes.  The chains'
   // streams may be gone (sfrt_sched.h), so the host waits for the device.
   int ray_release_all() {
     HIP_TRY(hipDeviceSynchronize());
-    for (sfrt::TileSched& c : scheds.chain) {
-      (void)hipFree(c.ray_buf);
-      c.ray_buf = nullptr;
-      c.ray_bytes = 0;
-      c.ray_policy.invalidate();
-    }
+    for (sfrt::TileSched& c : scheds.chain) c.release_ray_cache();
     return SFRT_OK;
   }
 
@@ -842,7 +851,9 @@ int sfrt_world_set_option(sfrt_world* w, int option, int value) {
   }
   if (option == SFRT_OPT_RAY_CACHE_MB) {
     if (value < 0) return SFRT_E_INVALID;
-    if (((long long)value << 20) < w->ray_bytes_held()) {
+    // (0 also frees tile records left without directions by a fill that found no memory)
+    if (((long long)value << 20) < w->ray_bytes_held() ||
+        (value == 0 && w->tile_rec_bytes_held() > 0)) {
       sfrt::DeviceGuard g(w->device);
       const int rc = w->ray_release_all();
       if (rc) return rc;
@@ -862,6 +873,13 @@ int sfrt_world_ray_cache_stats(const sfrt_world* w, int64_t* cached_frames, int6
   *cached_frames = w->ray_cached_frames;
   *fills = w->ray_fills;
   *bytes = w->ray_bytes_held();
+  return SFRT_OK;
+}
+
+int sfrt_world_tile_record_bytes(const sfrt_world* w, int64_t* bytes) {
+  if (!w || !bytes) return SFRT_E_INVALID;
+  std::lock_guard<std::mutex> lk(w->mu);
+  *bytes = w->tile_rec_bytes_held();
   return SFRT_OK;
 }
 
@@ -978,7 +996,7 @@ int sfrt_world_render_band(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes,
   HIP_TRY(w->tex_written.before_read(s));
   if ((rc = w->sched_begin(f, s))) return rc;
   if ((rc = w->sched_end(f, s, sfrt::launch_trace(f, recs.data(), s, nullptr, w->ring_event(),
-                                                  w->ray_cache) == 0)))
+                                                  w->ray_cache, w->tile_recs) == 0)))
     return rc;
   if ((rc = w->launched_with())) return rc;
   return SFRT_OK;
@@ -1135,7 +1153,7 @@ int sfrt_world_submit_frame(sfrt_world* w, uint8_t* pixels, int64_t* ticket) {
   if ((rc = w->sched_begin(f, w->stream))) return rc;  // adaptive tile order, as render_band
   if ((rc = w->sched_end(f, w->stream,
                          sfrt::launch_trace(f, recs.data(), w->stream, nullptr, w->ring_event(),
-                                            w->ray_cache) == 0)))
+                                            w->ray_cache, w->tile_recs) == 0)))
     return rc;
   if ((rc = w->launched_with())) return rc;
   HIP_TRY(hipEventRecord(slot.rendered, w->stream));

@@ -27,6 +27,7 @@
 #include "sfrt_device.h"
 #include "sfrt_math.h"
 #include "sfrt_probe.h"
+#include "sfrt_raycache.h"
 #include "sfrt_trace.h"
 
 #pragma clang fp contract(off)
@@ -409,6 +410,43 @@ __device__ __forceinline__ Cone tile_cone_corners(const FrameRec& f, int tile_x,
   return c;
 }
 
+// The tile's cone as the trace kernels and k_ray_fill both take it.
+// R >= 3: four corner rays per wave are cheaper than R rays per lane (profiles/ab/r3_ab9)
+template <int R, int SS>
+__device__ __forceinline__ Cone tile_cone(const FrameRec& f, int tile_x, int tile_y, int lane,
+                                          const float (&dx)[R], const float (&dy)[R],
+                                          const float (&dz)[R]) {
+  if constexpr (R >= 3) return tile_cone_corners<R, SS>(f, tile_x, tile_y, lane);
+  else return tile_cone_r<R, SS>(f, tile_x, tile_y, dx, dy, dz);
+}
+
+// The tile records (sfrt_raycache.h TileRec; DESIGN.md 5 "Ray cache"): tile_cone's result and
+// the tile's grid position, which depend on nothing outside the launch's RayKey.  Written by
+// lane 0 of k_ray_fill's wave (plain vector stores); read like a sphere record (rec_at): the
+// buffer is written only by the fill kernel that precedes the launch on its stream, never
+// while a launch runs, so a wave-uniform load through the constant address space is one
+// scalar 8-dword load.  The byte offset is 64-bit: an ordered grid has up to 2^28 tiles.
+__device__ __forceinline__ void tile_rec_store(TileRec* __restrict__ tr, int tile, int tile_x,
+                                               int tile_y, const Cone& c) {
+  TileRec t;
+  t.ax = c.ax; t.ay = c.ay; t.az = c.az;
+  t.sin_t = c.sin_t; t.cos_t = c.cos_t;
+  t.wide = c.wide ? 1u : 0u;
+  t.tile_x = (uint32_t)tile_x; t.tile_y = (uint32_t)tile_y;
+  tr[tile] = t;
+}
+__device__ __forceinline__ TileRec tile_rec_at(const TileRec* p, int tile) {
+  const __attribute__((address_space(4))) uint32_t* q =
+      (const __attribute__((address_space(4))) uint32_t*)(
+          (const __attribute__((address_space(4))) char*)p + (size_t)tile * sizeof(TileRec));
+  uint32_t w[sizeof(TileRec) / 4];
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(TileRec) / 4); i++) w[i] = q[i];
+  TileRec r;
+  __builtin_memcpy(&r, w, sizeof r);
+  return r;
+}
+
 // L = +0 for a lane's R rays at the start of a march step, two registers per
 // v_mov_b64 (left to itself the compiler copies one zero register into three
 // others and then pairs them: five moves a step for R = 4, not two).
@@ -484,12 +522,15 @@ __device__ __forceinline__ bool pass_body_r(const float (&ss)[R], float s_pass, 
 // stores.  S divides the tile's 8 rows and 8-column slots, and the subset's width and rows
 // are multiples of S, so a group is wholly inside the subset or wholly clamped duplicates.
 // CACHED: the rays' directions are loaded from the chain's ray cache rc (filled by k_ray_fill
-// for this launch's RayKey: the bits primary_dir gives) and not computed; all else is the same.
+// for this launch's RayKey: the bits primary_dir gives) and not computed, and the tile's cone
+// and grid position from the chain's tile records tr (the bits tile_cone gives); all else is
+// the same.
 template <int R, bool LIST, bool DUMP, class P, int SS = 0, bool CACHED = false>
 __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
                                                     const SphereRec* __restrict__ sph,
                                                     DumpArgs dmp,
-                                                    const float* __restrict__ rc = nullptr) {
+                                                    const float* __restrict__ rc = nullptr,
+                                                    const TileRec* tr = nullptr) {
   static_assert(SS == 0 || !DUMP, "trace_points dumps the 1x pixel");
   static_assert(!CACHED || !DUMP, "the DUMP kernels compute their directions");
   const int lane = threadIdx.x & 63;
@@ -507,9 +548,18 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   }
   uint32_t cls;  // the tile's class in the order (sfrt_device.h slot_tile)
   const int tile = slot_tile(f.tile_order, slot, ntiles, cls);
-  const int tile_y = tile / f.tiles_x;  // f.tiles_x = ceil(sub_w / (8 R)) for this kernel
-  const int tile_x = tile - tile_y * f.tiles_x;
-  if (tile_y * kTile >= f.sub_rows) return;  // grid rounding; uniform per wave
+  int tile_x, tile_y;
+  [[maybe_unused]] TileRec trec;
+  if constexpr (CACHED) {
+    if (tile >= ntiles) return;  // the same test as below, before the record is read
+    trec = tile_rec_at(tr, tile);  // issued ahead of ray_cache_load: the two latencies overlap
+    tile_x = (int)trec.tile_x;
+    tile_y = (int)trec.tile_y;
+  } else {
+    tile_y = tile / f.tiles_x;  // f.tiles_x = ceil(sub_w / (8 R)) for this kernel
+    tile_x = tile - tile_y * f.tiles_x;
+    if (tile_y * kTile >= f.sub_rows) return;  // grid rounding; uniform per wave
+  }
   probe.tile_begin();
   [[maybe_unused]] const int b = f.sub_row0 + tile_y * kTile + (lane >> 3);
   const int b_end = f.sub_row0 + f.sub_rows;
@@ -550,9 +600,14 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   float lo = -__builtin_inff(), hi = __builtin_inff();
   int cidx = lane;        // sphere of culled-list entry `lane`
   if (windowed) {
-    // R >= 3: four corner rays per wave are cheaper than R rays per lane (profiles/ab/r3_ab9)
-    const Cone cone = R >= 3 ? tile_cone_corners<R, SS>(f, tile_x, tile_y, lane)
-                             : tile_cone_r<R, SS>(f, tile_x, tile_y, dx, dy, dz);
+    Cone cone;
+    if constexpr (CACHED) {
+      cone.ax = trec.ax; cone.ay = trec.ay; cone.az = trec.az;
+      cone.sin_t = trec.sin_t; cone.cos_t = trec.cos_t;
+      cone.wide = trec.wide != 0;
+    } else {
+      cone = tile_cone<R, SS>(f, tile_x, tile_y, lane, dx, dy, dz);
+    }
     if (!LIST) {
       m = cull_window(f, sph, 0, cone, lo, hi);
     } else {
@@ -842,9 +897,11 @@ __global__ __launch_bounds__(64) void k_trace_window_list_ss(FrameRec f) {
 // The ray cache's kernels (sfrt_raycache.h), again of their own.  k_ray_fill: one wave per tile
 // of the grid f.tiles_x x ceil(sub_rows / 8), row-major, stores the directions the kernels
 // above compute for that tile (the same primary_dir on the same indices under the same flags:
-// the same bits).  The _rc kernels are the four above with the directions loaded from rc.
+// the same bits) and, from lane 0, the tile's record (the same tile_cone on the same inputs).
+// The _rc kernels are the four above with the directions loaded from rc and the cone from tr.
 template <int R, int SS>
-__global__ __launch_bounds__(64) void k_ray_fill(FrameRec f, float* __restrict__ rc) {
+__global__ __launch_bounds__(64) void k_ray_fill(FrameRec f, float* __restrict__ rc,
+                                                 TileRec* __restrict__ tr) {
   const int lane = threadIdx.x & 63;
   const int tile = (int)blockIdx.x;
   const int tile_y = tile / f.tiles_x;
@@ -853,16 +910,20 @@ __global__ __launch_bounds__(64) void k_ray_fill(FrameRec f, float* __restrict__
   float dx[R], dy[R], dz[R];
   tile_dirs<R, SS>(f, tile_x, tile_y, lane, dx, dy, dz);
   ray_cache_store<R>(rc, tile, lane, dx, dy, dz);
+  const Cone cone = tile_cone<R, SS>(f, tile_x, tile_y, lane, dx, dy, dz);  // every lane: wave ops
+  if (lane == 0) tile_rec_store(tr, tile, tile_x, tile_y, cone);
 }
 template <int R, int SS>
 __global__ __launch_bounds__(64, 8) void k_trace_window_r_rc(InlineArgs args,
-                                                             const float* __restrict__ rc) {
-  trace_tile_window_r<R, false, false, ActiveProbe, SS, true>(args.f, args.s, DumpArgs{}, rc);
+                                                             const float* __restrict__ rc,
+                                                             const TileRec* tr) {
+  trace_tile_window_r<R, false, false, ActiveProbe, SS, true>(args.f, args.s, DumpArgs{}, rc, tr);
 }
 template <int R, int SS>
 __global__ __launch_bounds__(64) void k_trace_window_list_rc(FrameRec f,
-                                                             const float* __restrict__ rc) {
-  trace_tile_window_r<R, true, false, ActiveProbe, SS, true>(f, f.spheres, DumpArgs{}, rc);
+                                                             const float* __restrict__ rc,
+                                                             const TileRec* tr) {
+  trace_tile_window_r<R, true, false, ActiveProbe, SS, true>(f, f.spheres, DumpArgs{}, rc, tr);
 }
 
 // The DUMP instantiations of both (sfrt_world_trace_points): the shipped march and
@@ -953,56 +1014,62 @@ void launch_list_ss(int rays, dim3 gr, hipStream_t s, hipEvent_t ev, const Frame
 
 // The ray-cache kernels by (rays, ss).
 template <int SS>
-void launch_inline_rc(int rays, dim3 gr, hipStream_t s, const InlineArgs& args, const float* rc) {
+void launch_inline_rc(int rays, dim3 gr, hipStream_t s, const InlineArgs& args, const float* rc,
+                      const TileRec* tr) {
   const dim3 b(64);
   switch (rays) {
-    case 1: hipLaunchKernelGGL((k_trace_window_r_rc<1, SS>), gr, b, 0, s, args, rc); break;
-    case 2: hipLaunchKernelGGL((k_trace_window_r_rc<2, SS>), gr, b, 0, s, args, rc); break;
-    case 3: hipLaunchKernelGGL((k_trace_window_r_rc<3, SS>), gr, b, 0, s, args, rc); break;
-    default: hipLaunchKernelGGL((k_trace_window_r_rc<4, SS>), gr, b, 0, s, args, rc); break;
+    case 1: hipLaunchKernelGGL((k_trace_window_r_rc<1, SS>), gr, b, 0, s, args, rc, tr); break;
+    case 2: hipLaunchKernelGGL((k_trace_window_r_rc<2, SS>), gr, b, 0, s, args, rc, tr); break;
+    case 3: hipLaunchKernelGGL((k_trace_window_r_rc<3, SS>), gr, b, 0, s, args, rc, tr); break;
+    default: hipLaunchKernelGGL((k_trace_window_r_rc<4, SS>), gr, b, 0, s, args, rc, tr); break;
   }
 }
 template <int SS>
 void launch_list_rc(int rays, dim3 gr, hipStream_t s, hipEvent_t ev, const FrameRec& g,
-                    const float* rc) {
+                    const float* rc, const TileRec* tr) {
   const dim3 b(64);
   switch (rays) {
-    case 1: hipExtLaunchKernelGGL((k_trace_window_list_rc<1, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc); break;
-    case 2: hipExtLaunchKernelGGL((k_trace_window_list_rc<2, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc); break;
-    case 3: hipExtLaunchKernelGGL((k_trace_window_list_rc<3, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc); break;
-    default: hipExtLaunchKernelGGL((k_trace_window_list_rc<4, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc); break;
+    case 1: hipExtLaunchKernelGGL((k_trace_window_list_rc<1, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc,
+                                  tr); break;
+    case 2: hipExtLaunchKernelGGL((k_trace_window_list_rc<2, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc,
+                                  tr); break;
+    case 3: hipExtLaunchKernelGGL((k_trace_window_list_rc<3, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc,
+                                  tr); break;
+    default: hipExtLaunchKernelGGL((k_trace_window_list_rc<4, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc,
+                                  tr); break;
   }
 }
 template <int SS>
-void launch_fill(int rays, dim3 gr, hipStream_t s, const FrameRec& g, float* rc) {
+void launch_fill(int rays, dim3 gr, hipStream_t s, const FrameRec& g, float* rc, TileRec* tr) {
   const dim3 b(64);
   switch (rays) {
-    case 1: hipLaunchKernelGGL((k_ray_fill<1, SS>), gr, b, 0, s, g, rc); break;
-    case 2: hipLaunchKernelGGL((k_ray_fill<2, SS>), gr, b, 0, s, g, rc); break;
-    case 3: hipLaunchKernelGGL((k_ray_fill<3, SS>), gr, b, 0, s, g, rc); break;
-    default: hipLaunchKernelGGL((k_ray_fill<4, SS>), gr, b, 0, s, g, rc); break;
+    case 1: hipLaunchKernelGGL((k_ray_fill<1, SS>), gr, b, 0, s, g, rc, tr); break;
+    case 2: hipLaunchKernelGGL((k_ray_fill<2, SS>), gr, b, 0, s, g, rc, tr); break;
+    case 3: hipLaunchKernelGGL((k_ray_fill<3, SS>), gr, b, 0, s, g, rc, tr); break;
+    default: hipLaunchKernelGGL((k_ray_fill<4, SS>), gr, b, 0, s, g, rc, tr); break;
   }
 }
 
 }  // namespace
 
-int launch_ray_fill(const FrameRec& f, float* ray_cache, void* stream) {
+int launch_ray_fill(const FrameRec& f, float* ray_cache, TileRec* tile_recs, void* stream) {
   long long tiles = 0;
-  if (!ray_cache || f.ss < 0 || f.ss > 2 || trace_tile_key(f, &tiles) == 0 || tiles > 0x7fffffffLL)
+  if (!ray_cache || !tile_recs || f.ss < 0 || f.ss > 2 || trace_tile_key(f, &tiles) == 0 || tiles > 0x7fffffffLL)
     return -1;
   const int rays = trace_rays(f, true);
   FrameRec g = f;
   g.tiles_x = (f.sub_w + rays * kTile - 1) / (rays * kTile);
   const dim3 gr((unsigned)tiles);
   hipStream_t s = (hipStream_t)stream;
-  if (f.ss == 0) launch_fill<0>(rays, gr, s, g, ray_cache);
-  else if (f.ss == 1) launch_fill<1>(rays, gr, s, g, ray_cache);
-  else launch_fill<2>(rays, gr, s, g, ray_cache);
+  if (f.ss == 0) launch_fill<0>(rays, gr, s, g, ray_cache, tile_recs);
+  else if (f.ss == 1) launch_fill<1>(rays, gr, s, g, ray_cache, tile_recs);
+  else launch_fill<2>(rays, gr, s, g, ray_cache, tile_recs);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
-                 const DumpArgs* dump, void* done_event, const float* ray_cache) {
+                 const DumpArgs* dump, void* done_event, const float* ray_cache,
+                 const TileRec* tile_recs) {
   const long long tiles_y = (f.sub_rows + kTile - 1) / kTile;
   if (tiles_y <= 0 || f.sub_w <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
@@ -1023,15 +1090,16 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
   if (f.ss < 0 || f.ss > 2 || (f.ss && dump)) return -1;  // trace_points dumps the 1x pixel
   if (f.ss && (f.sub_w | f.sub_row0 | f.sub_rows) & ((1 << f.ss) - 1)) return -1;  // whole groups
   // the cache is laid out for the ordered kernel's grid (launch_ray_fill), never dumped
+  if ((ray_cache != nullptr) != (tile_recs != nullptr)) return -1;
   if (ray_cache && (!ordered || !g.tile_cost || dump)) return -1;
   if (f.n <= kInlineSpheres) {
     InlineArgs args;
     args.f = g;
     for (int k = 0; k < f.n; k++) args.s[k] = host_spheres[k];
     if (ray_cache) {
-      if (f.ss == 0) launch_inline_rc<0>(rays, gr, s, args, ray_cache);
-      else if (f.ss == 1) launch_inline_rc<1>(rays, gr, s, args, ray_cache);
-      else launch_inline_rc<2>(rays, gr, s, args, ray_cache);
+      if (f.ss == 0) launch_inline_rc<0>(rays, gr, s, args, ray_cache, tile_recs);
+      else if (f.ss == 1) launch_inline_rc<1>(rays, gr, s, args, ray_cache, tile_recs);
+      else launch_inline_rc<2>(rays, gr, s, args, ray_cache, tile_recs);
     } else if (f.ss) {
       if (f.ss == 1) launch_inline_ss<1>(rays, gr, s, args);
       else launch_inline_ss<2>(rays, gr, s, args);
@@ -1054,9 +1122,9 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
     return -1;  // the list kernel's lookahead reads culled-list lane 63 (a sphere index < n)
   } else if (ray_cache) {
     const hipEvent_t ev = (hipEvent_t)done_event;
-    if (f.ss == 0) launch_list_rc<0>(rays, gr, s, ev, g, ray_cache);
-    else if (f.ss == 1) launch_list_rc<1>(rays, gr, s, ev, g, ray_cache);
-    else launch_list_rc<2>(rays, gr, s, ev, g, ray_cache);
+    if (f.ss == 0) launch_list_rc<0>(rays, gr, s, ev, g, ray_cache, tile_recs);
+    else if (f.ss == 1) launch_list_rc<1>(rays, gr, s, ev, g, ray_cache, tile_recs);
+    else launch_list_rc<2>(rays, gr, s, ev, g, ray_cache, tile_recs);
   } else if (f.ss) {
     const hipEvent_t ev = (hipEvent_t)done_event;
     if (f.ss == 1) launch_list_ss<1>(rays, gr, s, ev, g);

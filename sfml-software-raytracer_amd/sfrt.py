@@ -61,6 +61,7 @@ ABI_SYMBOLS = (
     "sfrt_band_unpack", "sfrt_world_alpha_binary", "sfrt_multi_transport_library",
     "sfrt_multi_use_test_transport", "sfrt_world_get_option",
     "sfrt_voxel_get_option", "sfrt_glsl_get_option", "sfrt_world_ray_cache_stats",
+    "sfrt_world_tile_record_bytes",
 )
 
 SFRT_MULTI_AUTO, SFRT_MULTI_RCCL, SFRT_MULTI_PEER = 0, 1, 2
@@ -138,6 +139,7 @@ def lib() -> ctypes.CDLL:
         "sfrt_world_get_option": ([W, c_int, P(c_int)], c_int),
         "sfrt_world_ray_cache_stats": ([W, P(ctypes.c_int64), P(ctypes.c_int64),
                                         P(ctypes.c_int64)], c_int),
+        "sfrt_world_tile_record_bytes": ([W, P(ctypes.c_int64)], c_int),
         "sfrt_world_submit_frame": ([W, vp, P(ctypes.c_int64)], c_int),
         "sfrt_world_wait_frame": ([W, ctypes.c_int64], c_int),
         "sfrt_host_alloc": ([P(vp), ctypes.c_int64], c_int),
@@ -378,6 +380,13 @@ class World:
         _check(lib().sfrt_world_ray_cache_stats(self._h, ctypes.byref(c), ctypes.byref(f),
                                                 ctypes.byref(b)), "ray_cache_stats")
         return {"cached_frames": c.value, "fills": f.value, "bytes": b.value}
+
+    def tile_record_bytes(self) -> int:
+        """Device bytes of the tile records that ride with the cached directions
+        (sfrt_world_tile_record_bytes): 32 per tile of every filled cache, 0 when off."""
+        b = ctypes.c_int64()
+        _check(lib().sfrt_world_tile_record_bytes(self._h, ctypes.byref(b)), "tile_record_bytes")
+        return b.value
 
     def set_scene(self, scene, width: int, height: int) -> None:
         """Load a scenes.Scene (spheres verbatim, camera pose) at width x height."""

@@ -4,8 +4,9 @@
     python tools/isa_block_profile.py run    KERNEL   # GPU: block executions per launch (JSON)
     python tools/isa_block_profile.py report KERNEL COUNTS.json [--pmc profiles/<tag>_traffic.json]
 
-KERNEL is one of: sphere (k_trace_window_r<4>, the headline), voxel (k_voxel_ordered), glsl
-(k_glsl_ordered).
+KERNEL is one of: sphere (k_trace_window_r<4>, the headline's uncached kernel), sphere_rc
+(k_trace_window_r_rc<4, 0>: the same launch served from the ray cache and the tile records, which
+is what the headline's steady state runs), voxel (k_voxel_ordered), glsl (k_glsl_ordered).
 
 Method.  The release kernel's assembly (hipcc -S of the product source, release flags plus
 -gline-tables-only, which only adds .loc directives: the kernel's instruction text is checked
@@ -51,6 +52,9 @@ MAX_BLOCKS = 64 * 12
 KERNELS = {
     "sphere": {"src": "sphere_trace.hip", "obj": "sphere_trace.o",
                "symbol": "_ZN4sfrt12_GLOBAL__N_116k_trace_window_rILi4EEEvNS_10InlineArgsE"},
+    "sphere_rc": {"src": "sphere_trace.hip", "obj": "sphere_trace.o",
+                  "symbol": "_ZN4sfrt12_GLOBAL__N_119k_trace_window_r_rcILi4ELi0EEEvNS_10InlineArgsEPKf"
+                            "PKNS_7TileRecE"},
     # k_voxel_ordered<false>: the launch without tile costs (the voxel default)
     "voxel": {"src": "voxel_trace.hip", "obj": "voxel_trace.o",
               "symbol": "_ZN4sfrt12_GLOBAL__N_115k_voxel_orderedILb0EEEvNS_8VoxFrameEii"},
@@ -367,9 +371,12 @@ def run(kind, frames=3):
         import scenes
         wd = sfrt.World(0)
         wd.load_texture(*scenes.load_floor())
+        if kind == "sphere":  # the uncached kernel runs in the steady state only with the cache off
+            wd.set_option(sfrt.SFRT_OPT_RAY_CACHE_MB, 0)
         w, h = 3840, 2160
         wd.set_scene(scenes.lcg64(), w, h)
         buf = torch.empty(h, w * 4, dtype=torch.uint8, device="cuda")
+        # (sphere_rc: the three warm-up frames are the uncached one, the fill and a first read)
         measure(str(w * h + 256), f"{w}x{h} lcg64 pose (0,0), adaptive order (+ the sorter)",
                 lambda: wd.render_band(buf.data_ptr(), w * 4, 0, h, 0))
         wd.check()
@@ -559,10 +566,11 @@ def regions_glsl(blocks):
     return region
 
 
-def regions_sphere(blocks):
-    """k_trace_window_r<4>: by helper function on the inline chain, else by the line of
-    trace_tile_window_r (or of one of its lambdas) the instruction belongs to."""
-    A = {k: src_anchor("sphere", v) for k, v in {
+def regions_sphere(blocks, kind="sphere"):
+    """k_trace_window_r<4> (and its cached twin, kind = "sphere_rc"): by helper function on the
+    inline chain, else by the line of trace_tile_window_r (or of one of its lambdas) the
+    instruction belongs to."""
+    A = {k: src_anchor(kind, v) for k, v in {
         "fn_first": "const int lane = threadIdx.x & 63;\n  P probe;",
         "windowed": "const bool windowed = f.cull && l0 > 0.0f;",
         "entry_lambda": "auto entry = [&](uint32_t e)",
@@ -580,7 +588,8 @@ def regions_sphere(blocks):
         "fn_last": "probe.tile_end(px_out(0), lane_s, valid(0), trips, slot, m);",
     }.items() if k != "slots_loop"}
     helpers = [("sort_tiles", "sorter"), ("shade_texel", "shade"), ("shade_rgba", "shade"),
-               ("primary_dir", "ray_setup"), ("tile_cone", "cull"), ("cull_window", "cull"),
+               ("primary_dir", "ray_setup"), ("ray_cache_load", "ray_setup"),
+               ("tile_cone", "cull"), ("tile_rec_at", "cull"), ("cull_window", "cull"),
                ("dist2", "visit_test"), ("pass_body_r", "pass_body"), ("zero_steps", "step_control")]
 
     def region(b, ch):
@@ -617,7 +626,8 @@ def regions_sphere(blocks):
     return region
 
 
-REGIONS = {"voxel": regions_voxel, "glsl": regions_glsl, "sphere": regions_sphere}
+REGIONS = {"voxel": regions_voxel, "glsl": regions_glsl, "sphere": regions_sphere,
+           "sphere_rc": lambda blocks: regions_sphere(blocks, "sphere_rc")}
 
 
 def report(kind, counts_path, pmc_path):
