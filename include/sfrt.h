@@ -120,6 +120,55 @@ SFRT_API int sfrt_world_update_image(sfrt_world* w, uint8_t* pixels, int ystart,
 SFRT_API int sfrt_world_render_band(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes, int row0,
                            int rows, void* hip_stream);
 SFRT_API int sfrt_world_check(sfrt_world* w, void* hip_stream);
+
+/* ---- the frame fill's per-pixel planes: depth, sphere index, march steps ----
+ * For pixel (i, j) of the world's width x height frame there are three optional planes of
+ * 4 bytes per pixel, written by the same launch that writes the colour:
+ *   depth  (float):   the binary32 value of VLength(r->pos - cam.pos) as SphereWorld.cpp:375
+ *                     evaluates it -- the operand of std::max(.., 3.0f), not the clamped
+ *                     value: sqrtf((ex*ex + ey*ey) + ez*ez) with e = pos - cam per component,
+ *                     correctly rounded, no contraction.  (The colour's brightness is 1 for
+ *                     every depth below 3 and carries no depth there; this plane does.)
+ *   sphere (int32_t): drawSphere after the march (SphereWorld.cpp:360-369), an index into the
+ *                     world's current sphere order, the order sfrt_world_get_spheres returns.
+ *   steps  (int32_t): the loop trips of SphereWorld.cpp:362, the first one included: the same
+ *                     count as sfrt_pixel_dump.iters.
+ * With SFRT_OPT_SUPERSAMPLE S = 2 or 4 the colour is the box-filtered pixel as always, and the
+ * three planes describe the output pixel's FIRST SAMPLE, sample pixel (S*i, S*j) of the
+ * S*width x S*height frame: point-sampled, as a resolved depth buffer takes sample 0; no
+ * filtered, minimum or per-sample depth.
+ * The planes do not depend on the texel: a frame whose status is SFRT_E_TEXEL still has defined
+ * planes.  Pixels of a ray that hit the march guard (SFRT_E_MARCH_LIMIT) are unspecified, as
+ * their colour is.
+ * Planes must not overlap each other or the colour target; that is the caller's duty.
+ * Both calls below return SFRT_E_INVALID, with nothing queued or written, when all three
+ * planes are NULL, or (render_band_aux) a non-NULL plane's pitch is not a multiple of 4 or is
+ * below 4*width; a NULL plane's pitch is ignored.  The plain calls' own argument checks apply
+ * unchanged, and the plain calls keep their behaviour exactly.
+ * The planes come from kernels of their own, which compute their ray directions: an aux call
+ * neither reads, fills nor invalidates the ray cache (SFRT_OPT_RAY_CACHE_MB) and leaves the
+ * counters of sfrt_world_ray_cache_stats alone.  sfrt_world_submit_frame, sfrt_multi_* and the
+ * voxel and GLSL renderers have no planes. */
+typedef struct {
+  void* depth;  int64_t depth_pitch_bytes;   /* float   per pixel, or NULL */
+  void* sphere; int64_t sphere_pitch_bytes;  /* int32_t per pixel, or NULL */
+  void* steps;  int64_t steps_pitch_bytes;   /* int32_t per pixel, or NULL */
+} sfrt_aux_planes;
+/* sfrt_world_render_band plus the planes (device memory on this world's device): same rows,
+ * same global row index, same stream semantics, same status word, same place in the adaptive
+ * tile order (sfrt_world_row_costs works after it); row r of a plane at
+ * plane + (r - row0) * its pitch. */
+SFRT_API int sfrt_world_render_band_aux(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes,
+                                        const sfrt_aux_planes* aux, int row0, int rows,
+                                        void* hip_stream);
+/* sfrt_world_update_image plus host planes of width*height elements (pitch 4*width); any of
+ * depth / sphere / steps may be NULL (not all); only addressed pixels are written, in every
+ * plane.  On SFRT_E_TEXEL the planes are written and `pixels` is left as
+ * sfrt_world_update_image leaves it on that status (unwritten). */
+SFRT_API int sfrt_world_update_image_aux(sfrt_world* w, uint8_t* pixels, float* depth,
+                                         int32_t* sphere, int32_t* steps, int ystart, int yadd,
+                                         int xstart, int xadd);
+
 /* Estimated work per pixel row of the world's last frame fill that ran in the adaptive
  * tile order (sfrt_world_render_band, sfrt_world_submit_frame; SFRT_OPT_TILE_ORDER on):
  * *row0, *rows = the global rows it covered, costs[i] (i < *rows <= capacity) = the

@@ -165,6 +165,21 @@ class SphereWorld {
     check(sfrt_world_render_band(w_, dev_pixels, pitch_bytes, row0, rows, hip_stream),
           "render_band");
   }
+  // Both with the per-pixel planes (sfrt.h sfrt_aux_planes: hit distance before the
+  // brightness clamp, drawSphere, march steps; any may be null, not all): for compositing
+  // sprites behind the cave walls, picking and cost maps.
+  void UpdateImageAux(uint8_t* pixels, float* depth, int32_t* sphere, int32_t* steps,
+                      short ystart, short yadd, short xstart, short xadd) {
+    push_state();
+    check(sfrt_world_update_image_aux(w_, pixels, depth, sphere, steps, ystart, yadd, xstart, xadd),
+          "UpdateImageAux");
+  }
+  void RenderBandAux(void* dev_pixels, int64_t pitch_bytes, const sfrt_aux_planes& aux, int row0,
+                     int rows, void* hip_stream) {
+    push_state();
+    check(sfrt_world_render_band_aux(w_, dev_pixels, pitch_bytes, &aux, row0, rows, hip_stream),
+          "render_band_aux");
+  }
   void Check(void* hip_stream = nullptr) { check(sfrt_world_check(w_, hip_stream), "check"); }
   // SFRT_OPT_* (sfrt.h): SFRT_OPT_SUPERSAMPLE 2 or 4 box-filters S x S samples per pixel
   // inside the frame-fill kernel; width, height and every buffer stay in output pixels.

@@ -113,7 +113,22 @@ struct DumpArgs {
   PixelDump* out;      // npix records
 };
 
+// The optional per-pixel planes of the frame fill (sfrt_world_render_band_aux),
+// written by the AUX instantiation of the same march and shading beside the colour: 4 bytes
+// per output pixel each, addressed like the colour -- pixel (a, b) at
+// plane + ((b - sub_row0) >> ss) * pitch + (a >> ss) (pitches in elements) --, a null plane
+// is not written.  Supersampled, the output pixel's first sample (its group's leader lane).
+// A kernel argument of its own, as DumpArgs is: FrameRec's layout is every kernel's.
+struct AuxArgs {
+  float* depth;        // |pos - cam| of the hit (shade_texel's bl, before max(.., 3.0f))
+  int32_t* sphere;     // drawSphere
+  int32_t* steps;      // loop trips of SphereWorld.cpp:362 (the host's first one included)
+  long long depth_pitch, sphere_pitch, steps_pitch;
+};
+
 // sphere_trace.hip.  dump != nullptr: the DUMP instantiation of the kernel the table picks.
+// aux != nullptr (with at least one plane set): its AUX instantiation -- never with dump or
+// the ray cache.
 // done_event (hipEvent_t, may be null): recorded by the list kernel's own completion (its stop
 // event; the inline kernel, which reads no device records, takes none).
 // ray_cache, tile_recs (both null, or both set): the chain's ray cache and tile records, filled
@@ -122,7 +137,8 @@ struct DumpArgs {
 // non-dump launch only).
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump = nullptr, void* done_event = nullptr,
-                 const float* ray_cache = nullptr, const TileRec* tile_recs = nullptr);
+                 const float* ray_cache = nullptr, const TileRec* tile_recs = nullptr,
+                 const AuxArgs* aux = nullptr);
 // Fills ray_cache (ray_cache_bytes(tiles, rays) bytes, sfrt_raycache.h, of the grid
 // trace_tile_key names) with the primary directions of f's rays, tile-major, and tile_recs
 // (tile_rec_bytes(tiles) bytes) with the tiles' records.

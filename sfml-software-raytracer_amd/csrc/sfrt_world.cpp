@@ -172,6 +172,12 @@ struct sfrt_world {
   size_t d_frame_px = 0;
   uint32_t* h_stage = nullptr;  // pinned D2H staging
   size_t h_stage_px = 0;
+  // The same pair per plane of sfrt_world_update_image_aux (depth, sphere, steps), grown the
+  // same way by the first call that asks for the plane.
+  uint32_t* d_aux[3] = {};
+  size_t d_aux_px[3] = {};
+  uint32_t* h_aux[3] = {};
+  size_t h_aux_px[3] = {};
   sfrt::RetiredHost retired_host;  // replaced pinned buffers (sfrt_host.h)
   std::vector<void*> retired_device;  // replaced record rings, freed with the world
   // --- frame pipeline (display path): render k+1 while frame k is copied ---
@@ -218,6 +224,10 @@ struct sfrt_world {
     relay.release();
     (void)hipFree(d_frame);
     (void)hipHostFree(h_stage);
+    for (int q = 0; q < 3; q++) {
+      (void)hipFree(d_aux[q]);
+      (void)hipHostFree(h_aux[q]);
+    }
     retired_host.release();
     for (void* p : retired_device) (void)hipFree(p);
     if (stream) (void)hipStreamDestroy(stream);
@@ -389,7 +399,10 @@ struct sfrt_world {
   }
 
   // Before a render_band / submit_frame launch on s: link f into the tile-order chain.
-  int sched_begin(sfrt::FrameRec& f, hipStream_t s) {
+  // aux (sfrt_world_render_band_aux): the launch joins the chain like any band but takes no
+  // part in the ray cache's policy -- it neither reads, fills nor invalidates the cache, and
+  // sched_end commits nothing for it.
+  int sched_begin(sfrt::FrameRec& f, hipStream_t s, bool aux = false) {
     long long tiles = 0;
     const long long key = tile_order_on ? sfrt::trace_tile_key(f, &tiles) : 0;
     sfrt::TileSchedPtrs p;
@@ -412,7 +425,7 @@ struct sfrt_world {
     ray_cache = nullptr;
     tile_recs = nullptr;
     ray_action = sfrt::RayAction::kTrace;
-    if (tile_order_on == 1 && p.tile_cost && sched.pending_key != 0) {
+    if (!aux && tile_order_on == 1 && p.tile_cost && sched.pending_key != 0) {
       ray_active = true;
       ray_key = make_ray_key(f, key);
       const long long bytes = sfrt::ray_cache_bytes(tiles, (int)((key >> 56) & 7));
@@ -896,9 +909,12 @@ int sfrt_world_get_option(const sfrt_world* w, int option, int* value) {
   }
 }
 
-int sfrt_world_update_image(sfrt_world* w, uint8_t* pixels, int ystart, int yadd, int xstart,
-                            int xadd) {
+// sfrt_world_update_image and sfrt_world_update_image_aux (planes: depth, sphere, steps as
+// host planes of width*height elements, any null; nullptr for the plain call).
+static int update_image_body(sfrt_world* w, uint8_t* pixels, void* const* planes, int ystart,
+                             int yadd, int xstart, int xadd) {
   if (!w || !pixels || ystart < 0 || xstart < 0 || yadd <= 0 || xadd <= 0) return SFRT_E_INVALID;
+  if (planes && !planes[0] && !planes[1] && !planes[2]) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
   int rc = w->validate();
   if (rc) return rc;
@@ -911,20 +927,26 @@ int sfrt_world_update_image(sfrt_world* w, uint8_t* pixels, int ystart, int yadd
   // Growth waits for no other stream (sfrt_host.h: hipFree / hipHostFree wait for the whole
   // device): the device frame stream-ordered on the world's stream, behind the last update_image
   // (which waited for its own copy); the old pinned staging retired.
-  if (w->d_frame_px < px) {
-    if (w->d_frame) HIP_TRY(hipFreeAsync(w->d_frame, w->stream));
-    w->d_frame = nullptr;
-    w->d_frame_px = 0;
-    HIP_TRY(hipMallocAsync((void**)&w->d_frame, px * 4, w->stream));
-    w->d_frame_px = px;
-  }
-  if (w->h_stage_px < px) {
-    w->retired_host.add(w->h_stage);
-    w->h_stage = nullptr;
-    w->h_stage_px = 0;
-    HIP_TRY(hipHostMalloc(&w->h_stage, px * 4, hipHostMallocDefault));
-    w->h_stage_px = px;
-  }
+  const auto grow = [&](uint32_t*& dev, size_t& dev_px, uint32_t*& host, size_t& host_px) -> int {
+    if (dev_px < px) {
+      if (dev) HIP_TRY(hipFreeAsync(dev, w->stream));
+      dev = nullptr;
+      dev_px = 0;
+      HIP_TRY(hipMallocAsync((void**)&dev, px * 4, w->stream));
+      dev_px = px;
+    }
+    if (host_px < px) {
+      w->retired_host.add(host);
+      host = nullptr;
+      host_px = 0;
+      HIP_TRY(hipHostMalloc(&host, px * 4, hipHostMallocDefault));
+      host_px = px;
+    }
+    return SFRT_OK;
+  };
+  if ((rc = grow(w->d_frame, w->d_frame_px, w->h_stage, w->h_stage_px))) return rc;
+  for (int q = 0; planes && q < 3; q++)
+    if (planes[q] && (rc = grow(w->d_aux[q], w->d_aux_px[q], w->h_aux[q], w->h_aux_px[q]))) return rc;
   sfrt::FrameRec f;
   std::vector<sfrt::SphereRec> recs;
   // Supersampled (S = 1 << ss): S x S samples per addressed pixel, start and strides in samples
@@ -941,37 +963,82 @@ int sfrt_world_update_image(sfrt_world* w, uint8_t* pixels, int ystart, int yadd
   f.tiles_x = (f.sub_w + sfrt::kTile - 1) / sfrt::kTile;
   f.out = w->d_frame;
   f.out_pitch = sub_w;
+  sfrt::AuxArgs aux{};
+  if (planes) {  // compact planes beside the compact frame
+    aux.depth = planes[0] ? (float*)w->d_aux[0] : nullptr;
+    aux.sphere = planes[1] ? (int32_t*)w->d_aux[1] : nullptr;
+    aux.steps = planes[2] ? (int32_t*)w->d_aux[2] : nullptr;
+    aux.depth_pitch = aux.sphere_pitch = aux.steps_pitch = sub_w;
+  }
   if ((rc = w->launchable(f))) return rc;
   rc = w->stage_spheres(f, recs, w->stream, false);
   if (rc) return rc;
-  if (sfrt::launch_trace(f, recs.data(), w->stream, nullptr, w->ring_event())) return SFRT_E_HIP;
+  if (sfrt::launch_trace(f, recs.data(), w->stream, nullptr, w->ring_event(), nullptr, nullptr,
+                         planes ? &aux : nullptr))
+    return SFRT_E_HIP;
   if ((rc = w->launched_with())) return rc;
   HIP_TRY(hipMemcpyAsync(w->h_stage, w->d_frame, px * 4, hipMemcpyDeviceToHost, w->stream));
+  for (int q = 0; planes && q < 3; q++)
+    if (planes[q])
+      HIP_TRY(hipMemcpyAsync(w->h_aux[q], w->d_aux[q], px * 4, hipMemcpyDeviceToHost, w->stream));
   rc = w->read_status(w->stream);
-  if (rc) return rc;
+  // the planes do not depend on the texel: a frame whose status is SFRT_E_TEXEL has them defined
+  if (rc && !(planes && rc == SFRT_E_TEXEL)) return rc;
   // Scatter the subset into the caller's frame: only addressed pixels are written.
   const size_t W = (size_t)w->width;
-  for (int bb = 0; bb < sub_h; bb++) {
-    const size_t j = (size_t)ystart + (size_t)bb * yadd;
-    const uint32_t* src = w->h_stage + (size_t)bb * sub_w;
-    uint8_t* row = pixels + j * W * 4;
-    if (xadd == 1) {
-      std::memcpy(row + (size_t)xstart * 4, src, (size_t)sub_w * 4);
-    } else {
-      for (int a = 0; a < sub_w; a++)
-        std::memcpy(row + ((size_t)xstart + (size_t)a * xadd) * 4, src + a, 4);
+  const auto scatter = [&](const uint32_t* stage, uint8_t* dst) {
+    for (int bb = 0; bb < sub_h; bb++) {
+      const size_t j = (size_t)ystart + (size_t)bb * yadd;
+      const uint32_t* src = stage + (size_t)bb * sub_w;
+      uint8_t* row = dst + j * W * 4;
+      if (xadd == 1) {
+        std::memcpy(row + (size_t)xstart * 4, src, (size_t)sub_w * 4);
+      } else {
+        for (int a = 0; a < sub_w; a++)
+          std::memcpy(row + ((size_t)xstart + (size_t)a * xadd) * 4, src + a, 4);
+      }
     }
-  }
-  return SFRT_OK;
+  };
+  if (!rc) scatter(w->h_stage, pixels);
+  for (int q = 0; planes && q < 3; q++)
+    if (planes[q]) scatter(w->h_aux[q], (uint8_t*)planes[q]);
+  return rc;
 }
 
-int sfrt_world_render_band(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes, int row0,
-                           int rows, void* hip_stream) {
+int sfrt_world_update_image(sfrt_world* w, uint8_t* pixels, int ystart, int yadd, int xstart,
+                            int xadd) {
+  return update_image_body(w, pixels, nullptr, ystart, yadd, xstart, xadd);
+}
+
+int sfrt_world_update_image_aux(sfrt_world* w, uint8_t* pixels, float* depth, int32_t* sphere,
+                                int32_t* steps, int ystart, int yadd, int xstart, int xadd) {
+  void* const planes[3] = {depth, sphere, steps};
+  return update_image_body(w, pixels, planes, ystart, yadd, xstart, xadd);
+}
+
+// sfrt_world_render_band and sfrt_world_render_band_aux (aux: nullptr for the plain call).
+static int render_band_body(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes,
+                            const sfrt_aux_planes* aux, bool with_aux, int row0, int rows,
+                            void* hip_stream) {
   if (!w || !dev_pixels || row0 < 0 || rows < 0 || pitch_bytes % 4 != 0) return SFRT_E_INVALID;
+  if (with_aux && (!aux || (!aux->depth && !aux->sphere && !aux->steps))) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
   int rc = w->validate();
   if (rc) return rc;
   if (pitch_bytes < (int64_t)w->width * 4 || row0 + rows > w->height) return SFRT_E_INVALID;
+  sfrt::AuxArgs a{};
+  if (with_aux) {
+    const auto pitch_ok = [&](const void* p, int64_t pitch) {
+      return !p || (pitch % 4 == 0 && pitch >= (int64_t)w->width * 4);
+    };
+    if (!pitch_ok(aux->depth, aux->depth_pitch_bytes) ||
+        !pitch_ok(aux->sphere, aux->sphere_pitch_bytes) ||
+        !pitch_ok(aux->steps, aux->steps_pitch_bytes))
+      return SFRT_E_INVALID;
+    a.depth = (float*)aux->depth; a.depth_pitch = aux->depth ? aux->depth_pitch_bytes / 4 : 0;
+    a.sphere = (int32_t*)aux->sphere; a.sphere_pitch = aux->sphere ? aux->sphere_pitch_bytes / 4 : 0;
+    a.steps = (int32_t*)aux->steps; a.steps_pitch = aux->steps ? aux->steps_pitch_bytes / 4 : 0;
+  }
   if (rows == 0) {
     w->last_fill.valid = false;  // the last fill covered no rows (sfrt_world_row_costs)
     return SFRT_OK;
@@ -994,12 +1061,23 @@ int sfrt_world_render_band(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes,
   if (rc) return rc;
   // after the last texture upload (queued on w->stream, where the other launches run)
   HIP_TRY(w->tex_written.before_read(s));
-  if ((rc = w->sched_begin(f, s))) return rc;
+  if ((rc = w->sched_begin(f, s, with_aux))) return rc;
   if ((rc = w->sched_end(f, s, sfrt::launch_trace(f, recs.data(), s, nullptr, w->ring_event(),
-                                                  w->ray_cache, w->tile_recs) == 0)))
+                                                  w->ray_cache, w->tile_recs,
+                                                  with_aux ? &a : nullptr) == 0)))
     return rc;
   if ((rc = w->launched_with())) return rc;
   return SFRT_OK;
+}
+
+int sfrt_world_render_band(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes, int row0,
+                           int rows, void* hip_stream) {
+  return render_band_body(w, dev_pixels, pitch_bytes, nullptr, false, row0, rows, hip_stream);
+}
+
+int sfrt_world_render_band_aux(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes,
+                               const sfrt_aux_planes* aux, int row0, int rows, void* hip_stream) {
+  return render_band_body(w, dev_pixels, pitch_bytes, aux, true, row0, rows, hip_stream);
 }
 
 int sfrt_world_check(sfrt_world* w, void* hip_stream) {
@@ -1215,7 +1293,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 5; }
+int sfrt_version(void) { return 6; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

@@ -150,9 +150,10 @@ struct Shading {
   uint32_t tex;
   float brightness;
   bool outside;
+  float depth;  // AUX only: |pos - cam| (:375's VLength, the operand of its std::max)
 };
 
-template <class P>
+template <class P, bool AUX = false>
 __device__ __forceinline__ Shading shade_texel(const FrameRec& f, const SphereRec& d, float px,
                                                float py, float pz, PixelDump* dump) {
   float ang = d.atan_c - P::hit_atan2(pz, px);  // atan2f_wave == sfrt_math::atan2f (sfrt_device.h)
@@ -190,6 +191,8 @@ __device__ __forceinline__ Shading shade_texel(const FrameRec& f, const SphereRe
   sh.outside = !(idx < tw * th);
   sh.tex = d.tex_off + (sh.outside ? 0u : idx);
   sh.brightness = brightness;
+  if constexpr (AUX) sh.depth = bl;
+  else sh.depth = 0.0f;
   if (dump) {
     dump->xcoord = xcoord;
     dump->ycoord = ycoord;
@@ -525,14 +528,21 @@ __device__ __forceinline__ bool pass_body_r(const float (&ss)[R], float s_pass, 
 // for this launch's RayKey: the bits primary_dir gives) and not computed, and the tile's cone
 // and grid position from the chain's tile records tr (the bits tile_cone gives); all else is
 // the same.
-template <int R, bool LIST, bool DUMP, class P, int SS = 0, bool CACHED = false>
+// AUX (sfrt_world_render_band_aux): the same march, shading and colour store,
+// plus the per-ray step count of DUMP and, beside each colour store and under its condition,
+// one dword per non-null plane of `aux` (sfrt_trace.h AuxArgs): the hit distance shade_texel
+// computes for the brightness, drawSphere and the step count.  Supersampled, the leader lane
+// stores its own sample's values (the group's first sample), unfiltered.
+template <int R, bool LIST, bool DUMP, class P, int SS = 0, bool CACHED = false, bool AUX = false>
 __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
                                                     const SphereRec* __restrict__ sph,
                                                     DumpArgs dmp,
                                                     const float* __restrict__ rc = nullptr,
-                                                    const TileRec* tr = nullptr) {
+                                                    const TileRec* tr = nullptr,
+                                                    AuxArgs aux = AuxArgs{}) {
   static_assert(SS == 0 || !DUMP, "trace_points dumps the 1x pixel");
   static_assert(!CACHED || !DUMP, "the DUMP kernels compute their directions");
+  static_assert(!AUX || (!DUMP && !CACHED), "the AUX kernels compute their directions and dump nothing");
   const int lane = threadIdx.x & 63;
   P probe;
   probe.wave_entry();
@@ -567,7 +577,7 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   [[maybe_unused]] const int j = CACHED ? 0 : subset_index<SS>(f.ystart, f.yadd, bc);
   const float l0 = f.first_l;
   int draw[R];
-  int iters[R];  // DUMP only: loop trips of :362 per ray, the host's first one included
+  int iters[R];  // DUMP and AUX only: loop trips of :362 per ray, the host's first one included
   float dx[R], dy[R], dz[R], px[R], py[R], pz[R], mv[R], tacc[R];
   // mv: the ray's last step length (> 0 while it marches, +0 once it stopped);
   // `mv > 0` is one compare per step, where a loop-carried bool would be
@@ -665,7 +675,7 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
       px[r] = px[r] + dx[r] * L[r];
       py[r] = py[r] + dy[r] * L[r];
       pz[r] = pz[r] + dz[r] * L[r];
-      if constexpr (DUMP) iters[r] += mv[r] > 0.0f ? 1 : 0;  // a step of a marching ray
+      if constexpr (DUMP || AUX) iters[r] += mv[r] > 0.0f ? 1 : 0;  // a step of a marching ray
       mv[r] = L[r];
       tacc[r] = tacc[r] + L[r];
     }
@@ -791,6 +801,16 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   // (SS > 0: the output pixel of sample (a, b) is (a >> SS, (b - sub_row0) >> SS))
   uint32_t* const row_out = f.out + (long long)((b_s - f.sub_row0) >> SS) * f.out_pitch;
   auto px_out = [&](int r) { return row_out + (col(r) >> SS); };
+  // AUX: each plane's row likewise (null planes: wave-uniform, never stored)
+  [[maybe_unused]] float* depth_row = nullptr;
+  [[maybe_unused]] int32_t* sphere_row = nullptr;
+  [[maybe_unused]] int32_t* steps_row = nullptr;
+  if constexpr (AUX) {
+    const long long row = (long long)((b_s - f.sub_row0) >> SS);
+    if (aux.depth) depth_row = aux.depth + row * aux.depth_pitch;
+    if (aux.sphere) sphere_row = aux.sphere + row * aux.sphere_pitch;
+    if (aux.steps) steps_row = aux.steps + row * aux.steps_pitch;
+  }
   if constexpr (!P::kShade) {  // timing probe (sfrt_probe.h): the march without the shading tail
 #pragma unroll
     for (int r = 0; r < R; r++)
@@ -809,7 +829,14 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
     PixelDump dl[DUMP ? R : 1];
 #pragma unroll
     for (int r = 0; r < R; r++)
-      sh[r] = shade_texel<P>(f, d[r], px[r], py[r], pz[r], DUMP ? &dl[DUMP ? r : 0] : nullptr);
+      sh[r] = shade_texel<P, AUX>(f, d[r], px[r], py[r], pz[r], DUMP ? &dl[DUMP ? r : 0] : nullptr);
+    // AUX: ray r's plane values beside its colour store (plain vector stores)
+    [[maybe_unused]] auto aux_store = [&](int r) {
+      const int c = col(r) >> SS;
+      if (aux.depth) depth_row[c] = sh[r].depth;
+      if (aux.sphere) sphere_row[c] = draw[r];
+      if (aux.steps) steps_row[c] = iters[r];
+    };
     uint32_t texel[R];
 #pragma unroll
     for (int r = 0; r < R; r++) texel[r] = f.tex[sh[r].tex];
@@ -835,7 +862,10 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
         const uint32_t ga = group_sum_u32<SS>((rgba[r] >> 8) & 0x00ff00ffu);
         const uint32_t out = (((rb + kHalf) >> (2 * SS)) & 0x00ff00ffu) |
                              ((((ga + kHalf) >> (2 * SS)) & 0x00ff00ffu) << 8);
-        if (leader && valid(r)) *px_out(r) = out;
+        if (leader && valid(r)) {
+          *px_out(r) = out;
+          if constexpr (AUX) aux_store(r);
+        }
       }
     } else {
 #pragma unroll
@@ -845,6 +875,7 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
           const uint32_t rgba = shade_rgba(sh[r].outside ? 0u : texel[r], sh[r].brightness);
           if constexpr (!DUMP) {
             *px_out(r) = rgba;
+            if constexpr (AUX) aux_store(r);
           } else {  // the listed pixel's record, if it is listed (no frame store)
             const long long pid = (long long)(b_s - f.sub_row0) * f.sub_w + col(r);
             int q = 0, qe = dmp.npix;  // first entry >= pid
@@ -937,6 +968,18 @@ __global__ __launch_bounds__(64) void k_trace_window_list_dump(FrameRec f, DumpA
   trace_tile_window_r<R, true, true, NoProbe>(f, f.spheres, d);
 }
 
+// The AUX instantiations of both, at every factor (sfrt_world_render_band_aux; never probed).
+// Four step counters more than the plain kernels carry: no occupancy bound.
+template <int R, int SS>
+__global__ __launch_bounds__(64) void k_trace_window_r_aux(InlineArgs args, AuxArgs a) {
+  trace_tile_window_r<R, false, false, NoProbe, SS, false, true>(args.f, args.s, DumpArgs{}, nullptr,
+                                                                 nullptr, a);
+}
+template <int R, int SS>
+__global__ __launch_bounds__(64) void k_trace_window_list_aux(FrameRec f, AuxArgs a) {
+  trace_tile_window_r<R, true, false, NoProbe, SS, false, true>(f, f.spheres, DumpArgs{}, nullptr,
+                                                                nullptr, a);
+}
 
 }  // namespace
 
@@ -1039,6 +1082,28 @@ void launch_list_rc(int rays, dim3 gr, hipStream_t s, hipEvent_t ev, const Frame
                                   tr); break;
   }
 }
+// The AUX kernels by (rays, ss).
+template <int SS>
+void launch_inline_aux(int rays, dim3 gr, hipStream_t s, const InlineArgs& args, const AuxArgs& a) {
+  const dim3 b(64);
+  switch (rays) {
+    case 1: hipLaunchKernelGGL((k_trace_window_r_aux<1, SS>), gr, b, 0, s, args, a); break;
+    case 2: hipLaunchKernelGGL((k_trace_window_r_aux<2, SS>), gr, b, 0, s, args, a); break;
+    case 3: hipLaunchKernelGGL((k_trace_window_r_aux<3, SS>), gr, b, 0, s, args, a); break;
+    default: hipLaunchKernelGGL((k_trace_window_r_aux<4, SS>), gr, b, 0, s, args, a); break;
+  }
+}
+template <int SS>
+void launch_list_aux(int rays, dim3 gr, hipStream_t s, hipEvent_t ev, const FrameRec& g,
+                     const AuxArgs& a) {
+  const dim3 b(64);
+  switch (rays) {
+    case 1: hipExtLaunchKernelGGL((k_trace_window_list_aux<1, SS>), gr, b, 0, s, nullptr, ev, 0, g, a); break;
+    case 2: hipExtLaunchKernelGGL((k_trace_window_list_aux<2, SS>), gr, b, 0, s, nullptr, ev, 0, g, a); break;
+    case 3: hipExtLaunchKernelGGL((k_trace_window_list_aux<3, SS>), gr, b, 0, s, nullptr, ev, 0, g, a); break;
+    default: hipExtLaunchKernelGGL((k_trace_window_list_aux<4, SS>), gr, b, 0, s, nullptr, ev, 0, g, a); break;
+  }
+}
 template <int SS>
 void launch_fill(int rays, dim3 gr, hipStream_t s, const FrameRec& g, float* rc, TileRec* tr) {
   const dim3 b(64);
@@ -1069,7 +1134,7 @@ int launch_ray_fill(const FrameRec& f, float* ray_cache, TileRec* tile_recs, voi
 
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump, void* done_event, const float* ray_cache,
-                 const TileRec* tile_recs) {
+                 const TileRec* tile_recs, const AuxArgs* aux) {
   const long long tiles_y = (f.sub_rows + kTile - 1) / kTile;
   if (tiles_y <= 0 || f.sub_w <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
@@ -1092,11 +1157,17 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
   // the cache is laid out for the ordered kernel's grid (launch_ray_fill), never dumped
   if ((ray_cache != nullptr) != (tile_recs != nullptr)) return -1;
   if (ray_cache && (!ordered || !g.tile_cost || dump)) return -1;
+  // the AUX kernels compute their directions and dump nothing; one plane at least
+  if (aux && (dump || ray_cache || (!aux->depth && !aux->sphere && !aux->steps))) return -1;
   if (f.n <= kInlineSpheres) {
     InlineArgs args;
     args.f = g;
     for (int k = 0; k < f.n; k++) args.s[k] = host_spheres[k];
-    if (ray_cache) {
+    if (aux) {
+      if (f.ss == 0) launch_inline_aux<0>(rays, gr, s, args, *aux);
+      else if (f.ss == 1) launch_inline_aux<1>(rays, gr, s, args, *aux);
+      else launch_inline_aux<2>(rays, gr, s, args, *aux);
+    } else if (ray_cache) {
       if (f.ss == 0) launch_inline_rc<0>(rays, gr, s, args, ray_cache, tile_recs);
       else if (f.ss == 1) launch_inline_rc<1>(rays, gr, s, args, ray_cache, tile_recs);
       else launch_inline_rc<2>(rays, gr, s, args, ray_cache, tile_recs);
@@ -1120,6 +1191,11 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
     }
   } else if (f.n < 64) {
     return -1;  // the list kernel's lookahead reads culled-list lane 63 (a sphere index < n)
+  } else if (aux) {
+    const hipEvent_t ev = (hipEvent_t)done_event;
+    if (f.ss == 0) launch_list_aux<0>(rays, gr, s, ev, g, *aux);
+    else if (f.ss == 1) launch_list_aux<1>(rays, gr, s, ev, g, *aux);
+    else launch_list_aux<2>(rays, gr, s, ev, g, *aux);
   } else if (ray_cache) {
     const hipEvent_t ev = (hipEvent_t)done_event;
     if (f.ss == 0) launch_list_rc<0>(rays, gr, s, ev, g, ray_cache, tile_recs);

@@ -61,7 +61,7 @@ ABI_SYMBOLS = (
     "sfrt_band_unpack", "sfrt_world_alpha_binary", "sfrt_multi_transport_library",
     "sfrt_multi_use_test_transport", "sfrt_world_get_option",
     "sfrt_voxel_get_option", "sfrt_glsl_get_option", "sfrt_world_ray_cache_stats",
-    "sfrt_world_tile_record_bytes",
+    "sfrt_world_tile_record_bytes", "sfrt_world_render_band_aux", "sfrt_world_update_image_aux",
 )
 
 SFRT_MULTI_AUTO, SFRT_MULTI_RCCL, SFRT_MULTI_PEER = 0, 1, 2
@@ -90,6 +90,13 @@ class PixelDump(ctypes.Structure):
                 ("xcoord", ctypes.c_float), ("ycoord", ctypes.c_float),
                 ("brightness", ctypes.c_float), ("texel", ctypes.c_uint32 * 2),
                 ("rgba", ctypes.c_uint32)]
+
+
+class AuxPlanes(ctypes.Structure):
+    """sfrt_aux_planes: device planes of sfrt_world_render_band_aux (None = not wanted)."""
+    _fields_ = [("depth", ctypes.c_void_p), ("depth_pitch_bytes", ctypes.c_int64),
+                ("sphere", ctypes.c_void_p), ("sphere_pitch_bytes", ctypes.c_int64),
+                ("steps", ctypes.c_void_p), ("steps_pitch_bytes", ctypes.c_int64)]
 
 
 _lib = None
@@ -129,6 +136,9 @@ def lib() -> ctypes.CDLL:
         "sfrt_world_update_spheres": ([W], c_int),
         "sfrt_world_update_image": ([W, vp, c_int, c_int, c_int, c_int], c_int),
         "sfrt_world_render_band": ([W, vp, ctypes.c_int64, c_int, c_int, vp], c_int),
+        "sfrt_world_render_band_aux": ([W, vp, ctypes.c_int64, P(AuxPlanes), c_int, c_int, vp],
+                                       c_int),
+        "sfrt_world_update_image_aux": ([W, vp, vp, vp, vp, c_int, c_int, c_int, c_int], c_int),
         "sfrt_world_check": ([W, vp], c_int),
         "sfrt_world_row_costs": ([W, vp, c_int, P(c_int), P(c_int)], c_int),
         "sfrt_multi_cost_bands": ([vp, c_int, c_int, c_float, vp, vp], c_int),
@@ -415,6 +425,49 @@ class World:
         _check(lib().sfrt_world_render_band(self._h, ctypes.c_void_p(dev_ptr), int(pitch_bytes),
                                             int(row0), int(rows), ctypes.c_void_p(stream or None)),
                "render_band")
+
+    def render_band_aux(self, dev_ptr: int, pitch_bytes: int, row0: int, rows: int,
+                        stream: int = 0, depth=None, sphere=None, steps=None) -> None:
+        """render_band plus the per-pixel planes (sfrt_world_render_band_aux): depth (float32),
+        sphere and steps (int32), each None or a (device pointer, pitch in bytes) pair."""
+        planes = AuxPlanes()
+        for name, plane in (("depth", depth), ("sphere", sphere), ("steps", steps)):
+            if plane is not None:
+                setattr(planes, name, int(plane[0]))
+                setattr(planes, name + "_pitch_bytes", int(plane[1]))
+        _check(lib().sfrt_world_render_band_aux(self._h, ctypes.c_void_p(dev_ptr), int(pitch_bytes),
+                                                ctypes.byref(planes), int(row0), int(rows),
+                                                ctypes.c_void_p(stream or None)),
+               "render_band_aux")
+
+    def update_image_aux(self, pixels: np.ndarray, depth=None, sphere=None, steps=None,
+                         ystart=0, yadd=1, xstart=0, xadd=1) -> np.ndarray:
+        """update_image plus host planes of width*height elements (sfrt_world_update_image_aux):
+        depth float32, sphere and steps int32, each a contiguous array or None."""
+        w, h = self.size
+        if pixels.dtype != np.uint8 or pixels.size != w * h * 4 or not pixels.flags.c_contiguous:
+            raise ValueError("pixels must be a contiguous uint8 array of width*height*4")
+        ptrs = []
+        for plane, dtype in ((depth, np.float32), (sphere, np.int32), (steps, np.int32)):
+            if plane is not None and (plane.dtype != dtype or plane.size != w * h or
+                                      not plane.flags.c_contiguous):
+                raise ValueError(f"a plane must be a contiguous {np.dtype(dtype).name} array of "
+                                 "width*height")
+            ptrs.append(None if plane is None else plane.ctypes.data)
+        _check(lib().sfrt_world_update_image_aux(self._h, pixels.ctypes.data, *ptrs, ystart, yadd,
+                                                 xstart, xadd), "update_image_aux")
+        return pixels
+
+    def render_aux(self) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(rgba (h, w, 4) uint8, depth (h, w) float32, sphere (h, w) int32, steps (h, w) int32)
+        of the whole frame."""
+        w, h = self.size
+        rgba = np.zeros((h, w, 4), dtype=np.uint8)
+        depth = np.zeros((h, w), dtype=np.float32)
+        sphere = np.zeros((h, w), dtype=np.int32)
+        steps = np.zeros((h, w), dtype=np.int32)
+        self.update_image_aux(rgba, depth, sphere, steps)
+        return rgba, depth, sphere, steps
 
     def submit_frame(self, frame: "HostFrame") -> int:
         """Pipelined full-frame fill into a pinned HostFrame; returns a ticket."""
