@@ -201,6 +201,55 @@ SFRT_API int sfrt_host_free(void* ptr);
  * order).  A pixel may be listed more than once. */
 SFRT_API int sfrt_world_trace_points(sfrt_world* w, const int32_t* ij, int count, sfrt_pixel_dump* out);
 
+/* ---- batched ray queries: SphereWorld::Raycast (SphereWorld.cpp:355-382) for caller-supplied rays ----
+ * A valid ray.  `dirs` holds 3 floats per ray, un-normalised, exactly as Raycast receives
+ * r->dir.  `origins` holds 3 floats per ray.  origins == NULL means every ray starts at the
+ * world's cam.pos, as in the reference; the position is snapshotted at the call.
+ * Ray q is Raycast with cam.pos replaced by its origin o, in three places:
+ *   - pos = o.
+ *   - dir = d / sqrtf((dx*dx + dy*dy) + dz*dz) per component.
+ *   - Lines :359-372 run as written, including the first trip from pos == o.
+ *   - The tail :373-381 uses brightness = 3 / max(VLength(pos - o), 3) and the sphere's texture
+ *     slot (sfrt_world_set_sphere_textures is honoured).
+ * Arithmetic is binary32, round to nearest, no contraction, with correctly rounded / and sqrt.
+ * The transcendentals are sfrt_math's, as everywhere else.
+ * An invalid ray.  A ray is invalid when any direction or origin component is not finite, or
+ * when s = (dx*dx + dy*dy) + dz*dz is not a finite normal number.  That covers zero, underflow
+ * and overflow.  It is decided per ray before the march.  It is never marched.  It gets
+ * sphere = -1, and every other requested output is all-zero bytes.  It must not change any
+ * other ray's result.  It sets no status bit.
+ * Return codes and edge cases.  count == 0 returns SFRT_OK and writes nothing.
+ * SFRT_E_INVALID, with nothing queued or written, for: a NULL world; NULL dirs; count < 0 or
+ * count > 2^31-1; all five outputs NULL; a non-NULL pointer that is not 4-byte aligned.
+ * SFRT_E_EMPTY when there are no spheres.  SFRT_E_NO_TEXTURE only when rgba is requested: a
+ * world without textures can still answer pos, depth, sphere and steps.  Overlapping buffers
+ * are the caller's responsibility.
+ * Status.  The status bits are the frame fill's own: march guard, and texel outside the texture
+ * (only when rgba is requested).  The device call leaves them to sfrt_world_check(w,
+ * hip_stream).  The host call returns the code; on SFRT_E_TEXEL it writes every output except
+ * rgba, as sfrt_world_update_image_aux does.
+ * Options and shared state.  SFRT_OPT_CULL is honoured; the bytes are the same either way.
+ * SFRT_OPT_SUPERSAMPLE, SFRT_OPT_RAYS_PER_LANE and SFRT_OPT_TILE_ORDER are ignored.  The call
+ * joins no tile-order chain.  It neither reads, fills nor invalidates the ray cache or the tile
+ * records.  It leaves sfrt_world_ray_cache_stats, sfrt_world_tile_record_bytes and
+ * sfrt_world_row_costs exactly as they were.
+ * Concurrency.  Calls serialise on the world's mutex; the scene, camera and options are
+ * snapshotted at the call, as for sfrt_world_render_band. */
+typedef struct {          /* every member: one element per ray, or NULL; not all NULL */
+  float*    pos;          /* 3 floats per ray, packed x,y,z (12 B per ray): r->pos after the march */
+  float*    depth;        /* VLength(r->pos - origin) as :375 evaluates it, before std::max(.., 3.0f) */
+  int32_t*  sphere;       /* drawSphere (:360-369), index into the current sphere order; -1: invalid ray */
+  int32_t*  steps;        /* loop trips of :362, the first one included; 0: invalid ray */
+  uint8_t*  rgba;         /* 4 bytes per ray: r->c of :373-381 */
+} sfrt_ray_hits;
+
+/* device memory on the world's device, asynchronous on hip_stream; status via sfrt_world_check */
+SFRT_API int sfrt_world_cast_rays_device(sfrt_world* w, const float* dev_dirs, const float* dev_origins,
+                                         int64_t count, const sfrt_ray_hits* dev_out, void* hip_stream);
+/* host memory, synchronous */
+SFRT_API int sfrt_world_cast_rays(sfrt_world* w, const float* dirs, const float* origins,
+                                  int64_t count, const sfrt_ray_hits* out);
+
 /* Options: SFRT_OPT_CULL (1 = per-wave sphere culling, default; 0 = visit
  * every sphere -- same bytes, slower; used by A/B parity tests).
  * SFRT_OPT_RAYS_PER_LANE (0 = default): pixels per lane R of the frame-fill

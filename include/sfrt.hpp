@@ -100,6 +100,13 @@ inline sfrt_camera to_c(const Camera& c) {
   return o;
 }
 
+// struct Ray (SphereWorld.h): what SphereWorld::Raycast reads (dir) and writes (pos, c);
+// c is the sf::Color's r, g, b, a.
+struct Ray {
+  Vector3f pos, dir;
+  uint8_t c[4] = {0, 0, 0, 0};
+};
+
 // ---------------------------------------------------------------------------
 // SphereWorld (SphereWorld.h:40-78): the sphere-cave frame fill.
 class SphereWorld {
@@ -179,6 +186,33 @@ class SphereWorld {
     push_state();
     check(sfrt_world_render_band_aux(w_, dev_pixels, pitch_bytes, &aux, row0, rows, hip_stream),
           "render_band_aux");
+  }
+  // SphereWorld::Raycast (SphereWorld.cpp:355-382), the reference's own signature: r->dir is
+  // the un-normalised direction, the ray starts at cam.pos; writes r->pos and r->c (r->dir is
+  // left as given: the normalised copy lives in the kernel).  One ray per call, synchronous:
+  // the camera's ground probes (SphereWorld.cpp:279-289); batches go through CastRays.
+  void Raycast(Ray* r) {
+    push_camera();
+    const float dir[3] = {r->dir.x, r->dir.y, r->dir.z};
+    float pos[3] = {0, 0, 0};
+    sfrt_ray_hits out{};
+    out.pos = pos;
+    out.rgba = r->c;
+    check(sfrt_world_cast_rays(w_, dir, nullptr, 1, &out), "Raycast");
+    r->pos = Vector3f{pos[0], pos[1], pos[2]};
+  }
+  // `count` rays at once (sfrt.h sfrt_world_cast_rays): dirs and origins 3 floats per ray,
+  // origins null = every ray from cam.pos; any member of out may be null, not all.
+  void CastRays(const float* dirs, const float* origins, int64_t count, const sfrt_ray_hits& out) {
+    push_camera();
+    check(sfrt_world_cast_rays(w_, dirs, origins, count, &out), "CastRays");
+  }
+  // The same on device memory, asynchronous on hip_stream (status through Check).
+  void CastRaysDevice(const float* dev_dirs, const float* dev_origins, int64_t count,
+                      const sfrt_ray_hits& dev_out, void* hip_stream) {
+    push_camera();
+    check(sfrt_world_cast_rays_device(w_, dev_dirs, dev_origins, count, &dev_out, hip_stream),
+          "CastRaysDevice");
   }
   void Check(void* hip_stream = nullptr) { check(sfrt_world_check(w_, hip_stream), "check"); }
   // SFRT_OPT_* (sfrt.h): SFRT_OPT_SUPERSAMPLE 2 or 4 box-filters S x S samples per pixel

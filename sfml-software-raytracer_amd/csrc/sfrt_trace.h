@@ -126,6 +126,28 @@ struct AuxArgs {
   long long depth_pitch, sphere_pitch, steps_pitch;
 };
 
+// A batch of caller-supplied rays (sfrt_world_cast_rays[_device]): ray q's
+// direction is dirs[3q..3q+2] (un-normalised, as Raycast receives r->dir), its origin
+// origins[3q..3q+2], or f.cam for every ray when origins is null.  One element per ray in every
+// non-null output (pos: three floats).  A kernel argument of its own, as DumpArgs and AuxArgs
+// are: FrameRec's layout is every kernel's.
+struct RayArgs {
+  const float* dirs;
+  const float* origins;
+  long long count;
+  float* pos;        // r->pos after the march
+  float* depth;      // |pos - origin| (:375's VLength, before its std::max)
+  int32_t* sphere;   // drawSphere; -1: invalid ray
+  int32_t* steps;    // loop trips of :362, the first one included; 0: invalid ray
+  uint32_t* rgba;    // r->c of :373-381
+};
+
+// The ray-batch kernels (k_cast_rays): one wave per 64 consecutive rays, one ray per lane.  Of
+// f they read cam, first_l, first_draw, n, cull, cull_margin, tex, spheres and status; the
+// frame and tile-order members are ignored.  done_event as for launch_trace.
+int launch_cast_rays(const FrameRec& f, const SphereRec* host_spheres, const RayArgs& rays,
+                     void* stream, void* done_event);
+
 // sphere_trace.hip.  dump != nullptr: the DUMP instantiation of the kernel the table picks.
 // aux != nullptr (with at least one plane set): its AUX instantiation -- never with dump or
 // the ray cache.

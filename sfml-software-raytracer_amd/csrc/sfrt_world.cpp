@@ -178,6 +178,12 @@ struct sfrt_world {
   size_t d_aux_px[3] = {};
   uint32_t* h_aux[3] = {};
   size_t h_aux_px[3] = {};
+  // Staging of sfrt_world_cast_rays (the host call): one device and one pinned buffer holding
+  // the batch's inputs and outputs back to back, grown like d_frame / h_stage.
+  uint8_t* d_rays = nullptr;
+  size_t d_rays_bytes = 0;
+  uint8_t* h_rays = nullptr;
+  size_t h_rays_bytes = 0;
   sfrt::RetiredHost retired_host;  // replaced pinned buffers (sfrt_host.h)
   std::vector<void*> retired_device;  // replaced record rings, freed with the world
   // --- frame pipeline (display path): render k+1 while frame k is copied ---
@@ -228,6 +234,8 @@ struct sfrt_world {
       (void)hipFree(d_aux[q]);
       (void)hipHostFree(h_aux[q]);
     }
+    (void)hipFree(d_rays);
+    (void)hipHostFree(h_rays);
     retired_host.release();
     for (void* p : retired_device) (void)hipFree(p);
     if (stream) (void)hipStreamDestroy(stream);
@@ -1080,6 +1088,120 @@ int sfrt_world_render_band_aux(sfrt_world* w, void* dev_pixels, int64_t pitch_by
   return render_band_body(w, dev_pixels, pitch_bytes, aux, true, row0, rows, hip_stream);
 }
 
+// sfrt_world_cast_rays_device and, for the host call's staged copies, sfrt_world_cast_rays:
+// one launch of the ray-batch kernels on s with the world's mutex held.  The launch takes the
+// frame fill's immutable snapshot (records in the kernel arguments, or a ring slot with its
+// event) and nothing else of the world's: no tile-order chain, no ray cache, no last fill.
+static int cast_rays_launch(sfrt_world* w, const float* dev_dirs, const float* dev_origins,
+                            int64_t count, const sfrt_ray_hits& out, hipStream_t s) {
+  sfrt::FrameRec f;
+  std::vector<sfrt::SphereRec> recs;
+  w->prepare(f, recs);
+  int rc = w->stage_spheres(f, recs, s, false);
+  if (rc) return rc;
+  // after the last texture upload (queued on w->stream)
+  if (out.rgba) HIP_TRY(w->tex_written.before_read(s));
+  sfrt::RayArgs a{};
+  a.dirs = dev_dirs;
+  a.origins = dev_origins;
+  a.count = count;
+  a.pos = out.pos;
+  a.depth = out.depth;
+  a.sphere = out.sphere;
+  a.steps = out.steps;
+  a.rgba = (uint32_t*)out.rgba;
+  if (sfrt::launch_cast_rays(f, recs.data(), a, s, w->ring_event())) return SFRT_E_HIP;
+  return w->launched_with();
+}
+
+// The argument checks both calls share; the world's own come with its mutex held.
+static int cast_rays_args(const sfrt_world* w, const float* dirs, const float* origins,
+                          int64_t count, const sfrt_ray_hits* out) {
+  if (!w || !dirs || !out || count < 0 || count > 0x7fffffffLL) return SFRT_E_INVALID;
+  if (!out->pos && !out->depth && !out->sphere && !out->steps && !out->rgba) return SFRT_E_INVALID;
+  const void* const ptrs[7] = {dirs, origins, out->pos, out->depth, out->sphere, out->steps, out->rgba};
+  for (const void* p : ptrs)
+    if ((uintptr_t)p & 3u) return SFRT_E_INVALID;
+  return SFRT_OK;
+}
+static int cast_rays_world(const sfrt_world* w, bool rgba) {
+  if (w->spheres.empty()) return SFRT_E_EMPTY;
+  if ((int)w->spheres.size() > SFRT_MAX_SPHERES) return SFRT_E_TOO_MANY;
+  if (!rgba) return SFRT_OK;  // pos, depth, sphere and steps need no texture
+  if (w->tex_host[0].empty() || !w->d_tex) return SFRT_E_NO_TEXTURE;
+  for (int32_t k : w->sphere_tex)
+    if (w->tex_host[k].empty()) return SFRT_E_NO_TEXTURE;
+  return SFRT_OK;
+}
+
+int sfrt_world_cast_rays_device(sfrt_world* w, const float* dev_dirs, const float* dev_origins,
+                                int64_t count, const sfrt_ray_hits* dev_out, void* hip_stream) {
+  int rc = cast_rays_args(w, dev_dirs, dev_origins, count, dev_out);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(w->mu);
+  if (count == 0) return SFRT_OK;
+  if ((rc = cast_rays_world(w, dev_out->rgba != nullptr))) return rc;
+  sfrt::DeviceGuard g(w->device);
+  return cast_rays_launch(w, dev_dirs, dev_origins, count, *dev_out, (hipStream_t)hip_stream);
+}
+
+int sfrt_world_cast_rays(sfrt_world* w, const float* dirs, const float* origins, int64_t count,
+                         const sfrt_ray_hits* out) {
+  int rc = cast_rays_args(w, dirs, origins, count, out);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(w->mu);
+  if (count == 0) return SFRT_OK;
+  if ((rc = cast_rays_world(w, out->rgba != nullptr))) return rc;
+  sfrt::DeviceGuard g(w->device);
+  // The staging layout: dirs, origins, then the requested outputs, 4-byte elements throughout.
+  const size_t n = (size_t)count;
+  const size_t in_bytes = n * 12 * (origins ? 2 : 1);
+  void* const host_out[5] = {out->pos, out->depth, out->sphere, out->steps, out->rgba};
+  const size_t elem[5] = {12, 4, 4, 4, 4};
+  size_t off[5] = {}, bytes = in_bytes;
+  for (int q = 0; q < 5; q++) {
+    off[q] = bytes;
+    if (host_out[q]) bytes += n * elem[q];
+  }
+  // Growth waits for no other stream, as update_image's: the device buffer stream-ordered on the
+  // world's stream (the last host call waited for its own copies), the old pinned one retired.
+  if (w->d_rays_bytes < bytes) {
+    if (w->d_rays) HIP_TRY(hipFreeAsync(w->d_rays, w->stream));
+    w->d_rays = nullptr;
+    w->d_rays_bytes = 0;
+    HIP_TRY(hipMallocAsync((void**)&w->d_rays, bytes, w->stream));
+    w->d_rays_bytes = bytes;
+  }
+  if (w->h_rays_bytes < bytes) {
+    w->retired_host.add(w->h_rays);
+    w->h_rays = nullptr;
+    w->h_rays_bytes = 0;
+    HIP_TRY(hipHostMalloc((void**)&w->h_rays, bytes, hipHostMallocDefault));
+    w->h_rays_bytes = bytes;
+  }
+  std::memcpy(w->h_rays, dirs, n * 12);
+  if (origins) std::memcpy(w->h_rays + n * 12, origins, n * 12);
+  HIP_TRY(hipMemcpyAsync(w->d_rays, w->h_rays, in_bytes, hipMemcpyHostToDevice, w->stream));
+  sfrt_ray_hits dev{};
+  dev.pos = host_out[0] ? (float*)(w->d_rays + off[0]) : nullptr;
+  dev.depth = host_out[1] ? (float*)(w->d_rays + off[1]) : nullptr;
+  dev.sphere = host_out[2] ? (int32_t*)(w->d_rays + off[2]) : nullptr;
+  dev.steps = host_out[3] ? (int32_t*)(w->d_rays + off[3]) : nullptr;
+  dev.rgba = host_out[4] ? w->d_rays + off[4] : nullptr;
+  if ((rc = cast_rays_launch(w, (const float*)w->d_rays,
+                             origins ? (const float*)(w->d_rays + n * 12) : nullptr, count, dev,
+                             w->stream)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(w->h_rays + in_bytes, w->d_rays + in_bytes, bytes - in_bytes,
+                         hipMemcpyDeviceToHost, w->stream));
+  rc = w->read_status(w->stream);
+  // pos, depth, sphere and steps do not depend on the texel
+  if (rc && rc != SFRT_E_TEXEL) return rc;
+  for (int q = 0; q < 5; q++)
+    if (host_out[q] && !(rc && q == 4)) std::memcpy(host_out[q], w->h_rays + off[q], n * elem[q]);
+  return rc;
+}
+
 int sfrt_world_check(sfrt_world* w, void* hip_stream) {
   if (!w) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
@@ -1293,7 +1415,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 6; }
+int sfrt_version(void) { return 7; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "sfrt_device.h"
 #include "sfrt_math.h"
@@ -153,15 +154,19 @@ struct Shading {
   float depth;  // AUX only: |pos - cam| (:375's VLength, the operand of its std::max)
 };
 
-template <class P, bool AUX = false>
+// ORIGIN (the ray batches, k_cast_rays): the brightness is taken from the ray's own origin
+// (ox, oy, oz) in place of f.cam, :375's cam.pos.
+template <class P, bool AUX = false, bool ORIGIN = false>
 __device__ __forceinline__ Shading shade_texel(const FrameRec& f, const SphereRec& d, float px,
-                                               float py, float pz, PixelDump* dump) {
+                                               float py, float pz, PixelDump* dump, float ox = 0.0f,
+                                               float oy = 0.0f, float oz = 0.0f) {
   float ang = d.atan_c - P::hit_atan2(pz, px);  // atan2f_wave == sfrt_math::atan2f (sfrt_device.h)
   ang = ang > kPI ? ang - kPI2 : (ang < -kPI ? ang + kPI2 : ang);
   const float xcoord = sfrt_math::div_pi2_plus_1(ang);  // == ang / PI2 + 1.0f
   const float ex = px - d.cx, ey = py - d.cy, ez = pz - d.cz;
   const float el = sqrt_cr((ex * ex + ey * ey) + ez * ez);
-  const float bx = px - f.cam[0], by = py - f.cam[1], bz = pz - f.cam[2];
+  const float bx = px - (ORIGIN ? ox : f.cam[0]), by = py - (ORIGIN ? oy : f.cam[1]),
+              bz = pz - (ORIGIN ? oz : f.cam[2]);
   const float bl = sqrt_cr((bx * bx + by * by) + bz * bz);
   const float bd = bl < 3.0f ? 3.0f : bl;
   // ey / el and 3 / bd through div_inrange (same bits) unless some lane's operands
@@ -981,6 +986,274 @@ __global__ __launch_bounds__(64) void k_trace_window_list_aux(FrameRec f, AuxArg
                                                                 nullptr, a);
 }
 
+// ---- Ray batches: SphereWorld::Raycast for caller-supplied rays (sfrt_world_cast_rays;
+// DESIGN.md 18) ----
+//
+// Unit direction of a caller's ray (VNormalize, SphereWorld.cpp:330-333, :340-343):
+// (x, y, z) / sqrtf(s) with s = (x*x + y*y) + z*z a finite normal number, the correctly rounded
+// root and three correctly rounded divisions.  Unlike primary_dir's, the operands are
+// anything a caller passes: div_inrange only when every lane's components and length lie in
+// [2^-40, 2^40), the compiler's `/` in a kept branch otherwise.
+__device__ __forceinline__ void ray_dir(float x, float y, float z, float s, float& dx, float& dy,
+                                        float& dz) {
+  const float len = sqrt_cr(s);
+  if ((ballot_bad_operand(x) | ballot_bad_operand(y) | ballot_bad_operand(z) |
+       ballot_bad_operand(len)) == 0) {
+    const float sd = div_seed(len);
+    dx = div_inrange(x, len, sd);
+    dy = div_inrange(y, len, sd);
+    dz = div_inrange(z, len, sd);
+  } else {
+    const float l = keep_branch(len);
+    dx = x / l;
+    dy = y / l;
+    dz = z / l;
+  }
+}
+
+// Cone of a wave's 64 unit directions, all from one apex: the axis is lane 27's direction (the
+// middle of an 8x8-tile-major batch; any lane's serves), the half-angle's sine the wave's
+// largest |d x a| plus tile_cone_r's slack (d and a are unit to a few 1e-8, far inside it), and
+// the wave is wide when some lane is more than 60 degrees off the axis.  Every ray of the wave
+// lies in this cone by construction, which is all cull_window's argument needs of it.
+__device__ __forceinline__ Cone dirs_cone(float dx, float dy, float dz) {
+  const float ax = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dx), 27));
+  const float ay = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dy), 27));
+  const float az = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dz), 27));
+  const float cx = dy * az - dz * ay, cy = dz * ax - dx * az, cz = dx * ay - dy * ax;
+  const float sin_l = sqrt_cull((cx * cx + cy * cy) + cz * cz);
+  Cone c;
+  c.ax = ax; c.ay = ay; c.az = az;
+  c.sin_t = fminf(1.0f, __uint_as_float(wave_max_u32(__float_as_uint(sin_l))) + 1e-5f);
+  c.cos_t = sqrt_cull(fmaxf(0.0f, 1.0f - c.sin_t * c.sin_t));
+  c.wide = __builtin_amdgcn_ballot_w64(!(((dx * ax + dy * ay) + dz * az) >= 0.5f)) != 0;
+  return c;
+}
+
+// One wave per 64 consecutive rays of the batch, ray q = 64 * block + lane; the lanes past the
+// batch's end trace a duplicate of its last ray and store nothing.  The march is
+// trace_tile_window_r's at one ray per lane -- the same visits (pass_body_r), the same three
+// loops, the same culling against a cone (cull_window) -- with what the frame gives a tile
+// replaced by what the batch gives a wave:
+//  * the direction is loaded and normalised (ray_dir), not derived from a pixel;
+//  * OWN (origins given): every ray starts at its own origin, so the host's first iteration
+//    (first_l, first_draw: the trip from cam) does not apply -- the first trip runs here, steps
+//    count from 0 -- and neither does the drift bound behind cull_margin: every step visits
+//    every sphere in index order;
+//  * shared origin: the rays start at f.cam as a frame's do, and a wave culls against the cone
+//    of its own directions (dirs_cone), coherent or not (a scattered wave is wide: cull_window
+//    then keeps every sphere that can pass at all, with an unbounded window);
+//  * an invalid ray (a non-finite component, or s not a finite normal number) holds still at a
+//    NaN position, where no sphere passes (NaN < s_pass is false), so every step moves it by +0
+//    and counts nothing; its outputs are the invalid ray's constants.  A wave with such a lane
+//    does not cull (its cone would have to leave the lane out).
+// SHADE: rgba is requested -- the shading tail with the ray's origin in cam's place; without
+// it depth is the one root.  Each output is stored under a wave-uniform null test.
+template <bool LIST, bool SHADE, bool OWN>
+__device__ __forceinline__ void cast_rays_wave(const FrameRec& f, const SphereRec* __restrict__ sph,
+                                               const RayArgs& a) {
+  constexpr int R = 1;
+  const int lane = threadIdx.x & 63;
+  const long long q = (long long)blockIdx.x * 64 + lane;
+  const long long qc = q < a.count ? q : a.count - 1;
+  const float* __restrict__ dp = a.dirs + 3 * qc;
+  const float rx = dp[0], ry = dp[1], rz = dp[2];
+  float ox = f.cam[0], oy = f.cam[1], oz = f.cam[2];
+  if constexpr (OWN) {
+    const float* __restrict__ op = a.origins + 3 * qc;
+    ox = op[0]; oy = op[1]; oz = op[2];
+  }
+  const float s = (rx * rx + ry * ry) + rz * rz;  // finite only if every component is
+  const bool ok = s >= 0x1.0p-126f && s < __builtin_inff() &&
+                  __builtin_fabsf(ox) < __builtin_inff() && __builtin_fabsf(oy) < __builtin_inff() &&
+                  __builtin_fabsf(oz) < __builtin_inff();
+  const bool any_invalid = __builtin_amdgcn_ballot_w64(!ok) != 0;
+  const float l0 = OWN ? 0.0f : f.first_l;
+  int draw[R], iters[R];
+  float dx[R], dy[R], dz[R], px[R], py[R], pz[R], mv[R], tacc[R];
+  // an invalid lane normalises (1, 0, 0): its operands keep the wave on ray_dir's short path
+  ray_dir(ok ? rx : 1.0f, ok ? ry : 0.0f, ok ? rz : 0.0f, ok ? s : 1.0f, dx[0], dy[0], dz[0]);
+  if (ok) {
+    // r->pos = cam.pos (:357); shared origin: plus the host's first trip (:371)
+    px[0] = OWN ? ox : ox + dx[0] * l0;
+    py[0] = OWN ? oy : oy + dy[0] * l0;
+    pz[0] = OWN ? oz : oz + dz[0] * l0;
+    mv[0] = OWN ? 1.0f : (l0 > 0.0f ? 1.0f : 0.0f);
+  } else {
+    dx[0] = dy[0] = dz[0] = 0.0f;
+    px[0] = py[0] = pz[0] = __builtin_nanf("");
+    mv[0] = 0.0f;
+  }
+  draw[0] = OWN ? 0 : f.first_draw;
+  iters[0] = OWN ? 0 : 1;
+  tacc[0] = l0;
+  auto any_marching = [&]() { return __builtin_amdgcn_ballot_w64(mv[0] > 0.0f) != 0; };
+  const bool windowed = !OWN && f.cull && l0 > 0.0f && !any_invalid;
+  bool full = !windowed;  // visit every sphere every step
+  uint64_t m = 0;         // culled spheres (LIST: culled-list entries)
+  float lo = -__builtin_inff(), hi = __builtin_inff();
+  int cidx = lane;        // sphere of culled-list entry `lane`
+  if (windowed) {
+    const Cone cone = dirs_cone(dx[0], dy[0], dz[0]);
+    if constexpr (!LIST) {
+      m = cull_window(f, sph, 0, cone, lo, hi);
+    } else {
+      __shared__ float s_list[3][64];  // compaction scratch: lo, hi, index
+      int count = 0;
+      const int nwords = (f.n + 63) >> 6;
+      for (int w = 0; w < nwords; w++) {
+        float wlo, whi;
+        const uint64_t mw = cull_window(f, sph, w * 64, cone, wlo, whi);
+        const int cw = __builtin_popcountll(mw);
+        if (count + cw > 64) {
+          full = true;
+          break;
+        }
+        if ((mw >> lane) & 1ull) {
+          const int dst = count + (int)__builtin_amdgcn_mbcnt_hi(
+                                      (uint32_t)(mw >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mw, 0u));
+          s_list[0][dst] = wlo;
+          s_list[1][dst] = whi;
+          s_list[2][dst] = __int_as_float(w * 64 + lane);
+        }
+        count += cw;
+      }
+      __syncthreads();  // one wave: orders its own LDS writes before the reads
+      if (!full) {
+        m = count >= 64 ? ~0ull : ((1ull << count) - 1ull);
+        if (lane < count) {
+          lo = s_list[0][lane];
+          hi = s_list[1][lane];
+          cidx = __float_as_int(s_list[2][lane]);
+        }
+      }
+    }
+  }
+  // the helpers of trace_tile_window_r (entry 63 is readable here for the same reasons)
+  auto entry = [&](uint32_t e) { return LIST ? (uint32_t)__builtin_amdgcn_readlane(cidx, (int)e) : e; };
+  auto first_entry = [](uint64_t x) -> uint32_t {
+    uint32_t e;
+    __asm__("s_ff1_i32_b64 %0, %1" : "=s"(e) : "s"(x));
+    return e & 63u;
+  };
+  auto clear_entry = [](uint64_t x, uint32_t e) -> uint64_t { return x & ~(1ull << e); };
+  auto advance = [&](const float (&L)[R]) {
+    px[0] = px[0] + dx[0] * L[0];
+    py[0] = py[0] + dy[0] * L[0];
+    pz[0] = pz[0] + dz[0] * L[0];
+    iters[0] += mv[0] > 0.0f ? 1 : 0;  // a step of a marching ray
+    mv[0] = L[0];
+    tacc[0] = tacc[0] + L[0];
+  };
+  auto visit = [&](float cx, float cy, float cz, float rad, float s_pass, int k, float (&L)[R]) {
+    float ss[R];
+    ss[0] = dist2(px[0], py[0], pz[0], cx, cy, cz);
+    (void)pass_body_r<R>(ss, s_pass, rad, k, L, draw);
+  };
+  int trips = 1;
+  const int cull_end = full ? 1 : kCullSafeIterations;
+  if (kSlots > 0 && !full && __builtin_popcountll(m) <= kSlots) {
+    constexpr int NS = kSlots > 0 ? kSlots : 1;
+    float scx[NS], scy[NS], scz[NS], sr[NS], ssp[NS];
+    int sk[NS];
+    uint64_t mm = m;
+#pragma unroll
+    for (int j = 0; j < kSlots; j++) {
+      scx[j] = scy[j] = scz[j] = sr[j] = ssp[j] = 0.0f;  // an empty slot never passes
+      sk[j] = 0;
+      if (mm) {
+        const int k = entry(__builtin_ctzll(mm));
+        mm &= mm - 1;
+        const SphereRec r = rec_at(sph, k);
+        scx[j] = r.cx; scy[j] = r.cy; scz[j] = r.cz;
+        sr[j] = r.r; ssp[j] = r.s_pass;
+        sk[j] = k;
+      }
+    }
+    for (; any_marching() && trips < cull_end; ++trips) {
+      float L[R] = {0.0f};
+#pragma unroll
+      for (int j = 0; j < kSlots; j++) visit(scx[j], scy[j], scz[j], sr[j], ssp[j], sk[j], L);
+      advance(L);
+    }
+  } else {
+    float tlo = 0.0f;
+    for (; any_marching() && trips < cull_end; ++trips) {
+      float L[R] = {0.0f};
+      if (trips % 2 == 1)  // the low end, every second step: it only rises
+        tlo = __uint_as_float(wave_min_u32(mv[0] > 0.0f ? __float_as_uint(tacc[0]) : 0x7f800000u));
+      const float thi = __uint_as_float(wave_max_u32(__float_as_uint(tacc[0])));
+      const uint64_t win =
+          m & __builtin_amdgcn_ballot_w64(lo < thi) & __builtin_amdgcn_ballot_w64(hi > tlo);
+      if (win) {  // in index order, the next record's scalar loads issued ahead
+        uint32_t e = first_entry(win);
+        uint64_t mm = clear_entry(win, e);
+        uint32_t k = entry(e);
+        const SphereRec s0 = rec_at(sph, k);
+        float cx = s0.cx, cy = s0.cy, cz = s0.cz, rad = s0.r, sp = s0.s_pass;
+        bool more;
+        do {
+          const uint32_t en = first_entry(mm);
+          const uint32_t kn = entry(en);
+          const SphereRec sn = rec_at(sph, kn);
+          const float ncx = sn.cx, ncy = sn.cy, ncz = sn.cz, nr = sn.r, nsp = sn.s_pass;
+          visit(cx, cy, cz, rad, sp, (int)k, L);
+          more = mm != 0;
+          mm = clear_entry(mm, en);
+          k = kn; cx = ncx; cy = ncy; cz = ncz; rad = nr; sp = nsp;
+        } while (more);
+      }
+      advance(L);
+    }
+  }
+  // Every sphere in index order, every step: own origins, culling off, or past kCullSafeIterations.
+  for (; any_marching() && trips < kMaxIterations; ++trips) {
+    float L[R] = {0.0f};
+    for (int k = 0; k < f.n; k++) {
+      const SphereRec r = rec_at(sph, k);
+      visit(r.cx, r.cy, r.cz, r.r, r.s_pass, k, L);
+    }
+    advance(L);
+  }
+  if (trips >= kMaxIterations && any_marching() && lane == 0) atomicOr(f.status, 1);
+  const bool live = q < a.count;
+  uint32_t rgba = 0u;
+  float depth = 0.0f;
+  if constexpr (SHADE) {
+    // draw < n <= 1024: a 32-bit byte offset from the records' base
+    const SphereRec d = *(const SphereRec*)((const char*)sph + (uint32_t)draw[0] * (uint32_t)sizeof(SphereRec));
+    const Shading sh = shade_texel<NoProbe, true, true>(f, d, px[0], py[0], pz[0], nullptr, ox, oy, oz);
+    const uint32_t texel = f.tex[sh.tex];
+    if (live && ok && sh.outside) atomicOr(f.status, 2);  // the reference would read outside the image
+    rgba = shade_rgba(sh.outside ? 0u : texel, sh.brightness);
+    depth = sh.depth;
+  } else if (a.depth) {  // VLength(r->pos - origin) of :375 alone
+    const float bx = px[0] - ox, by = py[0] - oy, bz = pz[0] - oz;
+    depth = sqrt_cr((bx * bx + by * by) + bz * bz);
+  }
+  if (live) {  // an invalid ray: sphere -1, all-zero bytes elsewhere
+    if (a.pos) {
+      float* const o = a.pos + 3 * q;
+      o[0] = ok ? px[0] : 0.0f;
+      o[1] = ok ? py[0] : 0.0f;
+      o[2] = ok ? pz[0] : 0.0f;
+    }
+    if (a.depth) a.depth[q] = ok ? depth : 0.0f;
+    if (a.sphere) a.sphere[q] = ok ? draw[0] : -1;
+    if (a.steps) a.steps[q] = ok ? iters[0] : 0;
+    if constexpr (SHADE) a.rgba[q] = ok ? rgba : 0u;
+  }
+}
+
+// LIST: n > 64, the records in device memory (f.spheres) and the culled list per wave; else
+// they travel in the kernel arguments, as for the frame kernels.
+template <bool LIST, bool SHADE, bool OWN>
+__global__ __launch_bounds__(64) void k_cast_rays(std::conditional_t<LIST, FrameRec, InlineArgs> args,
+                                                  RayArgs rays) {
+  if constexpr (LIST) cast_rays_wave<true, SHADE, OWN>(args, args.spheres, rays);
+  else cast_rays_wave<false, SHADE, OWN>(args.f, args.s, rays);
+}
+
 }  // namespace
 
 // Pixels per lane R of an ordered launch (adaptive tile order): the widest
@@ -1220,6 +1493,43 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
       case 3: hipExtLaunchKernelGGL(k_trace_window_list<3>, gr, b, 0, s, nullptr, ev, 0, g); break;
       default: hipExtLaunchKernelGGL(k_trace_window_list<4>, gr, b, 0, s, nullptr, ev, 0, g); break;
     }
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+namespace {
+
+template <bool SHADE, bool OWN>
+void launch_cast(const FrameRec& f, const SphereRec* host_spheres, const RayArgs& rays, dim3 gr,
+                 hipStream_t s, hipEvent_t ev) {
+  const dim3 b(64);
+  if (f.n <= kInlineSpheres) {
+    InlineArgs args;
+    args.f = f;
+    for (int k = 0; k < f.n; k++) args.s[k] = host_spheres[k];
+    hipLaunchKernelGGL((k_cast_rays<false, SHADE, OWN>), gr, b, 0, s, args, rays);
+  } else {
+    hipExtLaunchKernelGGL((k_cast_rays<true, SHADE, OWN>), gr, b, 0, s, nullptr, ev, 0, f, rays);
+  }
+}
+
+}  // namespace
+
+int launch_cast_rays(const FrameRec& f, const SphereRec* host_spheres, const RayArgs& rays,
+                     void* stream, void* done_event) {
+  if (rays.count <= 0 || rays.count > 0x7fffffffLL || !rays.dirs || f.n <= 0) return -1;
+  if (!rays.pos && !rays.depth && !rays.sphere && !rays.steps && !rays.rgba) return -1;
+  if (f.n > kInlineSpheres && !f.spheres) return -1;
+  const dim3 gr((unsigned)((rays.count + 63) / 64));
+  hipStream_t s = (hipStream_t)stream;
+  const hipEvent_t ev = (hipEvent_t)done_event;
+  const bool own = rays.origins != nullptr;
+  if (rays.rgba) {
+    if (own) launch_cast<true, true>(f, host_spheres, rays, gr, s, ev);
+    else launch_cast<true, false>(f, host_spheres, rays, gr, s, ev);
+  } else {
+    if (own) launch_cast<false, true>(f, host_spheres, rays, gr, s, ev);
+    else launch_cast<false, false>(f, host_spheres, rays, gr, s, ev);
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -62,6 +62,7 @@ ABI_SYMBOLS = (
     "sfrt_multi_use_test_transport", "sfrt_world_get_option",
     "sfrt_voxel_get_option", "sfrt_glsl_get_option", "sfrt_world_ray_cache_stats",
     "sfrt_world_tile_record_bytes", "sfrt_world_render_band_aux", "sfrt_world_update_image_aux",
+    "sfrt_world_cast_rays", "sfrt_world_cast_rays_device",
 )
 
 SFRT_MULTI_AUTO, SFRT_MULTI_RCCL, SFRT_MULTI_PEER = 0, 1, 2
@@ -98,6 +99,14 @@ class AuxPlanes(ctypes.Structure):
                 ("sphere", ctypes.c_void_p), ("sphere_pitch_bytes", ctypes.c_int64),
                 ("steps", ctypes.c_void_p), ("steps_pitch_bytes", ctypes.c_int64)]
 
+
+class RayHits(ctypes.Structure):
+    """sfrt_ray_hits: the per-ray outputs of sfrt_world_cast_rays[_device] (None = not wanted)."""
+    _fields_ = [("pos", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("sphere", ctypes.c_void_p),
+                ("steps", ctypes.c_void_p), ("rgba", ctypes.c_void_p)]
+
+
+RAY_OUTPUTS = ("pos", "depth", "sphere", "steps", "rgba")
 
 _lib = None
 
@@ -139,6 +148,8 @@ def lib() -> ctypes.CDLL:
         "sfrt_world_render_band_aux": ([W, vp, ctypes.c_int64, P(AuxPlanes), c_int, c_int, vp],
                                        c_int),
         "sfrt_world_update_image_aux": ([W, vp, vp, vp, vp, c_int, c_int, c_int, c_int], c_int),
+        "sfrt_world_cast_rays": ([W, vp, vp, ctypes.c_int64, P(RayHits)], c_int),
+        "sfrt_world_cast_rays_device": ([W, vp, vp, ctypes.c_int64, P(RayHits), vp], c_int),
         "sfrt_world_check": ([W, vp], c_int),
         "sfrt_world_row_costs": ([W, vp, c_int, P(c_int), P(c_int)], c_int),
         "sfrt_multi_cost_bands": ([vp, c_int, c_int, c_float, vp, vp], c_int),
@@ -468,6 +479,47 @@ class World:
         steps = np.zeros((h, w), dtype=np.int32)
         self.update_image_aux(rgba, depth, sphere, steps)
         return rgba, depth, sphere, steps
+
+    # --- ray queries ---
+    def cast_rays(self, dirs, origins=None, outputs=RAY_OUTPUTS) -> dict:
+        """SphereWorld::Raycast for a batch of caller-supplied rays (sfrt_world_cast_rays).
+
+        dirs: (N, 3) float32, un-normalised; origins: (N, 3) float32, or None for the world's
+        camera position.  Returns {name: array} for the requested outputs: pos (N, 3) float32,
+        depth (N,) float32, sphere and steps (N,) int32, rgba (N, 4) uint8.  An invalid ray
+        (non-finite component, zero / underflowing / overflowing length) has sphere == -1 and
+        zeros elsewhere."""
+        dirs = np.ascontiguousarray(np.asarray(dirs, dtype=np.float32).reshape(-1, 3))
+        n = dirs.shape[0]
+        if origins is not None:
+            origins = np.ascontiguousarray(np.asarray(origins, dtype=np.float32).reshape(-1, 3))
+            if origins.shape[0] != n:
+                raise ValueError("origins must hold one position per direction")
+        shapes = {"pos": ((n, 3), np.float32), "depth": ((n,), np.float32),
+                  "sphere": ((n,), np.int32), "steps": ((n,), np.int32), "rgba": ((n, 4), np.uint8)}
+        res = {name: np.zeros(*shapes[name]) for name in outputs}
+        hits = RayHits()
+        for name, arr in res.items():
+            # an empty array's pointer still says "requested"
+            setattr(hits, name, arr.ctypes.data if n else 4)
+        _check(lib().sfrt_world_cast_rays(self._h, dirs.ctypes.data if n else 4,
+                                          None if origins is None else (origins.ctypes.data if n else 4),
+                                          n, ctypes.byref(hits)), "cast_rays")
+        return res
+
+    def cast_rays_device(self, dirs_ptr: int, origins_ptr, count: int, stream: int = 0, pos=None,
+                         depth=None, sphere=None, steps=None, rgba=None) -> None:
+        """Asynchronous sfrt_world_cast_rays_device on `stream`: device pointers (ints) to
+        count*3 float32 directions and origins (origins_ptr None or 0: the camera position) and
+        to each wanted output; the status is left to check(stream)."""
+        hits = RayHits()
+        for name, ptr in zip(RAY_OUTPUTS, (pos, depth, sphere, steps, rgba)):
+            if ptr:
+                setattr(hits, name, int(ptr))
+        _check(lib().sfrt_world_cast_rays_device(self._h, ctypes.c_void_p(dirs_ptr or None),
+                                                 ctypes.c_void_p(origins_ptr or None), int(count),
+                                                 ctypes.byref(hits), ctypes.c_void_p(stream or None)),
+               "cast_rays_device")
 
     def submit_frame(self, frame: "HostFrame") -> int:
         """Pipelined full-frame fill into a pinned HostFrame; returns a ticket."""
