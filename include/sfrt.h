@@ -148,7 +148,7 @@ SFRT_API int sfrt_world_check(sfrt_world* w, void* hip_stream);
  * The planes come from kernels of their own, which compute their ray directions: an aux call
  * neither reads, fills nor invalidates the ray cache (SFRT_OPT_RAY_CACHE_MB) and leaves the
  * counters of sfrt_world_ray_cache_stats alone.  sfrt_world_submit_frame, sfrt_multi_* and the
- * voxel and GLSL renderers have no planes. */
+ * GLSL renderer have no planes; the voxel renderer has its own (sfrt_voxel_render_band_aux). */
 typedef struct {
   void* depth;  int64_t depth_pitch_bytes;   /* float   per pixel, or NULL */
   void* sphere; int64_t sphere_pitch_bytes;  /* int32_t per pixel, or NULL */
@@ -505,6 +505,64 @@ SFRT_API int sfrt_voxel_update_image(sfrt_voxel* v, uint8_t* pixels, int ystart,
 SFRT_API int sfrt_voxel_render_band(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes, int row0,
                                     int rows, void* hip_stream);
 SFRT_API int sfrt_voxel_check(sfrt_voxel* v, void* hip_stream);
+
+/* ---- the voxel frame fill's per-pixel planes: depth, cell, face, DDA steps ----
+ * For pixel (i, j) of the world's width x height frame there are four optional planes of 4 bytes
+ * per pixel, written by the same launch that writes the colour.  Line numbers are World.cpp's.
+ *   face  (int32_t): what ended Raycast.
+ *                    0: the loop of :324 ran out (the sf::Color::Black return of :452).
+ *                    4: a billboard's opaque texel (the return at :373).
+ *                    +-1, +-2, +-3: a block hit (:385).  The magnitude is colRay of that step
+ *                    (1 = x, 2 = y, 3 = z; :329-349); the sign is that axis's dirXsign as
+ *                    :312-314 set it, before :397-410 zero the others: -1 when the direction's
+ *                    component is > 0, so the sign is the sign of the hit face's outward normal.
+ *                    Defined for colour blocks (textureID < 0) as well.
+ *   cell  (int32_t): block hit: the map key (posi.x << 20) + (posi.y << 10) + posi.z of :385,
+ *                    computed in wrapping 32-bit arithmetic as the lookup does; it is >= 0 for
+ *                    every hit.  Billboard: DI, the index into the list given to
+ *                    sfrt_voxel_set_dynamics.  Nothing: -1.
+ *   depth (float):   the binary32 value of `dist` when Raycast ends.  Block hit: tryDist as
+ *                    assigned at :380 (the light loop's reuse of `dist` at :419 is not visible).
+ *                    Billboard: d->distToCamera as assigned at :356.  Nothing: `dist` at loop
+ *                    exit.  It is the reference's own ray parameter along the un-normalised
+ *                    r->dir, which by :77 has unit component along the camera's horizontal
+ *                    forward axis; nothing more is claimed of it.
+ *   steps (int32_t): the number of times the body of the `while` at :324 was entered, the trip
+ *                    that hit included; 0 when the first loop test fails.
+ * Any plane may be NULL, but not all of them.  A non-NULL plane's pitch must be a multiple of 4
+ * and at least 4*width; a NULL plane's pitch is ignored.  Violations return SFRT_E_INVALID with
+ * nothing queued or written.  The plain calls' own checks apply unchanged (SFRT_E_EMPTY, band
+ * bounds, sample-grid limits), and the plain calls keep their behaviour exactly.
+ * Planes must not overlap each other or the colour target; that is the caller's duty.
+ * A billboard's outcome depends on a texel's alpha, and an out-of-range texel read gives the
+ * restatement's magenta with alpha 255: the planes are defined, and equal the reference's with
+ * that texel, even when the status is SFRT_E_TEXEL.
+ * With SFRT_OPT_SUPERSAMPLE S = 2 or 4 the colour is the box-filtered pixel as always, and the
+ * planes are those of the output pixel's FIRST SAMPLE, sample pixel (S*i, S*j) of the
+ * S*width x S*height frame, as the sphere planes are: no filtered or per-sample planes.
+ * SFRT_OPT_TILE_ORDER is honoured exactly as sfrt_voxel_render_band honours it: an aux band and
+ * a plain band of one stream share a chain.  sfrt_multi_*, the GLSL renderer and sfrt_world_*
+ * are untouched. */
+typedef struct {
+  void* depth; int64_t depth_pitch_bytes;   /* float   per pixel, or NULL */
+  void* cell;  int64_t cell_pitch_bytes;    /* int32_t per pixel, or NULL */
+  void* face;  int64_t face_pitch_bytes;    /* int32_t per pixel, or NULL */
+  void* steps; int64_t steps_pitch_bytes;   /* int32_t per pixel, or NULL */
+} sfrt_voxel_aux_planes;
+/* sfrt_voxel_render_band plus the planes (device memory on this world's device): same rows, same
+ * global row index, same stream semantics; row r of a plane at plane + (r - row0) * its pitch.
+ * The status is left to sfrt_voxel_check. */
+SFRT_API int sfrt_voxel_render_band_aux(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes,
+                                        const sfrt_voxel_aux_planes* aux, int row0, int rows,
+                                        void* hip_stream);
+/* sfrt_voxel_update_image plus host planes of width*height elements (pitch 4*width), addressed
+ * with the same strides; only addressed elements are written, in every plane.  A single-pixel
+ * pick of (i, j) is xstart = i, xadd = width, ystart = j, yadd = height.  On SFRT_E_TEXEL the
+ * call returns the code and writes neither `pixels` nor any plane, as sfrt_voxel_update_image
+ * leaves `pixels` unwritten. */
+SFRT_API int sfrt_voxel_update_image_aux(sfrt_voxel* v, uint8_t* pixels, float* depth, int32_t* cell,
+                                         int32_t* face, int32_t* steps, int ystart, int yadd,
+                                         int xstart, int xadd);
 /* SFRT_OPT_TILE_ORDER as for sfrt_world, but off (0) by default here: render_band with 1
  * dispatches 8x8 tiles longest-first by the DDA + shadow steps of two frames back (same
  * bytes; measured 1-6% slower on the voxel worlds).

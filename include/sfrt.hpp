@@ -395,6 +395,22 @@ class VoxelWorld {
     check(sfrt_voxel_render_band(v_, dev_pixels, pitch_bytes, row0, rows, hip_stream),
           "render_band");
   }
+  // The same plus the per-pixel planes (sfrt.h "the voxel frame fill's per-pixel planes"): depth,
+  // cell (map key or billboard index), face (what ended Raycast) and steps; any null, not all.
+  // A pick of pixel (i, j): UpdateImageAux(.., j, height, i, width).
+  void UpdateImageAux(uint8_t* pixels, float* depth, int32_t* cell, int32_t* face, int32_t* steps,
+                      short ystart, short yadd, short xstart, short xadd) {
+    push_state();
+    check(sfrt_voxel_update_image_aux(v_, pixels, depth, cell, face, steps, ystart, yadd, xstart,
+                                      xadd),
+          "UpdateImageAux");
+  }
+  void RenderBandAux(void* dev_pixels, int64_t pitch_bytes, const sfrt_voxel_aux_planes& aux,
+                     int row0, int rows, void* hip_stream) {
+    push_state();
+    check(sfrt_voxel_render_band_aux(v_, dev_pixels, pitch_bytes, &aux, row0, rows, hip_stream),
+          "render_band_aux");
+  }
   void Check(void* hip_stream = nullptr) { check(sfrt_voxel_check(v_, hip_stream), "check"); }
   // SFRT_OPT_TILE_ORDER, SFRT_OPT_SUPERSAMPLE (sfrt.h): the latter, 2 or 4, box-filters S x S
   // samples per pixel inside the kernel; width, height and every buffer stay in output pixels.

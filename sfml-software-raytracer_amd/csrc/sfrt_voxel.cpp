@@ -152,7 +152,14 @@ struct sfrt_voxel {
   int* d_status = nullptr;
   uint32_t* d_frame = nullptr;
   size_t d_frame_px = 0;
-  int tile_order_on = 0;     // SFRT_OPT_TILE_ORDER: off by default here (slower)
+  // sfrt_voxel_update_image_aux: per requested plane (depth, cell, face, steps) a compact device
+  // plane, grown the way d_frame is (stream-ordered on `stream`), and its pinned staging (a
+  // replaced one retired, sfrt_host.h: no hipHostFree while frames run)
+  uint32_t* d_aux[4] = {};
+  size_t d_aux_px[4] = {};
+  uint32_t* h_aux[4] = {};
+  size_t h_aux_px[4] = {};
+  int tile_order_on = 0;    // SFRT_OPT_TILE_ORDER: off by default here (slower)
   // SFRT_OPT_SUPERSAMPLE: log2 of the factor S (0, 1, 2).  S > 1: the frame's samples are the
   // pixels of World::UpdateImage at S * width x S * height (prepare() builds the tables for that
   // size), box-filtered in the kernel
@@ -187,6 +194,10 @@ struct sfrt_voxel {
     relay.release();
     (void)hipFree(d_status);
     (void)hipFree(d_frame);
+    for (int q = 0; q < 4; q++) {
+      (void)hipFree(d_aux[q]);
+      (void)hipHostFree(h_aux[q]);
+    }
     if (stream) (void)hipStreamDestroy(stream);
   }
 
@@ -534,9 +545,12 @@ int sfrt_voxel_set_lights(sfrt_voxel* v, const sfrt_light* lights, int count) {
   return SFRT_OK;
 }
 
-int sfrt_voxel_update_image(sfrt_voxel* v, uint8_t* pixels, int ystart, int yadd, int xstart,
-                            int xadd) {
+// sfrt_voxel_update_image and sfrt_voxel_update_image_aux (planes: depth, cell, face, steps as
+// host planes of width*height elements, any null but not all; nullptr for the plain call).
+static int update_image_body(sfrt_voxel* v, uint8_t* pixels, void* const* planes, int ystart,
+                             int yadd, int xstart, int xadd) {
   if (!v || !pixels || ystart < 0 || xstart < 0 || yadd <= 0 || xadd <= 0) return SFRT_E_INVALID;
+  if (planes && !planes[0] && !planes[1] && !planes[2] && !planes[3]) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(v->mu);
   const int sub_w = xstart < v->width ? (v->width - xstart + xadd - 1) / xadd : 0;
   const int sub_h = ystart < v->height ? (v->height - ystart + yadd - 1) / yadd : 0;
@@ -551,6 +565,32 @@ int sfrt_voxel_update_image(sfrt_voxel* v, uint8_t* pixels, int ystart, int yadd
     v->d_frame_px = 0;
     HIP_TRY(hipMallocAsync((void**)&v->d_frame, px * 4, v->stream));
     v->d_frame_px = px;
+  }
+  sfrt::VoxAux aux{};
+  for (int q = 0; planes && q < 4; q++) {
+    if (!planes[q]) continue;
+    if (v->d_aux_px[q] < px) {  // as d_frame
+      if (v->d_aux[q]) HIP_TRY(hipFreeAsync(v->d_aux[q], v->stream));
+      v->d_aux[q] = nullptr;
+      v->d_aux_px[q] = 0;
+      HIP_TRY(hipMallocAsync((void**)&v->d_aux[q], px * 4, v->stream));
+      v->d_aux_px[q] = px;
+    }
+    if (v->h_aux_px[q] < px) {
+      const size_t cap = sfrt::grown_capacity(v->h_aux_px[q], px);
+      v->retired_host.add(v->h_aux[q]);  // not hipHostFree: it would wait for the whole device
+      v->h_aux[q] = nullptr;
+      v->h_aux_px[q] = 0;
+      HIP_TRY(hipHostMalloc((void**)&v->h_aux[q], cap * 4, hipHostMallocDefault));
+      v->h_aux_px[q] = cap;
+    }
+  }
+  if (planes) {  // compact planes beside the compact frame
+    aux.depth = planes[0] ? (float*)v->d_aux[0] : nullptr;
+    aux.cell = planes[1] ? (int32_t*)v->d_aux[1] : nullptr;
+    aux.face = planes[2] ? (int32_t*)v->d_aux[2] : nullptr;
+    aux.steps = planes[3] ? (int32_t*)v->d_aux[3] : nullptr;
+    aux.depth_pitch = aux.cell_pitch = aux.face_pitch = aux.steps_pitch = sub_w;
   }
   sfrt::VoxFrame f;
   int rc = v->prepare(f, v->stream);
@@ -567,26 +607,63 @@ int sfrt_voxel_update_image(sfrt_voxel* v, uint8_t* pixels, int ystart, int yadd
   f.sub_rows = sub_h << ss;
   f.out = v->d_frame;
   f.out_pitch = sub_w;
-  if (sfrt::launch_voxel(f, v->stream, v->launch_event())) return SFRT_E_HIP;
+  if (sfrt::launch_voxel(f, v->stream, v->launch_event(), planes ? &aux : nullptr)) return SFRT_E_HIP;
   HIP_TRY(v->launched(v->stream));
   std::vector<uint32_t> stage(px);
   HIP_TRY(hipMemcpyAsync(stage.data(), v->d_frame, px * 4, hipMemcpyDeviceToHost, v->stream));
+  for (int q = 0; planes && q < 4; q++)
+    if (planes[q])
+      HIP_TRY(hipMemcpyAsync(v->h_aux[q], v->d_aux[q], px * 4, hipMemcpyDeviceToHost, v->stream));
   rc = v->read_status(v->stream);
-  if (rc) return rc;
+  if (rc) return rc;  // SFRT_E_TEXEL included: neither pixels nor any plane is written
   const size_t W = (size_t)v->width;
-  for (int b = 0; b < sub_h; b++) {
-    const size_t j = (size_t)ystart + (size_t)b * yadd;
-    for (int a = 0; a < sub_w; a++)
-      std::memcpy(pixels + (j * W + (size_t)xstart + (size_t)a * xadd) * 4, &stage[(size_t)b * sub_w + a], 4);
-  }
+  const auto scatter = [&](const uint32_t* src, uint8_t* dst) {
+    for (int b = 0; b < sub_h; b++) {
+      const size_t j = (size_t)ystart + (size_t)b * yadd;
+      for (int a = 0; a < sub_w; a++)
+        std::memcpy(dst + (j * W + (size_t)xstart + (size_t)a * xadd) * 4, &src[(size_t)b * sub_w + a], 4);
+    }
+  };
+  scatter(stage.data(), pixels);
+  for (int q = 0; planes && q < 4; q++)
+    if (planes[q]) scatter(v->h_aux[q], (uint8_t*)planes[q]);
   return SFRT_OK;
 }
 
-int sfrt_voxel_render_band(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes, int row0, int rows,
-                           void* hip_stream) {
+int sfrt_voxel_update_image(sfrt_voxel* v, uint8_t* pixels, int ystart, int yadd, int xstart,
+                            int xadd) {
+  return update_image_body(v, pixels, nullptr, ystart, yadd, xstart, xadd);
+}
+
+int sfrt_voxel_update_image_aux(sfrt_voxel* v, uint8_t* pixels, float* depth, int32_t* cell,
+                                int32_t* face, int32_t* steps, int ystart, int yadd, int xstart,
+                                int xadd) {
+  void* const planes[4] = {depth, cell, face, steps};
+  return update_image_body(v, pixels, planes, ystart, yadd, xstart, xadd);
+}
+
+// sfrt_voxel_render_band and sfrt_voxel_render_band_aux (with_aux false for the plain call).
+static int render_band_body(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes,
+                            const sfrt_voxel_aux_planes* aux, bool with_aux, int row0, int rows,
+                            void* hip_stream) {
   if (!v || !dev_pixels || row0 < 0 || rows < 0 || pitch_bytes % 4 != 0) return SFRT_E_INVALID;
+  if (with_aux && (!aux || (!aux->depth && !aux->cell && !aux->face && !aux->steps)))
+    return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(v->mu);
   if (pitch_bytes < (int64_t)v->width * 4 || row0 + rows > v->height) return SFRT_E_INVALID;
+  sfrt::VoxAux a{};
+  if (with_aux) {
+    const auto pitch_ok = [&](const void* p, int64_t pitch) {
+      return !p || (pitch % 4 == 0 && pitch >= (int64_t)v->width * 4);
+    };
+    if (!pitch_ok(aux->depth, aux->depth_pitch_bytes) || !pitch_ok(aux->cell, aux->cell_pitch_bytes) ||
+        !pitch_ok(aux->face, aux->face_pitch_bytes) || !pitch_ok(aux->steps, aux->steps_pitch_bytes))
+      return SFRT_E_INVALID;
+    a.depth = (float*)aux->depth; a.depth_pitch = aux->depth ? aux->depth_pitch_bytes / 4 : 0;
+    a.cell = (int32_t*)aux->cell; a.cell_pitch = aux->cell ? aux->cell_pitch_bytes / 4 : 0;
+    a.face = (int32_t*)aux->face; a.face_pitch = aux->face ? aux->face_pitch_bytes / 4 : 0;
+    a.steps = (int32_t*)aux->steps; a.steps_pitch = aux->steps ? aux->steps_pitch_bytes / 4 : 0;
+  }
   if (rows == 0) return SFRT_OK;
   if (!v->sample_grid_ok(v->width, rows)) return SFRT_E_INVALID;
   sfrt::DeviceGuard g(v->device);
@@ -604,6 +681,7 @@ int sfrt_voxel_render_band(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes,
   f.out = (uint32_t*)dev_pixels;
   f.out_pitch = pitch_bytes / 4;
   long long tiles = 0;
+  // the same key with and without planes: an aux band and a plain band of one stream share a chain
   const long long key = v->tile_order_on ? sfrt::voxel_tile_key(f, &tiles) : 0;
   sfrt::TileSchedPtrs p;
   sfrt::TileSched& sched = v->scheds.chain[v->scheds.pick(s)];
@@ -613,11 +691,21 @@ int sfrt_voxel_render_band(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes,
   f.prev_cost = p.prev_cost;
   f.next_order = p.next_order;
   f.cost_diff = p.cost_diff ? 1 : 0;
-  const bool queued = sfrt::launch_voxel(f, s, v->launch_event()) == 0;
+  const bool queued = sfrt::launch_voxel(f, s, v->launch_event(), with_aux ? &a : nullptr) == 0;
   HIP_TRY(sched.end(p, s, queued));
   if (!queued) return SFRT_E_HIP;
   HIP_TRY(v->launched(s));
   return SFRT_OK;
+}
+
+int sfrt_voxel_render_band(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes, int row0, int rows,
+                           void* hip_stream) {
+  return render_band_body(v, dev_pixels, pitch_bytes, nullptr, false, row0, rows, hip_stream);
+}
+
+int sfrt_voxel_render_band_aux(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes,
+                               const sfrt_voxel_aux_planes* aux, int row0, int rows, void* hip_stream) {
+  return render_band_body(v, dev_pixels, pitch_bytes, aux, true, row0, rows, hip_stream);
 }
 
 int sfrt_voxel_set_option(sfrt_voxel* v, int option, int value) {

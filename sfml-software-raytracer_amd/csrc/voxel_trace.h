@@ -95,10 +95,24 @@ struct VoxFrame {
   int32_t ss;
 };
 
+// The optional per-pixel planes of the frame fill (sfrt_voxel_render_band_aux):
+// device pointers, null = not wanted, pitches in elements (dwords).  Row r, column a of the band
+// (output pixels) at plane[r * pitch + a].  A kernel argument of its own, so that VoxFrame and
+// with it every plain kernel's scalar loads stay as they are.
+struct VoxAux {
+  float* depth;
+  int32_t* cell;
+  int32_t* face;
+  int32_t* steps;
+  long long depth_pitch, cell_pitch, face_pitch, steps_pitch;
+};
+
 // Tile grid of launch_voxel for f (8x8 tiles, of samples when f.ss > 0): key (> 0) and tile count.
 long long voxel_tile_key(const VoxFrame& f, long long* tiles);
 // done_event (hipEvent_t, may be null): recorded by the launch's own completion (its stop event).
-int launch_voxel(const VoxFrame& f, void* stream, void* done_event = nullptr);
+// aux != nullptr (at least one plane set): the plane-writing kernels on the same grid.
+int launch_voxel(const VoxFrame& f, void* stream, void* done_event = nullptr,
+                 const VoxAux* aux = nullptr);
 
 // Rewrites the key-indexed grid `cells` for a world of nx x ny x nz codes (`codes`, device,
 // x-major then y then z, as set_blocks takes them): every byte of planes x < bx, rows y < by,

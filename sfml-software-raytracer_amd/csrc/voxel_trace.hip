@@ -237,10 +237,17 @@ __device__ __forceinline__ uint32_t shade_hit(const VoxFrame& f, V3 pos, int32_t
               to_u8(min255((float)((c >> 16) & 0xffu) * litb)), c >> 24);
 }
 
-// World::Raycast, World.cpp:302-453.
-template <bool RECIP>
+// What ended World::Raycast for the lane (AUX kernels; include/sfrt.h "the voxel frame fill's
+// per-pixel planes"): read after the step loop from the registers the loop carries anyway.
+struct VoxHit {
+  float depth;
+  int32_t cell, face, steps;
+};
+
+// World::Raycast, World.cpp:302-453.  AUX: also the outcome in `hit` (untouched without it).
+template <bool RECIP, bool AUX>
 __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
-                              float atan_dir, uint32_t& work) {
+                              float atan_dir, uint32_t& work, VoxHit& hit) {
   const V3 cam{f.cam[0], f.cam[1], f.cam[2]};
   float dist = 0.0f;
   V3 pos = cam;
@@ -284,6 +291,10 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
   // selects per step, and left for the compiler to sink it carried two lane masks merged with
   // EXEC every step (193.3 -> 188.0 us, r5_ab6).
   uint32_t hcode = 0u, early = 0u;
+  // AUX: the trips of the loop's body (the one that hit included), and the distance of the
+  // billboard that stopped the lane (its `dist` is +inf by then; DI stays at that billboard)
+  uint32_t trips = 0u;
+  float stop_dist = 0.0f;
   if (0.0f < f.view_distance && 0u < f.maxiter) {
     for (uint32_t i = 0;;) {
       work++;
@@ -346,6 +357,7 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
                              to_u8(min255((float)((c >> 8) & 0xffu) * d.g)),
                              to_u8(min255((float)((c >> 16) & 0xffu) * d.b)), c >> 24);
                 tryDist = __builtin_inff();  // stops the lane through the loop test
+                if constexpr (AUX) stop_dist = bdist;
                 break;
               }
             }
@@ -361,10 +373,24 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
       pix = pos_i32<RECIP>(pos.x); piy = pos_i32<RECIP>(pos.y); piz = pos_i32<RECIP>(pos.z);
       cell_hit(f, pix, piy, piz, hcode);  // hcode != 0: hit a block (World.cpp:385)
       i++;
+      if constexpr (AUX) trips = i;
       if ((hcode != 0u) | !(dist < f.view_distance) | !(i < f.maxiter)) break;
     }
   }
-  if (early != 0u) return early;  // a billboard's texel with alpha > 127: never 0
+  if constexpr (AUX) {  // a march-out; the two returns below overwrite their fields
+    hit.depth = dist;
+    hit.cell = -1;
+    hit.face = 0;
+    hit.steps = (int32_t)trips;
+  }
+  if (early != 0u) {  // a billboard's texel with alpha > 127: never 0
+    if constexpr (AUX) {
+      hit.depth = stop_dist;
+      hit.cell = DI;
+      hit.face = 4;
+    }
+    return early;
+  }
   // the axis of the lane's last step, from that step's rays (kept in registers: the loop's last
   // assignment is its exit value), by the step's own rule
   if (RECIP) {
@@ -375,21 +401,39 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
     const bool ay = !ax & (last_y <= last_x) & (last_y <= last_z);
     colRay = ax ? 1 : (ay ? 2 : 3);
   }
-  if (hcode != 0u)
+  if (hcode != 0u) {
+    if constexpr (AUX) {
+      // the key of the lookup that hit (World.cpp:385, wrapping), and the crossed face: the axis
+      // with the sign of dirXsign (World.cpp:312-314), the face's outward normal
+      hit.cell = (int32_t)(((uint32_t)pix << 20) + ((uint32_t)piy << 10) + (uint32_t)piz);
+      hit.face = colRay == 1 ? (sx < 0.0f ? -1 : 1) : colRay == 2 ? (sy < 0.0f ? -2 : 2)
+                                                                  : (sz < 0.0f ? -3 : 3);
+    }
     return shade_hit<RECIP>(f, pos, pix, piy, piz, colRay, sx, sy, sz, dist,
                             (int)hcode - kVoxCellBias, work);
+  }
   return pack(0, 0, 0, 255);  // sf::Color::Black
 }
 
+template <bool AUX>
 __device__ uint32_t raycast(const VoxFrame& f, V3 dir, float yscale,
-                            float atan_dir, uint32_t& work) {
+                            float atan_dir, uint32_t& work, VoxHit& hit) {
   // the reciprocal divisions and, within the host's bound on the direction's spread, the plain
   // position conversions (pos_i32)
   const float lx = fabsf(dir.x), ly = fabsf(dir.y), lz = fabsf(dir.z);
   const bool ok = recip_ok(lx) && recip_ok(ly) && recip_ok(lz) &&
                   fmaxf(fmaxf(lx, ly), lz) <= f.dda_qlim * fminf(fminf(lx, ly), lz);
-  if (__builtin_amdgcn_ballot_w64(!ok)) return raycast_t<false>(f, dir, yscale, atan_dir, work);
-  return raycast_t<true>(f, dir, yscale, atan_dir, work);
+  if (__builtin_amdgcn_ballot_w64(!ok))
+    return raycast_t<false, AUX>(f, dir, yscale, atan_dir, work, hit);
+  return raycast_t<true, AUX>(f, dir, yscale, atan_dir, work, hit);
+}
+
+// The lane's outcome into the planes of `aux` at output pixel (row r, column a) of the band.
+__device__ __forceinline__ void store_planes(const VoxAux& aux, const VoxHit& hit, int r, int a) {
+  if (aux.depth) aux.depth[(long long)r * aux.depth_pitch + a] = hit.depth;
+  if (aux.cell) aux.cell[(long long)r * aux.cell_pitch + a] = hit.cell;
+  if (aux.face) aux.face[(long long)r * aux.face_pitch + a] = hit.face;
+  if (aux.steps) aux.steps[(long long)r * aux.steps_pitch + a] = hit.steps;
 }
 
 // 8x8 pixels per one-wave workgroup (a finished wave's slot refills at once;
@@ -414,9 +458,13 @@ __device__ uint32_t raycast(const VoxFrame& f, V3 dir, float yscale,
 // cost record that follows stays in the kernels' own bodies: inlined through here the compiler
 // turned tile_bucket's chain into other scalar code, and k_voxel_ordered<true> is to compile to
 // what it did before the supersampling kernels came.
-template <int SS>
-__device__ __forceinline__ bool voxel_tile(const VoxFrame& f, int tiles_x, int ntiles, int& tile,
-                                           uint32_t& cls, uint32_t& work) {
+//
+// AUX (k_voxel_aux): the planes of `aux` beside the colour, one dword per non-null plane from the
+// lane that stores the pixel -- for SS > 0 the group's leader, whose sample is the output pixel's
+// first, (S * i, S * j).  The null tests are wave-uniform (kernel arguments).
+template <int SS, bool AUX>
+__device__ __forceinline__ bool voxel_tile(const VoxFrame& f, const VoxAux& aux, int tiles_x,
+                                           int ntiles, int& tile, uint32_t& cls, uint32_t& work) {
   const int lane = threadIdx.x & 63;
   int slot = (int)blockIdx.x;
   if (f.prev_cost) {
@@ -438,20 +486,26 @@ __device__ __forceinline__ bool voxel_tile(const VoxFrame& f, int tiles_x, int n
   const int j = subset_index<SS>(f.ystart, f.yadd, bc);
   work = 0;
   const V3 dir{f.col[3 * i], f.row[2 * j], f.col[3 * i + 1]};
-  const uint32_t rgba = raycast(f, dir, f.row[2 * j + 1], f.col[3 * i + 2], work);
+  VoxHit hit;
+  const uint32_t rgba = raycast<AUX>(f, dir, f.row[2 * j + 1], f.col[3 * i + 2], work, hit);
   // The store's pixel from the lane id again (mbcnt, not threadIdx): kept live across
   // raycast(), a, b and `in` were spilled to scratch (16 bytes per lane).
   const int lane2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   const int a2 = tx * 8 + (lane2 & 7), r2 = ty * 8 + (lane2 >> 3);
   if constexpr (SS == 0) {
-    if (a2 < f.sub_w && r2 < f.sub_rows) f.out[(long long)r2 * f.out_pitch + a2] = rgba;
+    if (a2 < f.sub_w && r2 < f.sub_rows) {
+      f.out[(long long)r2 * f.out_pitch + a2] = rgba;
+      if constexpr (AUX) store_planes(aux, hit, r2, a2);
+    }
   } else {
     // every lane has its sample (edge lanes their duplicates) and the wave has reconverged
     // (raycast()'s branches are wave-uniform): the output pixel of sample (a2, r2) of the band is
     // (a2 >> SS, r2 >> SS), out and its pitch in output pixels
     const uint32_t px = group_box_rgba8<SS>(rgba);
-    if (group_leader<SS>(lane2) && a2 < f.sub_w && r2 < f.sub_rows)
+    if (group_leader<SS>(lane2) && a2 < f.sub_w && r2 < f.sub_rows) {
       f.out[(long long)(r2 >> SS) * f.out_pitch + (a2 >> SS)] = px;
+      if constexpr (AUX) store_planes(aux, hit, r2 >> SS, a2 >> SS);
+    }
   }
   return true;
 }
@@ -462,7 +516,7 @@ template <bool COST>
 __global__ __launch_bounds__(64, SFRT_VOX_WAVES) void k_voxel_ordered(VoxFrame f, int tiles_x, int ntiles) {
   int tile;
   uint32_t cls, work;
-  if (!voxel_tile<0>(f, tiles_x, ntiles, tile, cls, work)) return;
+  if (!voxel_tile<0, false>(f, VoxAux{}, tiles_x, ntiles, tile, cls, work)) return;
   if (COST) {
     // the tile's slowest ray, in DDA + shadow steps / 4 (the classes' scale)
     const uint32_t w = wave_max_u32(work);
@@ -475,8 +529,28 @@ template <bool COST, int SS>
 __global__ __launch_bounds__(64, SFRT_VOX_WAVES) void k_voxel_ordered_ss(VoxFrame f, int tiles_x, int ntiles) {
   int tile;
   uint32_t cls, work;
-  if (!voxel_tile<SS>(f, tiles_x, ntiles, tile, cls, work)) return;
+  if (!voxel_tile<SS, false>(f, VoxAux{}, tiles_x, ntiles, tile, cls, work)) return;
   if (COST) {  // as k_voxel_ordered: the sample tile's slowest ray
+    const uint32_t w = wave_max_u32(work);
+    if ((threadIdx.x & 63) == 0) store_cost(f.tile_cost, tile, tile_bucket(w >> 2), cls, f.cost_diff);
+  }
+}
+
+// The plane-writing instantiations (sfrt_voxel_render_band_aux), kernels of their
+// own over COST x SS with the planes in a kernel argument of their own: the kernels above keep
+// their arguments and compile to what they did.  The outcome's registers stay live across the
+// shading, so these take a bound of their own, seven waves per SIMD (up to 72 VGPRs): 63 VGPRs and
+// still eight waves without the cost record, 67 and seven with it, no scratch.
+#ifndef SFRT_VOX_AUX_WAVES
+#define SFRT_VOX_AUX_WAVES 7
+#endif
+template <bool COST, int SS>
+__global__ __launch_bounds__(64, SFRT_VOX_AUX_WAVES) void k_voxel_aux(VoxFrame f, int tiles_x, int ntiles,
+                                                                      VoxAux aux) {
+  int tile;
+  uint32_t cls, work;
+  if (!voxel_tile<SS, true>(f, aux, tiles_x, ntiles, tile, cls, work)) return;
+  if (COST) {  // as k_voxel_ordered
     const uint32_t w = wave_max_u32(work);
     if ((threadIdx.x & 63) == 0) store_cost(f.tile_cost, tile, tile_bucket(w >> 2), cls, f.cost_diff);
   }
@@ -521,9 +595,15 @@ void launch_voxel_ss(const VoxFrame& f, dim3 grid, long long tiles, void* stream
   hipExtLaunchKernelGGL((k_voxel_ordered_ss<COST, SS>), grid, dim3(64), 0, (hipStream_t)stream, nullptr,
                         (hipEvent_t)done_event, 0, f, (int)((f.sub_w + 7) / 8), (int)tiles);
 }
+template <bool COST, int SS>
+void launch_voxel_aux(const VoxFrame& f, const VoxAux& aux, dim3 grid, long long tiles, void* stream,
+                      void* done_event) {
+  hipExtLaunchKernelGGL((k_voxel_aux<COST, SS>), grid, dim3(64), 0, (hipStream_t)stream, nullptr,
+                        (hipEvent_t)done_event, 0, f, (int)((f.sub_w + 7) / 8), (int)tiles, aux);
+}
 }  // namespace
 
-int launch_voxel(const VoxFrame& f, void* stream, void* done_event) {
+int launch_voxel(const VoxFrame& f, void* stream, void* done_event, const VoxAux* aux) {
   long long tiles = 0;
   if (voxel_tile_key(f, &tiles) == 0) return 0;
   // the kernel reads the grid through a buffer resource over f.cells (f.cell_bytes) and the tables
@@ -537,6 +617,21 @@ int launch_voxel(const VoxFrame& f, void* stream, void* done_event) {
   if (f.ss < 0 || f.ss > 2) return -1;
   // whole S x S groups: the filter's cross-lane adds rely on it
   if (f.ss && ((f.sub_w | f.sub_row0 | f.sub_rows) & ((1 << f.ss) - 1))) return -1;
+  if (aux) {  // the same grid, the plane-writing kernels
+    if (!aux->depth && !aux->cell && !aux->face && !aux->steps) return -1;
+    const bool cost = f.tile_cost != nullptr;
+    if (f.ss == 0) {
+      if (cost) launch_voxel_aux<true, 0>(f, *aux, grid, tiles, stream, done_event);
+      else launch_voxel_aux<false, 0>(f, *aux, grid, tiles, stream, done_event);
+    } else if (f.ss == 1) {
+      if (cost) launch_voxel_aux<true, 1>(f, *aux, grid, tiles, stream, done_event);
+      else launch_voxel_aux<false, 1>(f, *aux, grid, tiles, stream, done_event);
+    } else {
+      if (cost) launch_voxel_aux<true, 2>(f, *aux, grid, tiles, stream, done_event);
+      else launch_voxel_aux<false, 2>(f, *aux, grid, tiles, stream, done_event);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+  }
   if (f.ss == 1) {
     if (f.tile_cost) launch_voxel_ss<true, 1>(f, grid, tiles, stream, done_event);
     else launch_voxel_ss<false, 1>(f, grid, tiles, stream, done_event);

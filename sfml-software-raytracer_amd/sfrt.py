@@ -63,6 +63,7 @@ ABI_SYMBOLS = (
     "sfrt_voxel_get_option", "sfrt_glsl_get_option", "sfrt_world_ray_cache_stats",
     "sfrt_world_tile_record_bytes", "sfrt_world_render_band_aux", "sfrt_world_update_image_aux",
     "sfrt_world_cast_rays", "sfrt_world_cast_rays_device",
+    "sfrt_voxel_render_band_aux", "sfrt_voxel_update_image_aux",
 )
 
 SFRT_MULTI_AUTO, SFRT_MULTI_RCCL, SFRT_MULTI_PEER = 0, 1, 2
@@ -98,6 +99,17 @@ class AuxPlanes(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_void_p), ("depth_pitch_bytes", ctypes.c_int64),
                 ("sphere", ctypes.c_void_p), ("sphere_pitch_bytes", ctypes.c_int64),
                 ("steps", ctypes.c_void_p), ("steps_pitch_bytes", ctypes.c_int64)]
+
+
+class VoxelAuxPlanes(ctypes.Structure):
+    """sfrt_voxel_aux_planes: device planes of sfrt_voxel_render_band_aux (None = not wanted)."""
+    _fields_ = [("depth", ctypes.c_void_p), ("depth_pitch_bytes", ctypes.c_int64),
+                ("cell", ctypes.c_void_p), ("cell_pitch_bytes", ctypes.c_int64),
+                ("face", ctypes.c_void_p), ("face_pitch_bytes", ctypes.c_int64),
+                ("steps", ctypes.c_void_p), ("steps_pitch_bytes", ctypes.c_int64)]
+
+
+VOXEL_PLANES = (("depth", np.float32), ("cell", np.int32), ("face", np.int32), ("steps", np.int32))
 
 
 class RayHits(ctypes.Structure):
@@ -185,6 +197,9 @@ def lib() -> ctypes.CDLL:
         "sfrt_voxel_light_dd_pass": ([ctypes.c_float], ctypes.c_float),
         "sfrt_voxel_update_image": ([vp, vp, c_int, c_int, c_int, c_int], c_int),
         "sfrt_voxel_render_band": ([vp, vp, ctypes.c_int64, c_int, c_int, vp], c_int),
+        "sfrt_voxel_render_band_aux": ([vp, vp, ctypes.c_int64, P(VoxelAuxPlanes), c_int, c_int, vp],
+                                       c_int),
+        "sfrt_voxel_update_image_aux": ([vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int], c_int),
         "sfrt_voxel_check": ([vp, vp], c_int),
         "sfrt_voxel_set_option": ([vp, c_int, c_int], c_int),
         "sfrt_voxel_get_option": ([vp, c_int, P(c_int)], c_int),
@@ -644,6 +659,48 @@ class VoxelWorld:
         _check(lib().sfrt_voxel_render_band(self._h, ctypes.c_void_p(dev_ptr), int(pitch_bytes),
                                             int(row0), int(rows), ctypes.c_void_p(stream or None)),
                "voxel_render_band")
+
+    def render_band_aux(self, dev_ptr: int, pitch_bytes: int, row0: int, rows: int,
+                        stream: int = 0, depth=None, cell=None, face=None, steps=None) -> None:
+        """render_band plus the per-pixel planes (sfrt_voxel_render_band_aux): depth (float32),
+        cell, face and steps (int32), each None or a (device pointer, pitch in bytes) pair."""
+        planes = VoxelAuxPlanes()
+        for name, plane in (("depth", depth), ("cell", cell), ("face", face), ("steps", steps)):
+            if plane is not None:
+                setattr(planes, name, int(plane[0]))
+                setattr(planes, name + "_pitch_bytes", int(plane[1]))
+        _check(lib().sfrt_voxel_render_band_aux(self._h, ctypes.c_void_p(dev_ptr), int(pitch_bytes),
+                                                ctypes.byref(planes), int(row0), int(rows),
+                                                ctypes.c_void_p(stream or None)),
+               "voxel_render_band_aux")
+
+    def update_image_aux(self, pixels: np.ndarray, depth=None, cell=None, face=None, steps=None,
+                         ystart=0, yadd=1, xstart=0, xadd=1) -> np.ndarray:
+        """update_image plus host planes of width*height elements (sfrt_voxel_update_image_aux):
+        depth float32, cell, face and steps int32, each a contiguous array or None.  A pick of
+        pixel (i, j) is xstart=i, xadd=width, ystart=j, yadd=height."""
+        n = self.width * self.height
+        if pixels.dtype != np.uint8 or pixels.size != n * 4 or not pixels.flags.c_contiguous:
+            raise ValueError("pixels must be a contiguous uint8 array of width*height*4")
+        ptrs = []
+        for plane, (_, dtype) in zip((depth, cell, face, steps), VOXEL_PLANES):
+            if plane is not None and (plane.dtype != dtype or plane.size != n or
+                                      not plane.flags.c_contiguous):
+                raise ValueError(f"a plane must be a contiguous {np.dtype(dtype).name} array of "
+                                 "width*height")
+            ptrs.append(None if plane is None else plane.ctypes.data)
+        _check(lib().sfrt_voxel_update_image_aux(self._h, pixels.ctypes.data, *ptrs, ystart, yadd,
+                                                 xstart, xadd), "voxel_update_image_aux")
+        return pixels
+
+    def render_aux(self):
+        """(rgba (h, w, 4) uint8, depth (h, w) float32, cell, face, steps (h, w) int32) of the
+        whole frame."""
+        w, h = self.width, self.height
+        rgba = np.zeros((h, w, 4), dtype=np.uint8)
+        planes = [np.zeros((h, w), dtype=dt) for _, dt in VOXEL_PLANES]
+        self.update_image_aux(rgba, *planes)
+        return (rgba, *planes)
 
     def check(self, stream: int = 0) -> None:
         _check(lib().sfrt_voxel_check(self._h, ctypes.c_void_p(stream or None)), "voxel_check")
