@@ -1,6 +1,7 @@
 // sfrt_probe.h -- diagnostic hooks of the sphere kernel (sphere_trace.hip), out of its body.
 //
-// trace_tile_window_r<R, LIST, DUMP, P> calls a handful of hooks on a probe object of type P.
+// trace_tile_window_r<R, LIST, DUMP, P> and the march_wave it calls call a handful of hooks on a
+// probe object of type P.
 // The shipped library instantiates it with NoProbe, whose hooks are empty (no state, no
 // instructions: the release ISA is the probe-free kernel's, tools/isa_compare.py).  A build with
 // -DSFRT_EXP=<bits> (sfrt_build_flavour() "diagnostic"; bench.py refuses it) instantiates

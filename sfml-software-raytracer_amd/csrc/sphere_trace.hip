@@ -497,11 +497,13 @@ __device__ __forceinline__ bool pass_body_r(const float (&ss)[R], float s_pass, 
   return any != 0;
 }
 
-// The march (SphereWorld.cpp:359-372), one wave per (8R)x8 tile.  Lane l holds
-// R rays (columns c, c + 8, ...), so the wave-uniform half of a sphere visit --
+// The march (SphereWorld.cpp:359-372) of one wave, shared by the frame kernels (one wave per
+// (8R)x8 tile: trace_tile_window_r) and the ray batches (one wave per 64 rays, R = 1:
+// cast_rays_wave).  Lane l holds R rays (a tile's columns c, c + 8, ...), so the
+// wave-uniform half of a sphere visit --
 // record load, window bits, branch -- is shared by R rays and each lane carries
-// R independent dependency chains.  Per wave: cull the spheres against the tile
-// cone (cull_window).  With n <= 64 (LIST = false, records in the kernel
+// R independent dependency chains.  Per wave: cull the spheres against the cone of
+// the wave's rays (cull_wave).  With n <= 64 (LIST = false, records in the kernel
 // arguments) lane l holds sphere l's march window and bit l of the culling mask
 // is sphere l; with n > 64 (LIST, records in device memory) the culled spheres
 // of every 64-sphere word are compacted, in index order, into lanes 0.. of a
@@ -510,14 +512,230 @@ __device__ __forceinline__ bool pass_body_r(const float (&ss)[R], float s_pass, 
 // A wave with <= kSlots culled spheres holds them in SGPRs and tests each every
 // step; otherwise each step visits, in index order, the culled spheres whose
 // march window meets the along-ray distances [min over marching rays, max over
-// the wave] (the low end refreshed every second step: it only rises).  Then
-// shade and store.
+// the wave] (the low end refreshed every second step: it only rises).  The caller
+// then shades and stores.
 //
 // A stopped ray advances unmasked: it had no passing sphere at its position
 // (its last step visited every sphere that could pass for it) and never moves
 // again, so each later step again has none: L = +0, draw unchanged, tacc + 0 =
 // tacc, and p + d * (+0) = p -- also for p = -0, which a marching wave's ray
 // only reaches through -0 + d * l0 with d of negative sign, so d * (+0) = -0.
+//
+// cull_wave: the cull against `cone`, which must contain every ray of the wave.  It leaves the
+// culled spheres in m (LIST: culled-list entries), their windows in lo / hi and, LIST, entry
+// `lane`'s sphere in cidx -- or clears `culled`: every step then visits every sphere.
+template <bool LIST>
+__device__ __forceinline__ void cull_wave(const FrameRec& f, const SphereRec* sph,
+                                          const Cone& cone, int lane, bool& culled, uint64_t& m,
+                                          float& lo, float& hi, int& cidx) {
+  if (!LIST) {
+    m = cull_window(f, sph, 0, cone, lo, hi);
+  } else {
+    __shared__ float s_list[3][64];  // compaction scratch: lo, hi, index
+    int count = 0;
+    const int nwords = (f.n + 63) >> 6;
+    for (int w = 0; w < nwords; w++) {
+      float wlo, whi;
+      const uint64_t mw = cull_window(f, sph, w * 64, cone, wlo, whi);
+      const int cw = __builtin_popcountll(mw);
+      if (count + cw > 64) {
+        culled = false;
+        break;
+      }
+      if ((mw >> lane) & 1ull) {
+        const int dst = count + (int)__builtin_amdgcn_mbcnt_hi(
+                                    (uint32_t)(mw >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mw, 0u));
+        s_list[0][dst] = wlo;
+        s_list[1][dst] = whi;
+        s_list[2][dst] = __int_as_float(w * 64 + lane);
+      }
+      count += cw;
+    }
+    __syncthreads();  // one wave: orders its own LDS writes before the reads
+    if (culled) {
+      m = count >= 64 ? ~0ull : ((1ull << count) - 1ull);
+      if (lane < count) {
+        lo = s_list[0][lane];
+        hi = s_list[1][lane];
+        cidx = __float_as_int(s_list[2][lane]);
+      }
+    }
+  }
+}
+
+// A wave's rays as the march carries them, R per lane: the last passing sphere (drawSphere), the
+// steps taken (the loop trips of :362; counted only where asked), the unit direction, the
+// position, mv -- the last step length: > 0 while the ray marches, +0 once it stopped (`mv > 0`
+// is one compare per step, where a loop-carried bool would be rematerialised through VGPRs) --
+// and tacc, the along-ray distance marched (the binary32 sum of the steps).
+template <int R>
+struct Rays {
+  int draw[R], iters[R];
+  float dx[R], dy[R], dz[R], px[R], py[R], pz[R], mv[R], tacc[R];
+  int trips = 0;  // output only, set by march_wave: the wave's loop trips, the host's first included
+};
+
+// march_wave: the steps, from the rays' state after the host's first trip (or before any: the
+// batches' own origins) to every ray stopped or kMaxIterations trips, which sets status bit 1.
+// The rays go in and come back by value, so that the loops run on locals of this function: it is
+// optimised on its own before it is inlined, and through references the arrays would stay in
+// memory form until then (more registers in every frame kernel).
+// COUNT: iters counts each ray's steps.  P: the probe hooks (sfrt_probe.h).
+template <int R, bool LIST, bool COUNT, class P>
+__device__ __forceinline__ Rays<R> march_wave(const FrameRec& f, const SphereRec* sph, int lane, P& probe,
+                                              bool culled, uint64_t m, float lo, float hi, int cidx,
+                                              Rays<R> ray) {
+  auto any_marching = [&]() {
+    uint64_t q = 0;
+#pragma unroll
+    for (int r = 0; r < R; r++) q |= __builtin_amdgcn_ballot_w64(ray.mv[r] > 0.0f);
+    return q != 0;
+  };
+  // sphere of culled entry e (wave-uniform)
+  auto entry = [&](uint32_t e) { return LIST ? (uint32_t)__builtin_amdgcn_readlane(cidx, (int)e) : e; };
+  // First set bit of a 64-bit culling mask, 63 for an empty mask (s_ff1 gives -1): entry 63 is
+  // always readable -- a record of the n <= 64 kernel's argument block, or lane 63 of the list
+  // (its sphere, or sphere 63 < n) -- so a lookahead past the last entry loads a record it never uses.
+  static_assert(kInlineSpheres == 64,
+                "entry 63 must be readable: record 63 of the 64-entry argument block, or lane 63 "
+                "of the list kernel's culled list (that kernel runs only for n > kInlineSpheres, "
+                "so lane 63's default sphere 63 exists)");
+  auto first_entry = [](uint64_t x) -> uint32_t {
+    uint32_t e;
+    __asm__("s_ff1_i32_b64 %0, %1" : "=s"(e) : "s"(x));
+    return e & 63u;
+  };
+  auto clear_entry = [](uint64_t x, uint32_t e) -> uint64_t { return x & ~(1ull << e); };  // s_bitset0
+
+  // pos += dir * L (SphereWorld.cpp:371) on every lane (see above)
+  auto advance = [&](const float (&L)[R]) {
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      ray.px[r] = ray.px[r] + ray.dx[r] * L[r];
+      ray.py[r] = ray.py[r] + ray.dy[r] * L[r];
+      ray.pz[r] = ray.pz[r] + ray.dz[r] * L[r];
+      if constexpr (COUNT) ray.iters[r] += ray.mv[r] > 0.0f ? 1 : 0;  // a step of a marching ray
+      ray.mv[r] = L[r];
+      ray.tacc[r] = ray.tacc[r] + L[r];
+    }
+  };
+  auto visit = [&](float cx, float cy, float cz, float rad, float s_pass, int k, float (&L)[R]) {
+    float ss[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) ss[r] = dist2(ray.px[r], ray.py[r], ray.pz[r], cx, cy, cz);
+    probe.visit(pass_body_r<R>(ss, s_pass, rad, k, L, ray.draw));
+  };
+  // Every sphere in index order (no culling: cull off, or past kCullSafeIterations steps).
+  auto visit_all = [&](float (&L)[R]) {
+    for (int k = 0; k < f.n; k++) {
+      const SphereRec s = rec_at(sph, k);
+      visit(s.cx, s.cy, s.cz, s.r, s.s_pass, k, L);
+    }
+  };
+  int trips = 1;
+  // Culled steps run while trips < kCullSafeIterations (the margins' bound, sec. 4 of
+  // DESIGN.md); a wave still marching then continues in the full-list loop below.  Each
+  // loop is single-exit (the guard is its condition) with one body shape: a second exit,
+  // or a full/culled branch inside the step, makes the compiler copy every loop-carried
+  // register (draw, L) between register sets each step.
+  const int cull_end = culled ? kCullSafeIterations : 1;
+  if (kSlots > 0 && culled && __builtin_popcountll(m) <= kSlots) {
+    constexpr int NS = kSlots > 0 ? kSlots : 1;
+    // Few culled spheres: hold them in SGPR slots and test every one each step
+    // (cheaper than maintaining the window).  Empty slots never pass.
+    float scx[NS], scy[NS], scz[NS], sr[NS], ssp[NS];
+    int sk[NS];
+    uint64_t mm = m;
+#pragma unroll
+    for (int q = 0; q < kSlots; q++) {
+      scx[q] = scy[q] = scz[q] = sr[q] = ssp[q] = 0.0f;
+      sk[q] = 0;
+      if (mm) {
+        const int k = entry(__builtin_ctzll(mm));
+        mm &= mm - 1;
+        const SphereRec s = rec_at(sph, k);
+        scx[q] = s.cx; scy[q] = s.cy; scz[q] = s.cz;
+        sr[q] = s.r; ssp[q] = s.s_pass;
+        sk[q] = k;
+      }
+    }
+    for (; any_marching() && trips < cull_end; ++trips) {
+      float L[R];
+      zero_steps<R>(L);
+#pragma unroll
+      for (int q = 0; q < kSlots; q++) visit(scx[q], scy[q], scz[q], sr[q], ssp[q], sk[q], L);
+      advance(L);
+    }
+  } else {
+    probe.window_mode();
+    float tlo = 0.0f;
+    for (; any_marching() && trips < cull_end; ++trips) {
+      float L[R];
+      zero_steps<R>(L);
+      // tacc >= +0: reduce the bit patterns (wave_min_u32 / wave_max_u32)
+      uint32_t th = 0u;  // +0
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        const uint32_t u = __float_as_uint(ray.tacc[r]);
+        th = u > th ? u : th;
+      }
+      if (trips % 2 == 1) {  // the low end, every second step (every 3rd/4th: slower)
+        uint32_t tl = 0x7f800000u;  // +inf
+        if constexpr (R == 1) {  // the one ray's own value: the minimum with +inf costs a v_min_u32
+          tl = ray.mv[0] > 0.0f ? __float_as_uint(ray.tacc[0]) : tl;
+        } else {
+#pragma unroll
+          for (int r = 0; r < R; r++) {
+            const uint32_t u = __float_as_uint(ray.tacc[r]);
+            const uint32_t ua = ray.mv[r] > 0.0f ? u : 0x7f800000u;
+            tl = ua < tl ? ua : tl;
+          }
+        }
+        tlo = __uint_as_float(wave_min_u32(tl));
+      }
+      const float thi = __uint_as_float(wave_max_u32(th));
+      const uint64_t win =
+          m & __builtin_amdgcn_ballot_w64(lo < thi) & __builtin_amdgcn_ballot_w64(hi > tlo);
+      // The visits, in index order, each issuing the next record's scalar loads
+      // before its own arithmetic (the loads' latency hides under the R rays'
+      // distance tests; past the last entry the lookahead loads entry 63's record,
+      // unused).  Scalar work per visit is kept short: the scalar unit is shared by
+      // the CU's four SIMDs (profiles/r3y_salu_mix_check.txt).
+      if (win) {
+        uint32_t e = first_entry(win);
+        uint64_t mm = clear_entry(win, e);
+        uint32_t k = entry(e);
+        const SphereRec s0 = rec_at(sph, k);
+        float cx = s0.cx, cy = s0.cy, cz = s0.cz, rad = s0.r, sp = s0.s_pass;
+        bool more;
+        do {  // the exit test at the bottom: a mid-loop exit made the back edge ~18 scalar ops
+          const uint32_t en = first_entry(mm);
+          const uint32_t kn = entry(en);
+          const SphereRec sn = rec_at(sph, kn);
+          const float ncx = sn.cx, ncy = sn.cy, ncz = sn.cz, nr = sn.r, nsp = sn.s_pass;
+          visit(cx, cy, cz, rad, sp, (int)k, L);
+          more = mm != 0;
+          mm = clear_entry(mm, en);
+          k = kn; cx = ncx; cy = ncy; cz = ncz; rad = nr; sp = nsp;
+        } while (more);
+      }
+      advance(L);
+    }
+  }
+  // Every sphere in index order, every step: culling off, or past kCullSafeIterations.
+  for (; any_marching() && trips < kMaxIterations; ++trips) {
+    float L[R];
+    zero_steps<R>(L);
+    visit_all(L);
+    advance(L);
+  }
+  if (trips >= kMaxIterations && any_marching() && lane == 0) atomicOr(f.status, 1);
+  ray.trips = trips;
+  return ray;
+}
+
+// The frame fill: one wave per (8R)x8 tile sets its rays up, culls against the tile's cone,
+// marches (march_wave), shades and stores.
 // Edge lanes trace a clamped duplicate pixel (never stored) as the duplicate
 // it is, which keeps the tile cone tight.
 // DUMP (sfrt_world_trace_points only): the same march and shading, plus a per-ray
@@ -581,39 +799,28 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   [[maybe_unused]] const int bc = b < b_end ? b : b_end - 1;
   [[maybe_unused]] const int j = CACHED ? 0 : subset_index<SS>(f.ystart, f.yadd, bc);
   const float l0 = f.first_l;
-  int draw[R];
-  int iters[R];  // DUMP and AUX only: loop trips of :362 per ray, the host's first one included
-  float dx[R], dy[R], dz[R], px[R], py[R], pz[R], mv[R], tacc[R];
-  // mv: the ray's last step length (> 0 while it marches, +0 once it stopped);
-  // `mv > 0` is one compare per step, where a loop-carried bool would be
-  // rematerialised through VGPRs.
-  if constexpr (CACHED) ray_cache_load<R>(rc, tile, lane, dx, dy, dz);
+  Rays<R> ray;  // iters: DUMP and AUX only, the host's first trip included
+  if constexpr (CACHED) ray_cache_load<R>(rc, tile, lane, ray.dx, ray.dy, ray.dz);
 #pragma unroll
   for (int r = 0; r < R; r++) {
     if constexpr (!CACHED) {
       const int a = tile_x * R * kTile + r * kTile + (lane & 7);
       const int ac = a < f.sub_w ? a : f.sub_w - 1;
-      primary_dir(f, subset_index<SS>(f.xstart, f.xadd, ac), j, dx[r], dy[r], dz[r]);
+      primary_dir(f, subset_index<SS>(f.xstart, f.xadd, ac), j, ray.dx[r], ray.dy[r], ray.dz[r]);
     }
-    px[r] = f.cam[0] + dx[r] * l0;
-    py[r] = f.cam[1] + dy[r] * l0;
-    pz[r] = f.cam[2] + dz[r] * l0;
-    draw[r] = f.first_draw;
-    iters[r] = 1;
-    mv[r] = l0 > 0.0f ? 1.0f : 0.0f;
-    tacc[r] = l0;  // along-ray distance marched (binary32 sum of the steps)
+    ray.px[r] = f.cam[0] + ray.dx[r] * l0;
+    ray.py[r] = f.cam[1] + ray.dy[r] * l0;
+    ray.pz[r] = f.cam[2] + ray.dz[r] * l0;
+    ray.draw[r] = f.first_draw;
+    ray.iters[r] = 1;
+    ray.mv[r] = l0 > 0.0f ? 1.0f : 0.0f;
+    ray.tacc[r] = l0;  // along-ray distance marched (binary32 sum of the steps)
   }
-  auto any_marching = [&]() {
-    uint64_t q = 0;
-#pragma unroll
-    for (int r = 0; r < R; r++) q |= __builtin_amdgcn_ballot_w64(mv[r] > 0.0f);
-    return q != 0;
-  };
   const bool windowed = f.cull && l0 > 0.0f;
-  bool full = !windowed;  // visit every sphere every step
-  uint64_t m = 0;         // culled spheres (LIST: culled-list entries)
+  bool culled = windowed;  // else every step visits every sphere
+  uint64_t m = 0;          // culled spheres (LIST: culled-list entries)
   float lo = -__builtin_inff(), hi = __builtin_inff();
-  int cidx = lane;        // sphere of culled-list entry `lane`
+  int cidx = lane;         // sphere of culled-list entry `lane`
   if (windowed) {
     Cone cone;
     if constexpr (CACHED) {
@@ -621,178 +828,12 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
       cone.sin_t = trec.sin_t; cone.cos_t = trec.cos_t;
       cone.wide = trec.wide != 0;
     } else {
-      cone = tile_cone<R, SS>(f, tile_x, tile_y, lane, dx, dy, dz);
+      cone = tile_cone<R, SS>(f, tile_x, tile_y, lane, ray.dx, ray.dy, ray.dz);
     }
-    if (!LIST) {
-      m = cull_window(f, sph, 0, cone, lo, hi);
-    } else {
-      __shared__ float s_list[3][64];  // compaction scratch: lo, hi, index
-      int count = 0;
-      const int nwords = (f.n + 63) >> 6;
-      for (int w = 0; w < nwords; w++) {
-        float wlo, whi;
-        const uint64_t mw = cull_window(f, sph, w * 64, cone, wlo, whi);
-        const int cw = __builtin_popcountll(mw);
-        if (count + cw > 64) {
-          full = true;
-          break;
-        }
-        if ((mw >> lane) & 1ull) {
-          const int dst = count + (int)__builtin_amdgcn_mbcnt_hi(
-                                      (uint32_t)(mw >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mw, 0u));
-          s_list[0][dst] = wlo;
-          s_list[1][dst] = whi;
-          s_list[2][dst] = __int_as_float(w * 64 + lane);
-        }
-        count += cw;
-      }
-      __syncthreads();  // one wave: orders its own LDS writes before the reads
-      if (!full) {
-        m = count >= 64 ? ~0ull : ((1ull << count) - 1ull);
-        if (lane < count) {
-          lo = s_list[0][lane];
-          hi = s_list[1][lane];
-          cidx = __float_as_int(s_list[2][lane]);
-        }
-      }
-    }
+    cull_wave<LIST>(f, sph, cone, lane, culled, m, lo, hi, cidx);
   }
-  // sphere of culled entry e (wave-uniform)
-  auto entry = [&](uint32_t e) { return LIST ? (uint32_t)__builtin_amdgcn_readlane(cidx, (int)e) : e; };
-  // First set bit of a 64-bit culling mask, 63 for an empty mask (s_ff1 gives -1): entry 63 is
-  // always readable -- a record of the n <= 64 kernel's argument block, or lane 63 of the list
-  // (its sphere, or sphere 63 < n) -- so a lookahead past the last entry loads a record it never uses.
-  static_assert(kInlineSpheres == 64,
-                "entry 63 must be readable: record 63 of the 64-entry argument block, or lane 63 "
-                "of the list kernel's culled list (that kernel runs only for n > kInlineSpheres, "
-                "so lane 63's default sphere 63 exists; launch_trace checks n >= 64)");
-  auto first_entry = [](uint64_t x) -> uint32_t {
-    uint32_t e;
-    __asm__("s_ff1_i32_b64 %0, %1" : "=s"(e) : "s"(x));
-    return e & 63u;
-  };
-  auto clear_entry = [](uint64_t x, uint32_t e) -> uint64_t { return x & ~(1ull << e); };  // s_bitset0
-
-  // pos += dir * L (SphereWorld.cpp:371) on every lane (see above)
-  auto advance = [&](const float (&L)[R]) {
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      px[r] = px[r] + dx[r] * L[r];
-      py[r] = py[r] + dy[r] * L[r];
-      pz[r] = pz[r] + dz[r] * L[r];
-      if constexpr (DUMP || AUX) iters[r] += mv[r] > 0.0f ? 1 : 0;  // a step of a marching ray
-      mv[r] = L[r];
-      tacc[r] = tacc[r] + L[r];
-    }
-  };
-  auto visit = [&](float cx, float cy, float cz, float rad, float s_pass, int k, float (&L)[R]) {
-    float ss[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) ss[r] = dist2(px[r], py[r], pz[r], cx, cy, cz);
-    probe.visit(pass_body_r<R>(ss, s_pass, rad, k, L, draw));
-  };
-  // Every sphere in index order (no culling: cull off, or past kCullSafeIterations steps).
-  auto visit_all = [&](float (&L)[R]) {
-    for (int k = 0; k < f.n; k++) {
-      const SphereRec s = rec_at(sph, k);
-      visit(s.cx, s.cy, s.cz, s.r, s.s_pass, k, L);
-    }
-  };
-  int trips = 1;
-  // Culled steps run while trips < kCullSafeIterations (the margins' bound, sec. 4 of
-  // DESIGN.md); a wave still marching then continues in the full-list loop below.  Each
-  // loop is single-exit (the guard is its condition) with one body shape: a second exit,
-  // or a full/culled branch inside the step, makes the compiler copy every loop-carried
-  // register (draw, L) between register sets each step.
-  const int cull_end = full ? 1 : kCullSafeIterations;
-  constexpr int kSlotsR = kSlots;
-  if (kSlotsR > 0 && !full && __builtin_popcountll(m) <= kSlotsR) {
-    constexpr int NS = kSlotsR > 0 ? kSlotsR : 1;
-    // Few culled spheres: hold them in SGPR slots and test every one each step
-    // (cheaper than maintaining the window).  Empty slots never pass.
-    float scx[NS], scy[NS], scz[NS], sr[NS], ssp[NS];
-    int sk[NS];
-    uint64_t mm = m;
-#pragma unroll
-    for (int q = 0; q < kSlotsR; q++) {
-      scx[q] = scy[q] = scz[q] = sr[q] = ssp[q] = 0.0f;
-      sk[q] = 0;
-      if (mm) {
-        const int k = entry(__builtin_ctzll(mm));
-        mm &= mm - 1;
-        const SphereRec s = rec_at(sph, k);
-        scx[q] = s.cx; scy[q] = s.cy; scz[q] = s.cz;
-        sr[q] = s.r; ssp[q] = s.s_pass;
-        sk[q] = k;
-      }
-    }
-    for (; any_marching() && trips < cull_end; ++trips) {
-      float L[R];
-      zero_steps<R>(L);
-#pragma unroll
-      for (int q = 0; q < kSlotsR; q++) visit(scx[q], scy[q], scz[q], sr[q], ssp[q], sk[q], L);
-      advance(L);
-    }
-  } else {
-    probe.window_mode();
-    float tlo = 0.0f;
-    for (; any_marching() && trips < cull_end; ++trips) {
-      float L[R];
-      zero_steps<R>(L);
-      // tacc >= +0: reduce the bit patterns (wave_min_u32 / wave_max_u32)
-      uint32_t th = 0u;  // +0
-#pragma unroll
-      for (int r = 0; r < R; r++) {
-        const uint32_t u = __float_as_uint(tacc[r]);
-        th = u > th ? u : th;
-      }
-      if (trips % 2 == 1) {  // the low end, every second step (every 3rd/4th: slower)
-        uint32_t tl = 0x7f800000u;  // +inf
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-          const uint32_t u = __float_as_uint(tacc[r]);
-          const uint32_t ua = mv[r] > 0.0f ? u : 0x7f800000u;
-          tl = ua < tl ? ua : tl;
-        }
-        tlo = __uint_as_float(wave_min_u32(tl));
-      }
-      const float thi = __uint_as_float(wave_max_u32(th));
-      const uint64_t win =
-          m & __builtin_amdgcn_ballot_w64(lo < thi) & __builtin_amdgcn_ballot_w64(hi > tlo);
-      // The visits, in index order, each issuing the next record's scalar loads
-      // before its own arithmetic (the loads' latency hides under the R rays'
-      // distance tests; past the last entry the lookahead loads entry 63's record,
-      // unused).  Scalar work per visit is kept short: the scalar unit is shared by
-      // the CU's four SIMDs (profiles/r3y_salu_mix_check.txt).
-      if (win) {
-        uint32_t e = first_entry(win);
-        uint64_t mm = clear_entry(win, e);
-        uint32_t k = entry(e);
-        const SphereRec s0 = rec_at(sph, k);
-        float cx = s0.cx, cy = s0.cy, cz = s0.cz, rad = s0.r, sp = s0.s_pass;
-        bool more;
-        do {  // the exit test at the bottom: a mid-loop exit made the back edge ~18 scalar ops
-          const uint32_t en = first_entry(mm);
-          const uint32_t kn = entry(en);
-          const SphereRec sn = rec_at(sph, kn);
-          const float ncx = sn.cx, ncy = sn.cy, ncz = sn.cz, nr = sn.r, nsp = sn.s_pass;
-          visit(cx, cy, cz, rad, sp, (int)k, L);
-          more = mm != 0;
-          mm = clear_entry(mm, en);
-          k = kn; cx = ncx; cy = ncy; cz = ncz; rad = nr; sp = nsp;
-        } while (more);
-      }
-      advance(L);
-    }
-  }
-  // Every sphere in index order, every step: culling off, or past kCullSafeIterations.
-  for (; any_marching() && trips < kMaxIterations; ++trips) {
-    float L[R];
-    zero_steps<R>(L);
-    visit_all(L);
-    advance(L);
-  }
-  if (trips >= kMaxIterations && any_marching() && lane == 0) atomicOr(f.status, 1);
+  ray = march_wave<R, LIST, DUMP || AUX>(f, sph, lane, probe, culled, m, lo, hi, cidx, ray);
+  const int trips = ray.trips;
   if (f.tile_cost && lane == 0) store_cost(f.tile_cost, tile, tile_bucket((uint32_t)trips), cls, f.cost_diff);
   // Pixel (a, b) of ray r, recomputed here from a fresh lane id (mbcnt, so that the
   // compiler does not reuse the kernel entry's values): kept from there, the columns sat
@@ -820,8 +861,8 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
 #pragma unroll
     for (int r = 0; r < R; r++)
       if (valid(r))
-        probe.march_only(px_out(r), __float_as_uint(px[r]) ^ __float_as_uint(py[r]) ^
-                                        __float_as_uint(pz[r]) ^ (uint32_t)draw[r]);
+        probe.march_only(px_out(r), __float_as_uint(ray.px[r]) ^ __float_as_uint(ray.py[r]) ^
+                                        __float_as_uint(ray.pz[r]) ^ (uint32_t)ray.draw[r]);
   } else {
     // Shading: the R records gathered first, then the R texel indices, the R texel
     // loads back to back, and the stores.  Edge lanes shade their duplicates too
@@ -829,18 +870,18 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
     SphereRec d[R];
 #pragma unroll
     for (int r = 0; r < R; r++)  // draw < n <= 1024: a 32-bit byte offset from the records' base
-      d[r] = *(const SphereRec*)((const char*)sph + (uint32_t)draw[r] * (uint32_t)sizeof(SphereRec));
+      d[r] = *(const SphereRec*)((const char*)sph + (uint32_t)ray.draw[r] * (uint32_t)sizeof(SphereRec));
     Shading sh[R];
     PixelDump dl[DUMP ? R : 1];
 #pragma unroll
     for (int r = 0; r < R; r++)
-      sh[r] = shade_texel<P, AUX>(f, d[r], px[r], py[r], pz[r], DUMP ? &dl[DUMP ? r : 0] : nullptr);
+      sh[r] = shade_texel<P, AUX>(f, d[r], ray.px[r], ray.py[r], ray.pz[r], DUMP ? &dl[DUMP ? r : 0] : nullptr);
     // AUX: ray r's plane values beside its colour store (plain vector stores)
     [[maybe_unused]] auto aux_store = [&](int r) {
       const int c = col(r) >> SS;
       if (aux.depth) depth_row[c] = sh[r].depth;
-      if (aux.sphere) sphere_row[c] = draw[r];
-      if (aux.steps) steps_row[c] = iters[r];
+      if (aux.sphere) sphere_row[c] = ray.draw[r];
+      if (aux.steps) steps_row[c] = ray.iters[r];
     };
     uint32_t texel[R];
 #pragma unroll
@@ -891,9 +932,9 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
             }
             if (q < dmp.npix && dmp.pix[q] == pid) {
               PixelDump& o = dl[r];
-              o.pos[0] = px[r]; o.pos[1] = py[r]; o.pos[2] = pz[r];
-              o.draw = draw[r];
-              o.iters = iters[r];
+              o.pos[0] = ray.px[r]; o.pos[1] = ray.py[r]; o.pos[2] = ray.pz[r];
+              o.draw = ray.draw[r];
+              o.iters = ray.iters[r];
               o.rgba = rgba;
               dmp.out[q] = o;
             }
@@ -1031,10 +1072,9 @@ __device__ __forceinline__ Cone dirs_cone(float dx, float dy, float dz) {
 }
 
 // One wave per 64 consecutive rays of the batch, ray q = 64 * block + lane; the lanes past the
-// batch's end trace a duplicate of its last ray and store nothing.  The march is
-// trace_tile_window_r's at one ray per lane -- the same visits (pass_body_r), the same three
-// loops, the same culling against a cone (cull_window) -- with what the frame gives a tile
-// replaced by what the batch gives a wave:
+// batch's end trace a duplicate of its last ray and store nothing.  The cull and the march are
+// the frame kernels' at one ray per lane (cull_wave, march_wave), with what the frame gives a
+// tile replaced by what the batch gives a wave:
 //  * the direction is loaded and normalised (ray_dir), not derived from a pixel;
 //  * OWN (origins given): every ray starts at its own origin, so the host's first iteration
 //    (first_l, first_draw: the trip from cam) does not apply -- the first trip runs here, steps
@@ -1069,178 +1109,58 @@ __device__ __forceinline__ void cast_rays_wave(const FrameRec& f, const SphereRe
                   __builtin_fabsf(oz) < __builtin_inff();
   const bool any_invalid = __builtin_amdgcn_ballot_w64(!ok) != 0;
   const float l0 = OWN ? 0.0f : f.first_l;
-  int draw[R], iters[R];
-  float dx[R], dy[R], dz[R], px[R], py[R], pz[R], mv[R], tacc[R];
+  Rays<R> ray;
   // an invalid lane normalises (1, 0, 0): its operands keep the wave on ray_dir's short path
-  ray_dir(ok ? rx : 1.0f, ok ? ry : 0.0f, ok ? rz : 0.0f, ok ? s : 1.0f, dx[0], dy[0], dz[0]);
+  ray_dir(ok ? rx : 1.0f, ok ? ry : 0.0f, ok ? rz : 0.0f, ok ? s : 1.0f, ray.dx[0], ray.dy[0], ray.dz[0]);
   if (ok) {
     // r->pos = cam.pos (:357); shared origin: plus the host's first trip (:371)
-    px[0] = OWN ? ox : ox + dx[0] * l0;
-    py[0] = OWN ? oy : oy + dy[0] * l0;
-    pz[0] = OWN ? oz : oz + dz[0] * l0;
-    mv[0] = OWN ? 1.0f : (l0 > 0.0f ? 1.0f : 0.0f);
+    ray.px[0] = OWN ? ox : ox + ray.dx[0] * l0;
+    ray.py[0] = OWN ? oy : oy + ray.dy[0] * l0;
+    ray.pz[0] = OWN ? oz : oz + ray.dz[0] * l0;
+    ray.mv[0] = OWN ? 1.0f : (l0 > 0.0f ? 1.0f : 0.0f);
   } else {
-    dx[0] = dy[0] = dz[0] = 0.0f;
-    px[0] = py[0] = pz[0] = __builtin_nanf("");
-    mv[0] = 0.0f;
+    ray.dx[0] = ray.dy[0] = ray.dz[0] = 0.0f;
+    ray.px[0] = ray.py[0] = ray.pz[0] = __builtin_nanf("");
+    ray.mv[0] = 0.0f;
   }
-  draw[0] = OWN ? 0 : f.first_draw;
-  iters[0] = OWN ? 0 : 1;
-  tacc[0] = l0;
-  auto any_marching = [&]() { return __builtin_amdgcn_ballot_w64(mv[0] > 0.0f) != 0; };
+  ray.draw[0] = OWN ? 0 : f.first_draw;
+  ray.iters[0] = OWN ? 0 : 1;
+  ray.tacc[0] = l0;
   const bool windowed = !OWN && f.cull && l0 > 0.0f && !any_invalid;
-  bool full = !windowed;  // visit every sphere every step
-  uint64_t m = 0;         // culled spheres (LIST: culled-list entries)
+  bool culled = windowed;  // else every step visits every sphere
+  uint64_t m = 0;          // culled spheres (LIST: culled-list entries)
   float lo = -__builtin_inff(), hi = __builtin_inff();
-  int cidx = lane;        // sphere of culled-list entry `lane`
+  int cidx = lane;         // sphere of culled-list entry `lane`
   if (windowed) {
-    const Cone cone = dirs_cone(dx[0], dy[0], dz[0]);
-    if constexpr (!LIST) {
-      m = cull_window(f, sph, 0, cone, lo, hi);
-    } else {
-      __shared__ float s_list[3][64];  // compaction scratch: lo, hi, index
-      int count = 0;
-      const int nwords = (f.n + 63) >> 6;
-      for (int w = 0; w < nwords; w++) {
-        float wlo, whi;
-        const uint64_t mw = cull_window(f, sph, w * 64, cone, wlo, whi);
-        const int cw = __builtin_popcountll(mw);
-        if (count + cw > 64) {
-          full = true;
-          break;
-        }
-        if ((mw >> lane) & 1ull) {
-          const int dst = count + (int)__builtin_amdgcn_mbcnt_hi(
-                                      (uint32_t)(mw >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mw, 0u));
-          s_list[0][dst] = wlo;
-          s_list[1][dst] = whi;
-          s_list[2][dst] = __int_as_float(w * 64 + lane);
-        }
-        count += cw;
-      }
-      __syncthreads();  // one wave: orders its own LDS writes before the reads
-      if (!full) {
-        m = count >= 64 ? ~0ull : ((1ull << count) - 1ull);
-        if (lane < count) {
-          lo = s_list[0][lane];
-          hi = s_list[1][lane];
-          cidx = __float_as_int(s_list[2][lane]);
-        }
-      }
-    }
+    cull_wave<LIST>(f, sph, dirs_cone(ray.dx[0], ray.dy[0], ray.dz[0]), lane, culled, m, lo, hi, cidx);
   }
-  // the helpers of trace_tile_window_r (entry 63 is readable here for the same reasons)
-  auto entry = [&](uint32_t e) { return LIST ? (uint32_t)__builtin_amdgcn_readlane(cidx, (int)e) : e; };
-  auto first_entry = [](uint64_t x) -> uint32_t {
-    uint32_t e;
-    __asm__("s_ff1_i32_b64 %0, %1" : "=s"(e) : "s"(x));
-    return e & 63u;
-  };
-  auto clear_entry = [](uint64_t x, uint32_t e) -> uint64_t { return x & ~(1ull << e); };
-  auto advance = [&](const float (&L)[R]) {
-    px[0] = px[0] + dx[0] * L[0];
-    py[0] = py[0] + dy[0] * L[0];
-    pz[0] = pz[0] + dz[0] * L[0];
-    iters[0] += mv[0] > 0.0f ? 1 : 0;  // a step of a marching ray
-    mv[0] = L[0];
-    tacc[0] = tacc[0] + L[0];
-  };
-  auto visit = [&](float cx, float cy, float cz, float rad, float s_pass, int k, float (&L)[R]) {
-    float ss[R];
-    ss[0] = dist2(px[0], py[0], pz[0], cx, cy, cz);
-    (void)pass_body_r<R>(ss, s_pass, rad, k, L, draw);
-  };
-  int trips = 1;
-  const int cull_end = full ? 1 : kCullSafeIterations;
-  if (kSlots > 0 && !full && __builtin_popcountll(m) <= kSlots) {
-    constexpr int NS = kSlots > 0 ? kSlots : 1;
-    float scx[NS], scy[NS], scz[NS], sr[NS], ssp[NS];
-    int sk[NS];
-    uint64_t mm = m;
-#pragma unroll
-    for (int j = 0; j < kSlots; j++) {
-      scx[j] = scy[j] = scz[j] = sr[j] = ssp[j] = 0.0f;  // an empty slot never passes
-      sk[j] = 0;
-      if (mm) {
-        const int k = entry(__builtin_ctzll(mm));
-        mm &= mm - 1;
-        const SphereRec r = rec_at(sph, k);
-        scx[j] = r.cx; scy[j] = r.cy; scz[j] = r.cz;
-        sr[j] = r.r; ssp[j] = r.s_pass;
-        sk[j] = k;
-      }
-    }
-    for (; any_marching() && trips < cull_end; ++trips) {
-      float L[R] = {0.0f};
-#pragma unroll
-      for (int j = 0; j < kSlots; j++) visit(scx[j], scy[j], scz[j], sr[j], ssp[j], sk[j], L);
-      advance(L);
-    }
-  } else {
-    float tlo = 0.0f;
-    for (; any_marching() && trips < cull_end; ++trips) {
-      float L[R] = {0.0f};
-      if (trips % 2 == 1)  // the low end, every second step: it only rises
-        tlo = __uint_as_float(wave_min_u32(mv[0] > 0.0f ? __float_as_uint(tacc[0]) : 0x7f800000u));
-      const float thi = __uint_as_float(wave_max_u32(__float_as_uint(tacc[0])));
-      const uint64_t win =
-          m & __builtin_amdgcn_ballot_w64(lo < thi) & __builtin_amdgcn_ballot_w64(hi > tlo);
-      if (win) {  // in index order, the next record's scalar loads issued ahead
-        uint32_t e = first_entry(win);
-        uint64_t mm = clear_entry(win, e);
-        uint32_t k = entry(e);
-        const SphereRec s0 = rec_at(sph, k);
-        float cx = s0.cx, cy = s0.cy, cz = s0.cz, rad = s0.r, sp = s0.s_pass;
-        bool more;
-        do {
-          const uint32_t en = first_entry(mm);
-          const uint32_t kn = entry(en);
-          const SphereRec sn = rec_at(sph, kn);
-          const float ncx = sn.cx, ncy = sn.cy, ncz = sn.cz, nr = sn.r, nsp = sn.s_pass;
-          visit(cx, cy, cz, rad, sp, (int)k, L);
-          more = mm != 0;
-          mm = clear_entry(mm, en);
-          k = kn; cx = ncx; cy = ncy; cz = ncz; rad = nr; sp = nsp;
-        } while (more);
-      }
-      advance(L);
-    }
-  }
-  // Every sphere in index order, every step: own origins, culling off, or past kCullSafeIterations.
-  for (; any_marching() && trips < kMaxIterations; ++trips) {
-    float L[R] = {0.0f};
-    for (int k = 0; k < f.n; k++) {
-      const SphereRec r = rec_at(sph, k);
-      visit(r.cx, r.cy, r.cz, r.r, r.s_pass, k, L);
-    }
-    advance(L);
-  }
-  if (trips >= kMaxIterations && any_marching() && lane == 0) atomicOr(f.status, 1);
+  NoProbe probe;
+  ray = march_wave<R, LIST, true>(f, sph, lane, probe, culled, m, lo, hi, cidx, ray);
   const bool live = q < a.count;
   uint32_t rgba = 0u;
   float depth = 0.0f;
   if constexpr (SHADE) {
     // draw < n <= 1024: a 32-bit byte offset from the records' base
-    const SphereRec d = *(const SphereRec*)((const char*)sph + (uint32_t)draw[0] * (uint32_t)sizeof(SphereRec));
-    const Shading sh = shade_texel<NoProbe, true, true>(f, d, px[0], py[0], pz[0], nullptr, ox, oy, oz);
+    const SphereRec d = *(const SphereRec*)((const char*)sph + (uint32_t)ray.draw[0] * (uint32_t)sizeof(SphereRec));
+    const Shading sh = shade_texel<NoProbe, true, true>(f, d, ray.px[0], ray.py[0], ray.pz[0], nullptr, ox, oy, oz);
     const uint32_t texel = f.tex[sh.tex];
     if (live && ok && sh.outside) atomicOr(f.status, 2);  // the reference would read outside the image
     rgba = shade_rgba(sh.outside ? 0u : texel, sh.brightness);
     depth = sh.depth;
   } else if (a.depth) {  // VLength(r->pos - origin) of :375 alone
-    const float bx = px[0] - ox, by = py[0] - oy, bz = pz[0] - oz;
+    const float bx = ray.px[0] - ox, by = ray.py[0] - oy, bz = ray.pz[0] - oz;
     depth = sqrt_cr((bx * bx + by * by) + bz * bz);
   }
   if (live) {  // an invalid ray: sphere -1, all-zero bytes elsewhere
     if (a.pos) {
       float* const o = a.pos + 3 * q;
-      o[0] = ok ? px[0] : 0.0f;
-      o[1] = ok ? py[0] : 0.0f;
-      o[2] = ok ? pz[0] : 0.0f;
+      o[0] = ok ? ray.px[0] : 0.0f;
+      o[1] = ok ? ray.py[0] : 0.0f;
+      o[2] = ok ? ray.pz[0] : 0.0f;
     }
     if (a.depth) a.depth[q] = ok ? depth : 0.0f;
-    if (a.sphere) a.sphere[q] = ok ? draw[0] : -1;
-    if (a.steps) a.steps[q] = ok ? iters[0] : 0;
+    if (a.sphere) a.sphere[q] = ok ? ray.draw[0] : -1;
+    if (a.steps) a.steps[q] = ok ? ray.iters[0] : 0;
     if constexpr (SHADE) a.rgba[q] = ok ? rgba : 0u;
   }
 }
@@ -1306,85 +1226,23 @@ long long trace_blocks(const FrameRec& f) {
 
 namespace {
 
-// The supersampling kernels by (rays, ss); the launch itself as in launch_trace.
-template <int SS>
-void launch_inline_ss(int rays, dim3 gr, hipStream_t s, const InlineArgs& args) {
-  const dim3 b(64);
+// Pixels per lane R = 1..4 and supersampling SS = 0..2 as compile-time constants: fn gets a
+// std::integral_constant<int, N>.
+template <class F>
+void with_rays(int rays, F fn) {
   switch (rays) {
-    case 1: hipLaunchKernelGGL((k_trace_window_r_ss<1, SS>), gr, b, 0, s, args); break;
-    case 2: hipLaunchKernelGGL((k_trace_window_r_ss<2, SS>), gr, b, 0, s, args); break;
-    case 3: hipLaunchKernelGGL((k_trace_window_r_ss<3, SS>), gr, b, 0, s, args); break;
-    default: hipLaunchKernelGGL((k_trace_window_r_ss<4, SS>), gr, b, 0, s, args); break;
+    case 1: fn(std::integral_constant<int, 1>{}); break;
+    case 2: fn(std::integral_constant<int, 2>{}); break;
+    case 3: fn(std::integral_constant<int, 3>{}); break;
+    default: fn(std::integral_constant<int, 4>{}); break;
   }
 }
-template <int SS>
-void launch_list_ss(int rays, dim3 gr, hipStream_t s, hipEvent_t ev, const FrameRec& g) {
-  const dim3 b(64);
-  switch (rays) {
-    case 1: hipExtLaunchKernelGGL((k_trace_window_list_ss<1, SS>), gr, b, 0, s, nullptr, ev, 0, g); break;
-    case 2: hipExtLaunchKernelGGL((k_trace_window_list_ss<2, SS>), gr, b, 0, s, nullptr, ev, 0, g); break;
-    case 3: hipExtLaunchKernelGGL((k_trace_window_list_ss<3, SS>), gr, b, 0, s, nullptr, ev, 0, g); break;
-    default: hipExtLaunchKernelGGL((k_trace_window_list_ss<4, SS>), gr, b, 0, s, nullptr, ev, 0, g); break;
-  }
-}
-
-// The ray-cache kernels by (rays, ss).
-template <int SS>
-void launch_inline_rc(int rays, dim3 gr, hipStream_t s, const InlineArgs& args, const float* rc,
-                      const TileRec* tr) {
-  const dim3 b(64);
-  switch (rays) {
-    case 1: hipLaunchKernelGGL((k_trace_window_r_rc<1, SS>), gr, b, 0, s, args, rc, tr); break;
-    case 2: hipLaunchKernelGGL((k_trace_window_r_rc<2, SS>), gr, b, 0, s, args, rc, tr); break;
-    case 3: hipLaunchKernelGGL((k_trace_window_r_rc<3, SS>), gr, b, 0, s, args, rc, tr); break;
-    default: hipLaunchKernelGGL((k_trace_window_r_rc<4, SS>), gr, b, 0, s, args, rc, tr); break;
-  }
-}
-template <int SS>
-void launch_list_rc(int rays, dim3 gr, hipStream_t s, hipEvent_t ev, const FrameRec& g,
-                    const float* rc, const TileRec* tr) {
-  const dim3 b(64);
-  switch (rays) {
-    case 1: hipExtLaunchKernelGGL((k_trace_window_list_rc<1, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc,
-                                  tr); break;
-    case 2: hipExtLaunchKernelGGL((k_trace_window_list_rc<2, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc,
-                                  tr); break;
-    case 3: hipExtLaunchKernelGGL((k_trace_window_list_rc<3, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc,
-                                  tr); break;
-    default: hipExtLaunchKernelGGL((k_trace_window_list_rc<4, SS>), gr, b, 0, s, nullptr, ev, 0, g, rc,
-                                  tr); break;
-  }
-}
-// The AUX kernels by (rays, ss).
-template <int SS>
-void launch_inline_aux(int rays, dim3 gr, hipStream_t s, const InlineArgs& args, const AuxArgs& a) {
-  const dim3 b(64);
-  switch (rays) {
-    case 1: hipLaunchKernelGGL((k_trace_window_r_aux<1, SS>), gr, b, 0, s, args, a); break;
-    case 2: hipLaunchKernelGGL((k_trace_window_r_aux<2, SS>), gr, b, 0, s, args, a); break;
-    case 3: hipLaunchKernelGGL((k_trace_window_r_aux<3, SS>), gr, b, 0, s, args, a); break;
-    default: hipLaunchKernelGGL((k_trace_window_r_aux<4, SS>), gr, b, 0, s, args, a); break;
-  }
-}
-template <int SS>
-void launch_list_aux(int rays, dim3 gr, hipStream_t s, hipEvent_t ev, const FrameRec& g,
-                     const AuxArgs& a) {
-  const dim3 b(64);
-  switch (rays) {
-    case 1: hipExtLaunchKernelGGL((k_trace_window_list_aux<1, SS>), gr, b, 0, s, nullptr, ev, 0, g, a); break;
-    case 2: hipExtLaunchKernelGGL((k_trace_window_list_aux<2, SS>), gr, b, 0, s, nullptr, ev, 0, g, a); break;
-    case 3: hipExtLaunchKernelGGL((k_trace_window_list_aux<3, SS>), gr, b, 0, s, nullptr, ev, 0, g, a); break;
-    default: hipExtLaunchKernelGGL((k_trace_window_list_aux<4, SS>), gr, b, 0, s, nullptr, ev, 0, g, a); break;
-  }
-}
-template <int SS>
-void launch_fill(int rays, dim3 gr, hipStream_t s, const FrameRec& g, float* rc, TileRec* tr) {
-  const dim3 b(64);
-  switch (rays) {
-    case 1: hipLaunchKernelGGL((k_ray_fill<1, SS>), gr, b, 0, s, g, rc, tr); break;
-    case 2: hipLaunchKernelGGL((k_ray_fill<2, SS>), gr, b, 0, s, g, rc, tr); break;
-    case 3: hipLaunchKernelGGL((k_ray_fill<3, SS>), gr, b, 0, s, g, rc, tr); break;
-    default: hipLaunchKernelGGL((k_ray_fill<4, SS>), gr, b, 0, s, g, rc, tr); break;
+template <class F>
+void with_ss(int ss, F fn) {
+  switch (ss) {
+    case 0: fn(std::integral_constant<int, 0>{}); break;
+    case 1: fn(std::integral_constant<int, 1>{}); break;
+    default: fn(std::integral_constant<int, 2>{}); break;
   }
 }
 
@@ -1397,11 +1255,14 @@ int launch_ray_fill(const FrameRec& f, float* ray_cache, TileRec* tile_recs, voi
   const int rays = trace_rays(f, true);
   FrameRec g = f;
   g.tiles_x = (f.sub_w + rays * kTile - 1) / (rays * kTile);
-  const dim3 gr((unsigned)tiles);
+  const dim3 gr((unsigned)tiles), b(64);
   hipStream_t s = (hipStream_t)stream;
-  if (f.ss == 0) launch_fill<0>(rays, gr, s, g, ray_cache, tile_recs);
-  else if (f.ss == 1) launch_fill<1>(rays, gr, s, g, ray_cache, tile_recs);
-  else launch_fill<2>(rays, gr, s, g, ray_cache, tile_recs);
+  with_rays(rays, [&](auto r) {
+    with_ss(f.ss, [&](auto ss) {
+      hipLaunchKernelGGL((k_ray_fill<decltype(r)::value, decltype(ss)::value>), gr, b, 0, s, g, ray_cache,
+                         tile_recs);
+    });
+  });
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -1432,68 +1293,38 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
   if (ray_cache && (!ordered || !g.tile_cost || dump)) return -1;
   // the AUX kernels compute their directions and dump nothing; one plane at least
   if (aux && (dump || ray_cache || (!aux->depth && !aux->sphere && !aux->steps))) return -1;
-  if (f.n <= kInlineSpheres) {
-    InlineArgs args;
+  // The list kernels run only for n > 64: their lookahead reads culled-list lane 63, whose
+  // default sphere 63 must exist (the static_assert beside first_entry).
+  const bool list = f.n > kInlineSpheres;
+  InlineArgs args;  // n <= 64: the frame and the records in one argument block (else unused, unset)
+  if (!list) {
     args.f = g;
     for (int k = 0; k < f.n; k++) args.s[k] = host_spheres[k];
-    if (aux) {
-      if (f.ss == 0) launch_inline_aux<0>(rays, gr, s, args, *aux);
-      else if (f.ss == 1) launch_inline_aux<1>(rays, gr, s, args, *aux);
-      else launch_inline_aux<2>(rays, gr, s, args, *aux);
-    } else if (ray_cache) {
-      if (f.ss == 0) launch_inline_rc<0>(rays, gr, s, args, ray_cache, tile_recs);
-      else if (f.ss == 1) launch_inline_rc<1>(rays, gr, s, args, ray_cache, tile_recs);
-      else launch_inline_rc<2>(rays, gr, s, args, ray_cache, tile_recs);
-    } else if (f.ss) {
-      if (f.ss == 1) launch_inline_ss<1>(rays, gr, s, args);
-      else launch_inline_ss<2>(rays, gr, s, args);
-    } else if (dump) {
-      switch (rays) {
-        case 1: hipLaunchKernelGGL(k_trace_window_r_dump<1>, gr, b, 0, s, args, *dump); break;
-        case 2: hipLaunchKernelGGL(k_trace_window_r_dump<2>, gr, b, 0, s, args, *dump); break;
-        case 3: hipLaunchKernelGGL(k_trace_window_r_dump<3>, gr, b, 0, s, args, *dump); break;
-        default: hipLaunchKernelGGL(k_trace_window_r_dump<4>, gr, b, 0, s, args, *dump); break;
-      }
-    } else {
-      switch (rays) {
-        case 1: hipLaunchKernelGGL(k_trace_window_r<1>, gr, b, 0, s, args); break;
-        case 2: hipLaunchKernelGGL(k_trace_window_r<2>, gr, b, 0, s, args); break;
-        case 3: hipLaunchKernelGGL(k_trace_window_r<3>, gr, b, 0, s, args); break;
-        default: hipLaunchKernelGGL(k_trace_window_r<4>, gr, b, 0, s, args); break;
-      }
-    }
-  } else if (f.n < 64) {
-    return -1;  // the list kernel's lookahead reads culled-list lane 63 (a sphere index < n)
-  } else if (aux) {
-    const hipEvent_t ev = (hipEvent_t)done_event;
-    if (f.ss == 0) launch_list_aux<0>(rays, gr, s, ev, g, *aux);
-    else if (f.ss == 1) launch_list_aux<1>(rays, gr, s, ev, g, *aux);
-    else launch_list_aux<2>(rays, gr, s, ev, g, *aux);
-  } else if (ray_cache) {
-    const hipEvent_t ev = (hipEvent_t)done_event;
-    if (f.ss == 0) launch_list_rc<0>(rays, gr, s, ev, g, ray_cache, tile_recs);
-    else if (f.ss == 1) launch_list_rc<1>(rays, gr, s, ev, g, ray_cache, tile_recs);
-    else launch_list_rc<2>(rays, gr, s, ev, g, ray_cache, tile_recs);
-  } else if (f.ss) {
-    const hipEvent_t ev = (hipEvent_t)done_event;
-    if (f.ss == 1) launch_list_ss<1>(rays, gr, s, ev, g);
-    else launch_list_ss<2>(rays, gr, s, ev, g);
-  } else if (dump) {
-    switch (rays) {
-      case 1: hipLaunchKernelGGL(k_trace_window_list_dump<1>, gr, b, 0, s, g, *dump); break;
-      case 2: hipLaunchKernelGGL(k_trace_window_list_dump<2>, gr, b, 0, s, g, *dump); break;
-      case 3: hipLaunchKernelGGL(k_trace_window_list_dump<3>, gr, b, 0, s, g, *dump); break;
-      default: hipLaunchKernelGGL(k_trace_window_list_dump<4>, gr, b, 0, s, g, *dump); break;
-    }
-  } else {
-    const hipEvent_t ev = (hipEvent_t)done_event;  // the record ring's slot (sfrt_world.cpp)
-    switch (rays) {
-      case 1: hipExtLaunchKernelGGL(k_trace_window_list<1>, gr, b, 0, s, nullptr, ev, 0, g); break;
-      case 2: hipExtLaunchKernelGGL(k_trace_window_list<2>, gr, b, 0, s, nullptr, ev, 0, g); break;
-      case 3: hipExtLaunchKernelGGL(k_trace_window_list<3>, gr, b, 0, s, nullptr, ev, 0, g); break;
-      default: hipExtLaunchKernelGGL(k_trace_window_list<4>, gr, b, 0, s, nullptr, ev, 0, g); break;
-    }
   }
+  const hipEvent_t ev = (hipEvent_t)done_event;  // the record ring's slot (sfrt_world.cpp)
+  // A launch of each column: the argument block, plainly; the frame record with ev as the stop
+  // event; and the list dump kernel's, which records no event.
+  auto inl = [&](auto k, const auto&... a) { hipLaunchKernelGGL(k, gr, b, 0, s, args, a...); };
+  auto lst = [&](auto k, const auto&... a) { hipExtLaunchKernelGGL(k, gr, b, 0, s, nullptr, ev, 0, g, a...); };
+  auto lst_no_event = [&](auto k, const auto&... a) { hipLaunchKernelGGL(k, gr, b, 0, s, g, a...); };
+  with_rays(rays, [&](auto r) {
+    with_ss(f.ss, [&](auto ss) {
+      constexpr int R = decltype(r)::value, SS = decltype(ss)::value;
+      // mode                n <= 64                                                 n > 64
+      if (aux) {
+        list ? lst(k_trace_window_list_aux<R, SS>, *aux) : inl(k_trace_window_r_aux<R, SS>, *aux);
+      } else if (ray_cache) {
+        list ? lst(k_trace_window_list_rc<R, SS>, ray_cache, tile_recs)
+             : inl(k_trace_window_r_rc<R, SS>, ray_cache, tile_recs);
+      } else if constexpr (SS > 0) {
+        list ? lst(k_trace_window_list_ss<R, SS>) : inl(k_trace_window_r_ss<R, SS>);
+      } else if (dump) {
+        list ? lst_no_event(k_trace_window_list_dump<R>, *dump) : inl(k_trace_window_r_dump<R>, *dump);
+      } else {
+        list ? lst(k_trace_window_list<R>) : inl(k_trace_window_r<R>);
+      }
+    });
+  });
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -379,6 +379,60 @@ def test_supersampled_planes_are_the_first_sample(built, name, s):
             _assert_planes(got, want, f"ordered frame {k}")
 
 
+SMALL_W, SMALL_H = 40, 24  # partial tiles at every tile width; both factors divide both sides
+
+
+def _small_scene(n):
+    """n spheres: 64 travel in the kernel arguments, 65 are the fewest that take the list kernels."""
+    spheres = scenes.sort_spheres(scenes.lcg_spheres(count=n - 1, seed=31 + n))
+    return scenes.Scene(f"many{n}", spheres).posed(1.1, -0.2)
+
+
+@functools.lru_cache(maxsize=None)
+def _small_reference(n, s):
+    """(colour (H, W, 4), planes) of the 40x24 frame at factor s, from the oracle alone: its
+    s*W x s*H frame box-filtered, and the planes of each group's first sample (planes_reference's
+    construction, the depth pinned to the oracle's brightness in the same way)."""
+    import oracle
+    sc = _small_scene(n)
+    o = oracle.Oracle.from_scene(sc, s * SMALL_W, s * SMALL_H, *_floor())
+    big = o.render(host_threads())
+    sums = big.reshape(SMALL_H, s, SMALL_W, s, 4).astype(np.uint32).sum(axis=(1, 3))
+    colour = ((sums + s * s // 2) >> {2: 2, 4: 4}[s]).astype(np.uint8)
+    dumps = [[o.dump(s * i, s * j) for i in range(SMALL_W)] for j in range(SMALL_H)]
+    pos = np.array([[d["pos"] for d in row] for row in dumps], dtype=F)
+    bright = np.array([[d["brightness"] for d in row] for row in dumps], dtype=F)
+    depth = _depth_of(pos, np.asarray(sc.cam_pos, dtype=F))
+    assert depth.dtype == F
+    assert np.array_equal((F(3.0) / np.maximum(depth, F(3.0))).view(np.uint32), bright.view(np.uint32))
+    planes = {"depth": depth,
+              "sphere": np.array([[d["draw"] for d in row] for row in dumps], dtype=np.int32),
+              "steps": np.array([[d["iters"] for d in row] for row in dumps], dtype=np.int32)}
+    assert len(np.unique(planes["sphere"])) > 1 and planes["steps"].max() > planes["steps"].min()
+    for a in (colour, *planes.values()):
+        a.setflags(write=False)
+    return colour, planes
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rays", [1, 3, 4])
+@pytest.mark.parametrize("s", [2, 4])
+@pytest.mark.parametrize("n", [64, 65])
+def test_supersampled_planes_at_every_other_tile_shape(built, n, s, rays):
+    """The supersampled aux kernels at R = 1, 3 and 4, for n <= 64 and above: the tests above
+    reach them only at the kernel table's own choice, R = 2."""
+    import sfrt
+    colour, want = _small_reference(n, s)
+    with sfrt.World(0) as w:
+        w.load_texture(*_floor())
+        w.set_scene(_small_scene(n), SMALL_W, SMALL_H)
+        w.set_option(sfrt.SFRT_OPT_SUPERSAMPLE, s)
+        w.set_option(sfrt.SFRT_OPT_RAYS_PER_LANE, rays)
+        rgba, depth, sphere, steps = w.render_aux()
+    assert np.array_equal(rgba, colour)
+    _assert_planes({"depth": depth, "sphere": sphere, "steps": steps}, want, f"n={n} s={s} R={rays}")
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["default10", "lcg256"])
 def test_ray_cache_left_alone(built, name):

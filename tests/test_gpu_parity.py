@@ -256,6 +256,22 @@ def test_float_intermediates_list_kernel(world, floor, rays):
     assert same == 600
 
 
+@pytest.mark.parametrize("rays", [1, 3])
+def test_float_intermediates_list_kernel_other_tile_shapes(world, floor, rays):
+    """k_trace_window_list_dump<R> at the two tile shapes the test above leaves out, on a 40x24
+    frame (partial tiles at either width) of 65 spheres, the fewest that take the list kernel."""
+    import sfrt
+    spheres = scenes.sort_spheres(scenes.lcg_spheres(count=64, seed=96))
+    scene = scenes.Scene("many65", spheres).posed(1.1, -0.2)
+    world.set_scene(scene, 40, 24)
+    world.set_option(sfrt.SFRT_OPT_RAYS_PER_LANE, rays)
+    try:
+        same = _check_dumps(world, floor, scene, 40, 24, 200, 77 + rays, ("many65", rays))
+    finally:
+        world.set_option(sfrt.SFRT_OPT_RAYS_PER_LANE, 0)
+    assert same == 200
+
+
 def test_trace_points_frame_equals_render(world, floor):
     """The DUMP instantiation writes the same frame as the shipped kernel: the rgba of every
     pixel of a small frame out of trace_points equals render()'s bytes."""

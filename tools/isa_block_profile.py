@@ -568,61 +568,66 @@ def regions_glsl(blocks):
 
 def regions_sphere(blocks, kind="sphere"):
     """k_trace_window_r<4> (and its cached twin, kind = "sphere_rc"): by helper function on the
-    inline chain, else by the line of trace_tile_window_r (or of one of its lambdas) the
-    instruction belongs to."""
+    inline chain, else by the line of march_wave or of trace_tile_window_r (or of one of their
+    lambdas) the instruction belongs to."""
     A = {k: src_anchor(kind, v) for k, v in {
-        "fn_first": "const int lane = threadIdx.x & 63;\n  P probe;",
-        "windowed": "const bool windowed = f.cull && l0 > 0.0f;",
-        "entry_lambda": "auto entry = [&](uint32_t e)",
+        "march_first": "auto any_marching = [&]() {",
         "advance_first": "auto advance = [&](const float (&L)[R]) {",
         "visit_first": "auto visit = [&](float cx, float cy, float cz",
         "visit_all_first": "auto visit_all = [&](float (&L)[R]) {",
-        "slots_first": "if (kSlotsR > 0 && !full && __builtin_popcountll(m) <= kSlotsR) {",
-        "slots_loop": "for (q = 0; q < kSlotsR; q++) visit(",
+        "visit_all_last": "visit(s.cx, s.cy, s.cz, s.r, s.s_pass, k, L);\n    }\n  };",
+        "slots_first": "if (kSlots > 0 && culled && __builtin_popcountll(m) <= kSlots) {",
+        "slots_setup_last": "sk[q] = k;\n      }\n    }",
         "window_first": "uint32_t th = 0u;  // +0",
         "window_last": "m & __builtin_amdgcn_ballot_w64(lo < thi) & __builtin_amdgcn_ballot_w64(hi > tlo);",
         "visits_first": "if (win) {",
         "visits_last": "} while (more);",
         "full_loop": "for (; any_marching() && trips < kMaxIterations; ++trips) {",
-        "tail_first": "if (trips >= kMaxIterations && any_marching() && lane == 0)",
+        "march_last": "if (trips >= kMaxIterations && any_marching() && lane == 0) atomicOr(f.status, 1);",
+        "fn_first": "const int lane = threadIdx.x & 63;\n  P probe;",
+        "windowed": "const bool windowed = f.cull && l0 > 0.0f;",
+        "march_call": "ray = march_wave<R, LIST, DUMP || AUX>(",
         "fn_last": "probe.tile_end(px_out(0), lane_s, valid(0), trips, slot, m);",
-    }.items() if k != "slots_loop"}
+    }.items()}
     helpers = [("sort_tiles", "sorter"), ("shade_texel", "shade"), ("shade_rgba", "shade"),
                ("primary_dir", "ray_setup"), ("ray_cache_load", "ray_setup"),
                ("tile_cone", "cull"), ("tile_rec_at", "cull"), ("cull_window", "cull"),
+               ("cull_wave", "cull"),
                ("dist2", "visit_test"), ("pass_body_r", "pass_body"), ("zero_steps", "step_control")]
+
+    def march_region(line):
+        """A line of march_wave (or of one of its lambdas)."""
+        if A["advance_first"] <= line < A["visit_first"]:
+            return "advance"
+        if A["visit_all_first"] <= line <= A["visit_all_last"]:
+            return "full_list"
+        if A["window_first"] <= line <= A["window_last"]:
+            return "window_upkeep"
+        if A["visits_first"] <= line <= A["visits_last"]:
+            return "visit_loop"
+        if A["slots_first"] <= line <= A["slots_setup_last"]:
+            return "slots_setup"
+        if A["full_loop"] <= line < A["march_last"]:
+            return "full_list"
+        return "step_control"  # the loops' guards and steps, the status bit
 
     def region(b, ch):
         for fn, f, line in ch:
             for h, r in helpers:
                 if fn.startswith(h):
                     return r
-        line = None
-        for fn, f, ln in ch:
-            if f == "sphere_trace.hip" and A["fn_first"] <= ln <= A["fn_last"]:
-                line = ln
-                break
-        if line is None:
-            return None  # no line (compiler-made): the region of its neighbours
-        if line < A["windowed"]:
-            return "ray_setup"
-        if line < A["entry_lambda"]:
-            return "cull"
-        if A["advance_first"] <= line < A["visit_first"]:
-            return "advance"
-        if A["visit_all_first"] <= line < A["visit_all_first"] + 6:
-            return "full_list"
-        if A["window_first"] <= line <= A["window_last"]:
-            return "window_upkeep"
-        if A["visits_first"] <= line <= A["visits_last"]:
-            return "visit_loop"
-        if A["slots_first"] <= line < A["window_first"] - 4 and line < A["slots_first"] + 20:
-            return "slots_setup" if line < A["slots_first"] + 20 - 2 else "step_control"
-        if line >= A["tail_first"]:
-            return "shade"
-        if A["full_loop"] <= line < A["tail_first"]:
-            return "full_list"
-        return "step_control"
+        for fn, f, line in ch:  # innermost first
+            if f != "sphere_trace.hip":
+                continue
+            if A["march_first"] <= line <= A["march_last"] + 2:
+                return march_region(line)
+            if A["fn_first"] <= line <= A["fn_last"]:
+                if line < A["windowed"]:
+                    return "ray_setup"
+                if line < A["march_call"]:
+                    return "cull"
+                return "step_control" if line <= A["march_call"] + 1 else "shade"
+        return None  # no line (compiler-made): the region of its neighbours
     return region
 
 
