@@ -563,6 +563,92 @@ SFRT_API int sfrt_voxel_render_band_aux(sfrt_voxel* v, void* dev_pixels, int64_t
 SFRT_API int sfrt_voxel_update_image_aux(sfrt_voxel* v, uint8_t* pixels, float* depth, int32_t* cell,
                                          int32_t* face, int32_t* steps, int ystart, int yadd,
                                          int xstart, int xadd);
+
+/* ---- batched ray queries: World::Raycast (World.cpp:302-453) for caller-supplied rays ----
+ * sfrt_voxel_cast_rays[_device] runs Raycast for ray q of a batch.  Line numbers are World.cpp's.
+ * `dirs` holds 3 floats per ray, used as r->dir VERBATIM: the voxel Raycast never normalises, and
+ * `depth` is the reference's own ray parameter along that direction, as the depth plane above
+ * documents it.  `yscales` holds one float per ray, r->yscale; NULL means 1.0f for every ray.
+ * origins == NULL is the reference: pos = cam.pos (:305), snapshotted at the call, and the
+ * billboard loop of :353-378 runs, with atan2f(dir.z, dir.x) of VAngleXZ evaluated per ray by
+ * sfrt_math::atan2f.
+ * origins != NULL, 3 floats per ray: cam.pos of :305 is replaced by the ray's origin, and the
+ * billboard list is NOT VISITED, as if `dyn` were empty: distToCamera and
+ * VNormalizeXZ(d->pos - cam.pos) are camera quantities and have no meaning for another origin.
+ * Blocks, lights and shadow rays are unchanged: the hit block is shaded by :386-450 as for a
+ * pixel, shadowDistance compared with the ray's own tryDist.
+ * Outputs.  depth, cell, face and steps are exactly as the planes of sfrt_voxel_render_band_aux
+ * define them (face never 4 with origins given).  pos depends on how the ray ended: block hit,
+ * pos as assigned at :381, before :396-408 move it off the wall; billboard, pos after :357 for
+ * the billboard that returned; nothing, pos at loop exit.  rgba is r->c.  rgba == NULL skips the
+ * shading of a block hit entirely -- no block texel, no light loop, no shadow rays: the picking
+ * path does not pay for shading.  A billboard's alpha test still reads its texel then, so the
+ * texel status bit can still be set.
+ * A direction component of 0 is valid (the reference's own axis-parallel column has one) and
+ * marches as the frame kernels march it.  Arithmetic is binary32, round to nearest, no
+ * contraction, with correctly rounded / and sqrt, and the float -> int conversions of the
+ * reference's x86-64 build, as in the frame fill.
+ * An invalid ray is one with any non-finite component of dir, origin or yscale.  It is decided
+ * per ray before the march and never marched.  It gets face = 0, cell = -1, steps = 0, and every
+ * other requested output is all-zero bytes.  It changes no other ray's result and sets no status
+ * bit.
+ * Return codes.  count == 0 returns SFRT_OK and writes nothing.  SFRT_E_INVALID, with nothing
+ * queued or written, for: a NULL world; NULL dirs; a NULL output record; count < 0 or count >
+ * 2^31-1; all six outputs NULL; a non-NULL pointer that is not 4-byte aligned.  SFRT_E_EMPTY when
+ * there are no blocks, as the frame calls give it.  Overlapping buffers are the caller's
+ * responsibility.
+ * Status.  The only status bit is the frame fill's texel bit.  The device call is asynchronous
+ * on hip_stream and leaves it to sfrt_voxel_check(v, hip_stream).  The host call returns the
+ * code; on SFRT_E_TEXEL it writes no output, as sfrt_voxel_update_image_aux.
+ * Shared state.  A batch counts as a frame call for the deferred grid upload of
+ * sfrt_voxel_set_blocks and for the staged dynamics, lights and texture tables.  Calls serialise
+ * on the world's mutex; scene, camera and view distances are snapshotted at the call.
+ * SFRT_OPT_SUPERSAMPLE and SFRT_OPT_TILE_ORDER are ignored: the call joins no tile-order chain
+ * and leaves the recorded tile costs alone.  The host calls stage through one device buffer and
+ * one pinned buffer per world, grown on demand. */
+typedef struct {          /* every member: one element per ray, or NULL; not all NULL */
+  float*   pos;           /* 3 floats per ray, packed x,y,z (12 B per ray) */
+  float*   depth;
+  int32_t* cell;          /* -1: nothing hit, or an invalid ray */
+  int32_t* face;          /* 0: nothing hit, or an invalid ray */
+  int32_t* steps;         /* 0: invalid ray */
+  uint8_t* rgba;          /* 4 bytes per ray: r->c */
+} sfrt_voxel_ray_hits;
+/* device memory on the world's device, asynchronous on hip_stream; status via sfrt_voxel_check */
+SFRT_API int sfrt_voxel_cast_rays_device(sfrt_voxel* v, const float* dev_dirs, const float* dev_yscales,
+                                         const float* dev_origins, int64_t count,
+                                         const sfrt_voxel_ray_hits* dev_out, void* hip_stream);
+/* host memory, synchronous */
+SFRT_API int sfrt_voxel_cast_rays(sfrt_voxel* v, const float* dirs, const float* yscales,
+                                  const float* origins, int64_t count, const sfrt_voxel_ray_hits* out);
+
+/* ---- batched occlusion queries: World::LRaycast (World.cpp:455-491) for caller-supplied rays ----
+ * Ray q is LRaycast with r->pos = origins[3q..], r->dir = dirs[3q..] verbatim (the reference
+ * passes a normalised one) and r->maxDist = max_dists[q].
+ *   free  (int32_t): 1 where LRaycast returns true; 0 where it returns false -- a block, or the
+ *                    trip limit max(maxDist*2, 20) of :473 before maxDist; -1 for an invalid ray.
+ *   steps (int32_t): the number of times the body of the `for` at :475 was entered, the trip that
+ *                    returned false included; 0 for an invalid ray.
+ * Either output may be NULL, but not both.  A negative or zero max_dist is valid: the loop never
+ * runs and the answer is 1, as in the reference.  A zero direction component is valid.
+ * A ray is invalid when any component of origin or dir, or max_dist itself, is not finite, or
+ * when max_dist > SFRT_VOXEL_MAX_SHADOW_DIST: without a bound one caller value of 1e9 would keep
+ * a wave busy for 2e9 trips; 4096 covers viewDistance values far beyond the reference's 24.  An
+ * invalid ray is never marched and changes no other ray's result.
+ * No billboards, no textures, no status bits.  count == 0 returns SFRT_OK and writes nothing;
+ * SFRT_E_INVALID, with nothing queued or written, for a NULL world, NULL origins, dirs or
+ * max_dists, count < 0 or count > 2^31-1, both outputs NULL, or a non-NULL pointer that is not
+ * 4-byte aligned; SFRT_E_EMPTY when there are no blocks.  Shared state, snapshots, the mutex and
+ * the host call's staging are sfrt_voxel_cast_rays'. */
+#define SFRT_VOXEL_MAX_SHADOW_DIST 4096.0f
+SFRT_API int sfrt_voxel_cast_shadow_rays_device(sfrt_voxel* v, const float* dev_origins,
+                                                const float* dev_dirs, const float* dev_max_dists,
+                                                int64_t count, int32_t* dev_free, int32_t* dev_steps,
+                                                void* hip_stream);
+SFRT_API int sfrt_voxel_cast_shadow_rays(sfrt_voxel* v, const float* origins, const float* dirs,
+                                         const float* max_dists, int64_t count, int32_t* free_,
+                                         int32_t* steps);
+
 /* SFRT_OPT_TILE_ORDER as for sfrt_world, but off (0) by default here: render_band with 1
  * dispatches 8x8 tiles longest-first by the DDA + shadow steps of two frames back (same
  * bytes; measured 1-6% slower on the voxel worlds).

@@ -102,9 +102,13 @@ inline sfrt_camera to_c(const Camera& c) {
 
 // struct Ray (SphereWorld.h): what SphereWorld::Raycast reads (dir) and writes (pos, c);
 // c is the sf::Color's r, g, b, a.
+// The voxel World's Ray (World.h:49-56) has two more members its Raycast / LRaycast read:
+// yscale (the billboards' height scale) and maxDist (LRaycast's length), with its defaults.
 struct Ray {
   Vector3f pos, dir;
   uint8_t c[4] = {0, 0, 0, 0};
+  float maxDist = 100.0f;
+  float yscale = 1.0f;
 };
 
 // ---------------------------------------------------------------------------
@@ -410,6 +414,63 @@ class VoxelWorld {
     push_state();
     check(sfrt_voxel_render_band_aux(v_, dev_pixels, pitch_bytes, &aux, row0, rows, hip_stream),
           "render_band_aux");
+  }
+  // World::Raycast (World.cpp:302-453), the reference's own signature: r->dir verbatim (never
+  // normalised), r->yscale, from cam.pos with the billboards; fills r->c and r->pos (where the
+  // ray ended: sfrt.h sfrt_voxel_ray_hits).  One ray per call, synchronous; batches, own
+  // origins and the picking outputs (cell, face, depth) go through CastRays.
+  void Raycast(Ray* r) {
+    push_state();
+    const float dir[3] = {r->dir.x, r->dir.y, r->dir.z};
+    float pos[3] = {0, 0, 0};
+    sfrt_voxel_ray_hits out{};
+    out.pos = pos;
+    out.rgba = r->c;
+    check(sfrt_voxel_cast_rays(v_, dir, &r->yscale, nullptr, 1, &out), "Raycast");
+    r->pos = Vector3f{pos[0], pos[1], pos[2]};
+  }
+  // World::LRaycast (World.cpp:455-491): reads r->pos, r->dir (verbatim; the reference passes a
+  // normalised one) and r->maxDist; true when the segment is free.  A non-finite ray or a
+  // maxDist above SFRT_VOXEL_MAX_SHADOW_DIST throws (SFRT_E_INVALID).
+  bool LRaycast(Ray* r) {
+    push_state();
+    const float org[3] = {r->pos.x, r->pos.y, r->pos.z};
+    const float dir[3] = {r->dir.x, r->dir.y, r->dir.z};
+    int32_t free_ = 0;
+    check(sfrt_voxel_cast_shadow_rays(v_, org, dir, &r->maxDist, 1, &free_, nullptr), "LRaycast");
+    if (free_ < 0) check(SFRT_E_INVALID, "LRaycast");
+    return free_ == 1;
+  }
+  // `count` rays at once (sfrt.h sfrt_voxel_cast_rays): dirs 3 floats per ray, yscales one (null:
+  // 1.0f), origins 3 (null: every ray from cam.pos, with the billboards; given: no billboards);
+  // any member of out may be null, not all.  rgba null skips the shading: the picking path.
+  void CastRays(const float* dirs, const float* yscales, const float* origins, int64_t count,
+                const sfrt_voxel_ray_hits& out) {
+    push_state();
+    check(sfrt_voxel_cast_rays(v_, dirs, yscales, origins, count, &out), "CastRays");
+  }
+  // The same on device memory, asynchronous on hip_stream (status through Check).
+  void CastRaysDevice(const float* dev_dirs, const float* dev_yscales, const float* dev_origins,
+                      int64_t count, const sfrt_voxel_ray_hits& dev_out, void* hip_stream) {
+    push_state();
+    check(sfrt_voxel_cast_rays_device(v_, dev_dirs, dev_yscales, dev_origins, count, &dev_out,
+                                      hip_stream),
+          "CastRaysDevice");
+  }
+  // World::LRaycast for `count` segments (sfrt.h sfrt_voxel_cast_shadow_rays): line of sight and
+  // projectile tests.  free_: 1 free, 0 blocked, -1 invalid ray; steps: trips; either may be null.
+  void CastShadowRays(const float* origins, const float* dirs, const float* max_dists, int64_t count,
+                      int32_t* free_, int32_t* steps) {
+    push_state();
+    check(sfrt_voxel_cast_shadow_rays(v_, origins, dirs, max_dists, count, free_, steps),
+          "CastShadowRays");
+  }
+  void CastShadowRaysDevice(const float* dev_origins, const float* dev_dirs, const float* dev_max_dists,
+                            int64_t count, int32_t* dev_free, int32_t* dev_steps, void* hip_stream) {
+    push_state();
+    check(sfrt_voxel_cast_shadow_rays_device(v_, dev_origins, dev_dirs, dev_max_dists, count, dev_free,
+                                             dev_steps, hip_stream),
+          "CastShadowRaysDevice");
   }
   void Check(void* hip_stream = nullptr) { check(sfrt_voxel_check(v_, hip_stream), "check"); }
   // SFRT_OPT_TILE_ORDER, SFRT_OPT_SUPERSAMPLE (sfrt.h): the latter, 2 or 4, box-filters S x S

@@ -159,6 +159,12 @@ struct sfrt_voxel {
   size_t d_aux_px[4] = {};
   uint32_t* h_aux[4] = {};
   size_t h_aux_px[4] = {};
+  // Staging of sfrt_voxel_cast_rays and sfrt_voxel_cast_shadow_rays (the host calls): one device
+  // and one pinned buffer holding a batch's inputs and its requested outputs, grown on demand
+  uint8_t* d_rays = nullptr;
+  size_t d_rays_bytes = 0;
+  uint8_t* h_rays = nullptr;
+  size_t h_rays_bytes = 0;
   int tile_order_on = 0;    // SFRT_OPT_TILE_ORDER: off by default here (slower)
   // SFRT_OPT_SUPERSAMPLE: log2 of the factor S (0, 1, 2).  S > 1: the frame's samples are the
   // pixels of World::UpdateImage at S * width x S * height (prepare() builds the tables for that
@@ -198,6 +204,8 @@ struct sfrt_voxel {
       (void)hipFree(d_aux[q]);
       (void)hipHostFree(h_aux[q]);
     }
+    (void)hipFree(d_rays);
+    (void)hipHostFree(h_rays);
     if (stream) (void)hipStreamDestroy(stream);
   }
 
@@ -706,6 +714,208 @@ int sfrt_voxel_render_band(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes,
 int sfrt_voxel_render_band_aux(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes,
                                const sfrt_voxel_aux_planes* aux, int row0, int rows, void* hip_stream) {
   return render_band_body(v, dev_pixels, pitch_bytes, aux, true, row0, rows, hip_stream);
+}
+
+// ---- batched ray queries (include/sfrt.h) ----
+namespace {
+
+static_assert(SFRT_VOXEL_MAX_SHADOW_DIST == sfrt::kVoxMaxShadowDist, "one bound, two headers");
+
+bool aligned4(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if ((uintptr_t)p & 3u) return false;
+  return true;
+}
+
+// The argument checks the host and the device call share; the world's own come with its mutex held.
+int cast_rays_args(const sfrt_voxel* v, const float* dirs, const float* yscales, const float* origins,
+                   int64_t count, const sfrt_voxel_ray_hits* out) {
+  if (!v || !dirs || !out || count < 0 || count > 0x7fffffffLL) return SFRT_E_INVALID;
+  if (!out->pos && !out->depth && !out->cell && !out->face && !out->steps && !out->rgba)
+    return SFRT_E_INVALID;
+  if (!aligned4({dirs, yscales, origins, out->pos, out->depth, out->cell, out->face, out->steps, out->rgba}))
+    return SFRT_E_INVALID;
+  return SFRT_OK;
+}
+int shadow_rays_args(const sfrt_voxel* v, const float* origins, const float* dirs,
+                     const float* max_dists, int64_t count, const int32_t* free_, const int32_t* steps) {
+  if (!v || !origins || !dirs || !max_dists || count < 0 || count > 0x7fffffffLL) return SFRT_E_INVALID;
+  if (!free_ && !steps) return SFRT_E_INVALID;
+  if (!aligned4({origins, dirs, max_dists, free_, steps})) return SFRT_E_INVALID;
+  return SFRT_OK;
+}
+// What a batch needs of the world (mutex held), before anything is queued.
+int rays_world(const sfrt_voxel* v) {
+  if (v->blocks.empty()) return SFRT_E_EMPTY;
+  // prepare() stages the frame tables too (a batch counts as a frame call): their size must fit
+  if (v->width <= 0 || v->height <= 0 || !v->sample_grid_ok(1, 1)) return SFRT_E_INVALID;
+  return SFRT_OK;
+}
+
+// One launch of the ray-batch kernel on s with the world's mutex held: the frame fill's snapshot
+// (prepare: the deferred grid upload, the staged tables, camera and view distances) and nothing
+// of the tile-order chains.
+int cast_rays_launch(sfrt_voxel* v, const float* dev_dirs, const float* dev_yscales,
+                     const float* dev_origins, int64_t count, const sfrt_voxel_ray_hits& out,
+                     hipStream_t s) {
+  sfrt::VoxFrame f;
+  const int rc = v->prepare(f, s);
+  if (rc) return rc;
+  sfrt::VoxRays a{};
+  a.dirs = dev_dirs;
+  a.yscales = dev_yscales;
+  a.origins = dev_origins;
+  a.count = count;
+  a.pos = out.pos;
+  a.depth = out.depth;
+  a.cell = out.cell;
+  a.face = out.face;
+  a.steps = out.steps;
+  a.rgba = (uint32_t*)out.rgba;
+  if (sfrt::launch_voxel_rays(f, a, s, v->launch_event())) return SFRT_E_HIP;
+  HIP_TRY(v->launched(s));
+  return SFRT_OK;
+}
+int shadow_rays_launch(sfrt_voxel* v, const float* dev_origins, const float* dev_dirs,
+                       const float* dev_max_dists, int64_t count, int32_t* dev_free,
+                       int32_t* dev_steps, hipStream_t s) {
+  sfrt::VoxFrame f;
+  const int rc = v->prepare(f, s);
+  if (rc) return rc;
+  sfrt::VoxShadowRays a{};
+  a.origins = dev_origins;
+  a.dirs = dev_dirs;
+  a.max_dists = dev_max_dists;
+  a.count = count;
+  a.free_ = dev_free;
+  a.steps = dev_steps;
+  if (sfrt::launch_voxel_shadow_rays(f, a, s, v->launch_event())) return SFRT_E_HIP;
+  HIP_TRY(v->launched(s));
+  return SFRT_OK;
+}
+
+// The host calls' staging buffers at `bytes` or more.  Growth waits for no other stream, as
+// update_image's: the device buffer stream-ordered on the world's stream (the last host call
+// waited for its own copies), the old pinned one retired.
+int grow_rays(sfrt_voxel* v, size_t bytes) {
+  if (v->d_rays_bytes < bytes) {
+    if (v->d_rays) HIP_TRY(hipFreeAsync(v->d_rays, v->stream));
+    v->d_rays = nullptr;
+    v->d_rays_bytes = 0;
+    HIP_TRY(hipMallocAsync((void**)&v->d_rays, bytes, v->stream));
+    v->d_rays_bytes = bytes;
+  }
+  if (v->h_rays_bytes < bytes) {
+    v->retired_host.add(v->h_rays);
+    v->h_rays = nullptr;
+    v->h_rays_bytes = 0;
+    HIP_TRY(hipHostMalloc((void**)&v->h_rays, bytes, hipHostMallocDefault));
+    v->h_rays_bytes = bytes;
+  }
+  return SFRT_OK;
+}
+
+}  // namespace
+
+int sfrt_voxel_cast_rays_device(sfrt_voxel* v, const float* dev_dirs, const float* dev_yscales,
+                                const float* dev_origins, int64_t count,
+                                const sfrt_voxel_ray_hits* dev_out, void* hip_stream) {
+  int rc = cast_rays_args(v, dev_dirs, dev_yscales, dev_origins, count, dev_out);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(v->mu);
+  if (count == 0) return SFRT_OK;
+  if ((rc = rays_world(v))) return rc;
+  sfrt::DeviceGuard g(v->device);
+  return cast_rays_launch(v, dev_dirs, dev_yscales, dev_origins, count, *dev_out, (hipStream_t)hip_stream);
+}
+
+int sfrt_voxel_cast_rays(sfrt_voxel* v, const float* dirs, const float* yscales, const float* origins,
+                         int64_t count, const sfrt_voxel_ray_hits* out) {
+  int rc = cast_rays_args(v, dirs, yscales, origins, count, out);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(v->mu);
+  if (count == 0) return SFRT_OK;
+  if ((rc = rays_world(v))) return rc;
+  sfrt::DeviceGuard g(v->device);
+  // The staging layout: dirs, yscales, origins, then the requested outputs, 4-byte elements.
+  const size_t n = (size_t)count;
+  const size_t off_ys = n * 12, off_org = off_ys + (yscales ? n * 4 : 0);
+  const size_t in_bytes = off_org + (origins ? n * 12 : 0);
+  void* const host_out[6] = {out->pos, out->depth, out->cell, out->face, out->steps, out->rgba};
+  const size_t elem[6] = {12, 4, 4, 4, 4, 4};
+  size_t off[6] = {}, bytes = in_bytes;
+  for (int q = 0; q < 6; q++) {
+    off[q] = bytes;
+    if (host_out[q]) bytes += n * elem[q];
+  }
+  if ((rc = grow_rays(v, bytes))) return rc;
+  std::memcpy(v->h_rays, dirs, n * 12);
+  if (yscales) std::memcpy(v->h_rays + off_ys, yscales, n * 4);
+  if (origins) std::memcpy(v->h_rays + off_org, origins, n * 12);
+  HIP_TRY(hipMemcpyAsync(v->d_rays, v->h_rays, in_bytes, hipMemcpyHostToDevice, v->stream));
+  sfrt_voxel_ray_hits dev{};
+  dev.pos = host_out[0] ? (float*)(v->d_rays + off[0]) : nullptr;
+  dev.depth = host_out[1] ? (float*)(v->d_rays + off[1]) : nullptr;
+  dev.cell = host_out[2] ? (int32_t*)(v->d_rays + off[2]) : nullptr;
+  dev.face = host_out[3] ? (int32_t*)(v->d_rays + off[3]) : nullptr;
+  dev.steps = host_out[4] ? (int32_t*)(v->d_rays + off[4]) : nullptr;
+  dev.rgba = host_out[5] ? v->d_rays + off[5] : nullptr;
+  if ((rc = cast_rays_launch(v, (const float*)v->d_rays,
+                             yscales ? (const float*)(v->d_rays + off_ys) : nullptr,
+                             origins ? (const float*)(v->d_rays + off_org) : nullptr, count, dev,
+                             v->stream)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(v->h_rays + in_bytes, v->d_rays + in_bytes, bytes - in_bytes,
+                         hipMemcpyDeviceToHost, v->stream));
+  rc = v->read_status(v->stream);
+  if (rc) return rc;  // SFRT_E_TEXEL included: no output is written, as sfrt_voxel_update_image_aux
+  for (int q = 0; q < 6; q++)
+    if (host_out[q]) std::memcpy(host_out[q], v->h_rays + off[q], n * elem[q]);
+  return SFRT_OK;
+}
+
+int sfrt_voxel_cast_shadow_rays_device(sfrt_voxel* v, const float* dev_origins, const float* dev_dirs,
+                                       const float* dev_max_dists, int64_t count, int32_t* dev_free,
+                                       int32_t* dev_steps, void* hip_stream) {
+  int rc = shadow_rays_args(v, dev_origins, dev_dirs, dev_max_dists, count, dev_free, dev_steps);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(v->mu);
+  if (count == 0) return SFRT_OK;
+  if ((rc = rays_world(v))) return rc;
+  sfrt::DeviceGuard g(v->device);
+  return shadow_rays_launch(v, dev_origins, dev_dirs, dev_max_dists, count, dev_free, dev_steps,
+                            (hipStream_t)hip_stream);
+}
+
+int sfrt_voxel_cast_shadow_rays(sfrt_voxel* v, const float* origins, const float* dirs,
+                                const float* max_dists, int64_t count, int32_t* free_, int32_t* steps) {
+  int rc = shadow_rays_args(v, origins, dirs, max_dists, count, free_, steps);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(v->mu);
+  if (count == 0) return SFRT_OK;
+  if ((rc = rays_world(v))) return rc;
+  sfrt::DeviceGuard g(v->device);
+  // origins, dirs, max_dists, then the requested outputs
+  const size_t n = (size_t)count;
+  const size_t in_bytes = n * 28;
+  const size_t off_free = in_bytes, off_steps = off_free + (free_ ? n * 4 : 0);
+  const size_t bytes = off_steps + (steps ? n * 4 : 0);
+  if ((rc = grow_rays(v, bytes))) return rc;
+  std::memcpy(v->h_rays, origins, n * 12);
+  std::memcpy(v->h_rays + n * 12, dirs, n * 12);
+  std::memcpy(v->h_rays + n * 24, max_dists, n * 4);
+  HIP_TRY(hipMemcpyAsync(v->d_rays, v->h_rays, in_bytes, hipMemcpyHostToDevice, v->stream));
+  if ((rc = shadow_rays_launch(v, (const float*)v->d_rays, (const float*)(v->d_rays + n * 12),
+                               (const float*)(v->d_rays + n * 24), count,
+                               free_ ? (int32_t*)(v->d_rays + off_free) : nullptr,
+                               steps ? (int32_t*)(v->d_rays + off_steps) : nullptr, v->stream)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(v->h_rays + in_bytes, v->d_rays + in_bytes, bytes - in_bytes,
+                         hipMemcpyDeviceToHost, v->stream));
+  HIP_TRY(hipStreamSynchronize(v->stream));  // no status: a shadow ray reads no texel
+  if (free_) std::memcpy(free_, v->h_rays + off_free, n * 4);
+  if (steps) std::memcpy(steps, v->h_rays + off_steps, n * 4);
+  return SFRT_OK;
 }
 
 int sfrt_voxel_set_option(sfrt_voxel* v, int option, int value) {

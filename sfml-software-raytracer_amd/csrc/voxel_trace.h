@@ -114,6 +114,44 @@ long long voxel_tile_key(const VoxFrame& f, long long* tiles);
 int launch_voxel(const VoxFrame& f, void* stream, void* done_event = nullptr,
                  const VoxAux* aux = nullptr);
 
+// A batch of caller-supplied rays (sfrt_voxel_cast_rays[_device]): device pointers,
+// ray q's direction at dirs[3q..3q+2] (r->dir verbatim), its r->yscale at yscales[q] (null: 1.0f
+// for every ray), its origin at origins[3q..3q+2] (null: f.cam, with the billboards); every
+// output one element per ray (pos 3 floats, rgba one packed dword) or null, not all null.
+struct VoxRays {
+  const float* dirs;
+  const float* yscales;
+  const float* origins;
+  long long count;
+  float* pos;
+  float* depth;
+  int32_t* cell;
+  int32_t* face;
+  int32_t* steps;
+  uint32_t* rgba;
+};
+// One wave per 64 consecutive rays (k_voxel_cast_rays).  Of f it reads the camera, the view and
+// shadow distances, maxiter, the grid, the textures, colours, billboards and lights and the
+// status word: no frame tables, no subset, no output, no tile order.  done_event as launch_voxel's.
+int launch_voxel_rays(const VoxFrame& f, const VoxRays& rays, void* stream, void* done_event = nullptr);
+
+// sfrt_voxel_cast_shadow_rays[_device]'s bound on max_dist (SFRT_VOXEL_MAX_SHADOW_DIST): the
+// reference's trip limit is max(maxDist * 2, 20), so this is at most 8192 trips per ray.
+constexpr float kVoxMaxShadowDist = 4096.0f;
+// A batch of World::LRaycast queries: r->pos, r->dir (verbatim) and r->maxDist per ray; free_
+// (1 free, 0 blocked or out of trips, -1 invalid) and steps (trips of the loop's body), either
+// null but not both.  Of f it reads the grid alone (k_voxel_shadow_rays).
+struct VoxShadowRays {
+  const float* origins;
+  const float* dirs;
+  const float* max_dists;
+  long long count;
+  int32_t* free_;
+  int32_t* steps;
+};
+int launch_voxel_shadow_rays(const VoxFrame& f, const VoxShadowRays& rays, void* stream,
+                             void* done_event = nullptr);
+
 // Rewrites the key-indexed grid `cells` for a world of nx x ny x nz codes (`codes`, device,
 // x-major then y then z, as set_blocks takes them): every byte of planes x < bx, rows y < by,
 // columns z < bz gets its code inside the world and 0 outside it.  (bx, by, bz) covers the world

@@ -34,6 +34,9 @@ __device__ __forceinline__ int32_t to_i32(float f) {
 // A primary-ray DDA position to its cell coordinate: to_i32, or in the fast DDA (every lane of
 // the wave within the host's dda_qlim bound, so |f| < 2^30) the plain conversion it equals
 // there -- one v_cvt_i32_f32 instead of a compare, a conversion and a select per axis and step.
+// FAST is raycast_t's parameter of that name: a property of the wave's positions, proved by
+// whoever picks the instantiation (raycast() from the frame's dda_qlim, the ray batches from
+// the wave's own origins and directions, walk_bounded), and not of the divisions (RECIP).
 template <bool FAST>
 __device__ __forceinline__ int32_t pos_i32(float f) {
   return FAST ? (int32_t)f : to_i32(f);
@@ -244,14 +247,35 @@ struct VoxHit {
   int32_t cell, face, steps;
 };
 
+// What a ray batch (k_voxel_cast_rays) adds to a lane's ray: whether the lane marches at all (a
+// lane past the batch's end or with an invalid ray does not enter the step loop), the ray's own
+// origin (OWN) and, back, r->pos where Raycast ended.  The frame kernels pass none (NoRay).
+struct BatchRay {
+  bool live;
+  V3 org;
+  V3 end;
+};
+struct NoRay {};
+
 // World::Raycast, World.cpp:302-453.  AUX: also the outcome in `hit` (untouched without it).
-template <bool RECIP, bool AUX>
+// RECIP: the reciprocal divisions (every lane's |dir| components within recip_ok).  FAST: the
+// plain position conversions and the NaN-free choice of the step's axis -- every position of
+// every lane's walk stays below 2^30 in magnitude (pos_i32).  FAST implies RECIP's operands are
+// finite with normal or zero quotients; RECIP without FAST is not instantiated (a position past
+// 2^31 makes numerators that overflow the quotient, where div_recip gives NaN for the division's
+// inf).  The ray batches (RAY = BatchRay) add: OWN, the ray starts at its own origin and the
+// billboard list is not visited; SHADE = false, a block hit is not shaded (returns 0).
+template <bool RECIP, bool FAST, bool AUX, bool OWN = false, bool SHADE = true, class RAY = NoRay>
 __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
-                              float atan_dir, uint32_t& work, VoxHit& hit) {
+                              float atan_dir, uint32_t& work, VoxHit& hit, RAY& ray) {
+  static_assert(RECIP == FAST, "the reciprocal divisions are proved under FAST's bound only");
+  constexpr bool BATCH = !__is_same(RAY, NoRay);
+  static_assert(BATCH || (!OWN && SHADE), "OWN and SHADE = false are the ray batches'");
   const V3 cam{f.cam[0], f.cam[1], f.cam[2]};
   float dist = 0.0f;
   V3 pos = cam;
-  int32_t pix = pos_i32<RECIP>(pos.x), piy = pos_i32<RECIP>(pos.y), piz = pos_i32<RECIP>(pos.z);
+  if constexpr (OWN) pos = ray.org;
+  int32_t pix = pos_i32<FAST>(pos.x), piy = pos_i32<FAST>(pos.y), piz = pos_i32<FAST>(pos.z);
   // The reference's tryPos (World.cpp:318) equals pos at the top of every step (pos = tryPos
   // ends each step), so the step advances pos in place after the billboard loop, which works
   // on copies of pos and dist (the reference moves both there and then overwrites them with
@@ -265,6 +289,7 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
               yz = RECIP ? 1.0f / lz : 0.0f;
   int DI = 0;
   float dnext = f.ndyn > 0 ? f.dyn[0].dist : __builtin_nanf("");  // next billboard; NaN: never >=
+  if constexpr (OWN) dnext = __builtin_nanf("");  // no billboard: f.dyn is not read
   int colRay = 0;
   float last_x = 0.0f, last_y = 0.0f, last_z = 0.0f;  // the last step's rays (colRay, below)
   // Shading after the loop: a lane that hits a block (or a billboard's opaque texel) stops
@@ -295,7 +320,11 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
   // billboard that stopped the lane (its `dist` is +inf by then; DI stays at that billboard)
   uint32_t trips = 0u;
   float stop_dist = 0.0f;
+  V3 stop_pos{0.0f, 0.0f, 0.0f};  // BATCH: the position of that billboard (bp; pos moves on)
   if (0.0f < f.view_distance && 0u < f.maxiter) {
+    if constexpr (BATCH) {  // a lane without a ray to march stays out of the step loop
+      if (!ray.live) goto marched;
+    }
     for (uint32_t i = 0;;) {
       work++;
       const float xray = dv<RECIP>(dda_num(dirxadd, sx, pos.x, pix), lx, yx);
@@ -311,7 +340,7 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
       // +-0 alike)
       bool ax, ay;
       float raySpeed;
-      if (RECIP) {
+      if (FAST) {
         raySpeed = fminf(fminf(xray, yray), zray);
         ax = xray == raySpeed;
         ay = !ax & (yray == raySpeed);
@@ -358,6 +387,7 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
                              to_u8(min255((float)((c >> 16) & 0xffu) * d.b)), c >> 24);
                 tryDist = __builtin_inff();  // stops the lane through the loop test
                 if constexpr (AUX) stop_dist = bdist;
+                if constexpr (BATCH) stop_pos = bp;
                 break;
               }
             }
@@ -370,19 +400,21 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
       pos.x += dir.x * (ax ? rs2 : raySpeed);  // tryPos (World.cpp:330-350)
       pos.y += dir.y * (ay ? rs2 : raySpeed);
       pos.z += dir.z * ((ax | ay) ? raySpeed : rs2);
-      pix = pos_i32<RECIP>(pos.x); piy = pos_i32<RECIP>(pos.y); piz = pos_i32<RECIP>(pos.z);
+      pix = pos_i32<FAST>(pos.x); piy = pos_i32<FAST>(pos.y); piz = pos_i32<FAST>(pos.z);
       cell_hit(f, pix, piy, piz, hcode);  // hcode != 0: hit a block (World.cpp:385)
       i++;
       if constexpr (AUX) trips = i;
       if ((hcode != 0u) | !(dist < f.view_distance) | !(i < f.maxiter)) break;
     }
   }
+marched:
   if constexpr (AUX) {  // a march-out; the two returns below overwrite their fields
     hit.depth = dist;
     hit.cell = -1;
     hit.face = 0;
     hit.steps = (int32_t)trips;
   }
+  if constexpr (BATCH) ray.end = early != 0u ? stop_pos : pos;  // :357, or :381 / the loop's exit
   if (early != 0u) {  // a billboard's texel with alpha > 127: never 0
     if constexpr (AUX) {
       hit.depth = stop_dist;
@@ -393,7 +425,7 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
   }
   // the axis of the lane's last step, from that step's rays (kept in registers: the loop's last
   // assignment is its exit value), by the step's own rule
-  if (RECIP) {
+  if (FAST) {
     const float rs = fminf(fminf(last_x, last_y), last_z);
     colRay = last_x == rs ? 1 : (last_y == rs ? 2 : 3);
   } else {
@@ -409,6 +441,7 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
       hit.face = colRay == 1 ? (sx < 0.0f ? -1 : 1) : colRay == 2 ? (sy < 0.0f ? -2 : 2)
                                                                   : (sz < 0.0f ? -3 : 3);
     }
+    if constexpr (!SHADE) return 0u;  // the picking path: no texel, no light loop, no shadow rays
     return shade_hit<RECIP>(f, pos, pix, piy, piz, colRay, sx, sy, sz, dist,
                             (int)hcode - kVoxCellBias, work);
   }
@@ -423,9 +456,10 @@ __device__ uint32_t raycast(const VoxFrame& f, V3 dir, float yscale,
   const float lx = fabsf(dir.x), ly = fabsf(dir.y), lz = fabsf(dir.z);
   const bool ok = recip_ok(lx) && recip_ok(ly) && recip_ok(lz) &&
                   fmaxf(fmaxf(lx, ly), lz) <= f.dda_qlim * fminf(fminf(lx, ly), lz);
+  NoRay none;
   if (__builtin_amdgcn_ballot_w64(!ok))
-    return raycast_t<false, AUX>(f, dir, yscale, atan_dir, work, hit);
-  return raycast_t<true, AUX>(f, dir, yscale, atan_dir, work, hit);
+    return raycast_t<false, false, AUX>(f, dir, yscale, atan_dir, work, hit, none);
+  return raycast_t<true, true, AUX>(f, dir, yscale, atan_dir, work, hit, none);
 }
 
 // The lane's outcome into the planes of `aux` at output pixel (row r, column a) of the band.
@@ -556,6 +590,126 @@ __global__ __launch_bounds__(64, SFRT_VOX_AUX_WAVES) void k_voxel_aux(VoxFrame f
   }
 }
 
+// ---- Ray batches: World::Raycast / World::LRaycast for caller-supplied rays
+// (sfrt_voxel_cast_rays, sfrt_voxel_cast_shadow_rays) ----
+//
+// The frame kernels take the fast DDA (reciprocal divisions, plain conversions, the NaN-free axis
+// choice) on the host's dda_qlim, which is derived from cam, maxiter and the frame tables' largest
+// component.  A caller's rays have neither that origin nor those directions, so a batch wave
+// proves the same bound from its own lanes: dda_qlim's argument (sfrt_voxel.cpp) with the lane's
+// origin o in cam's place and the lane's own X = max_k |d_k|, m = min_k |d_k| -- one step moves an
+// axis by less than S = 2.001 X / m + 0.003 X + 33 while the position is below 2^30, so
+// |o|_max + (trips + 1) S <= 2^30 keeps every position of a walk of `trips` steps below 2^30.
+// Evaluated in binary32: every term is non-negative (no cancellation) and the seven roundings
+// stay within 2^-20 relative, so the sum is held to 2^30 - 2^20 instead; an overflow or a NaN
+// compares false.  m >= 2^-60 (recip_ok) is part of it.  DESIGN.md 20 has the argument.
+__device__ __forceinline__ bool walk_bounded(V3 o, V3 d, float trips) {
+  const float lx = fabsf(d.x), ly = fabsf(d.y), lz = fabsf(d.z);
+  const float X = fmaxf(fmaxf(lx, ly), lz), m = fminf(fminf(lx, ly), lz);
+  const float P = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
+  const float S = 2.001f * (X / m) + 0.003f * X + 33.0f;
+  return recip_ok(lx) && recip_ok(ly) && recip_ok(lz) && P + (trips + 1.0f) * S <= 1072693248.0f;
+}
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+  return fabsf(x) < __builtin_inff() && fabsf(y) < __builtin_inff() && fabsf(z) < __builtin_inff();
+}
+
+// One wave per 64 consecutive rays, ray q = 64 * block + lane, through the frame kernels'
+// raycast_t.  A lane past the batch's end and a lane with an invalid ray (a non-finite component
+// of dir, origin or yscale) get the direction (1, 1, 1), yscale 1 and the origin 0 -- operands
+// that vote for the fast DDA -- and stay out of the step loop (BatchRay::live), so they read no
+// cell, no billboard and no texel, set no status bit and change no other lane's path: raycast_t's
+// other ballots (billboards, the light skip, lraycast) run inside or after the loop, among the
+// lanes that marched.  OWN: origins given, no billboards (dnext is NaN, f.dyn is not read);
+// without it atan2f(dir.z, dir.x) of VAngleXZ is evaluated per ray, only when there are
+// billboards.  SHADE: rgba requested.  Each output is stored under a wave-uniform null test.
+// The plain frame kernels' bound, eight waves per SIMD: 63 (camera) / 64 (OWN) VGPRs shaded, 55 / 59
+// unshaded, no scratch; under the AUX kernels' seven-wave bound the shaded ones took 66 / 68 and
+// measured 4 % slower (tools/kernel_resources.py).
+template <bool OWN, bool SHADE>
+__global__ __launch_bounds__(64, SFRT_VOX_WAVES) void k_voxel_cast_rays(VoxFrame f, VoxRays a) {
+  const int lane = threadIdx.x & 63;
+  const long long q = (long long)blockIdx.x * 64 + lane;
+  const bool in = q < a.count;
+  const long long qc = in ? q : a.count - 1;
+  const float* __restrict__ dp = a.dirs + 3 * qc;
+  const float rx = dp[0], ry = dp[1], rz = dp[2];
+  const float rs = a.yscales ? a.yscales[qc] : 1.0f;
+  bool ok = finite3(rx, ry, rz) && fabsf(rs) < __builtin_inff();
+  BatchRay ray;
+  ray.org = V3{f.cam[0], f.cam[1], f.cam[2]};
+  if constexpr (OWN) {
+    const float* __restrict__ op = a.origins + 3 * qc;
+    ray.org = V3{op[0], op[1], op[2]};
+    ok = ok && finite3(ray.org.x, ray.org.y, ray.org.z);
+  }
+  ray.live = in && ok;
+  const V3 dir{ok ? rx : 1.0f, ok ? ry : 1.0f, ok ? rz : 1.0f};
+  const float yscale = ok ? rs : 1.0f;
+  if (!ok) ray.org = V3{0.0f, 0.0f, 0.0f};
+  ray.end = ray.org;
+  float atan_dir = 0.0f;
+  if constexpr (!OWN) {
+    if (f.ndyn > 0) atan_dir = sfrt_math::atan2f(dir.z, dir.x);  // VAngleXZ's ray term (World.cpp:272)
+  }
+  uint32_t work = 0;
+  VoxHit hit;
+  uint32_t rgba;
+  if (__builtin_amdgcn_ballot_w64(!walk_bounded(ray.org, dir, (float)f.maxiter)))
+    rgba = raycast_t<false, false, true, OWN, SHADE>(f, dir, yscale, atan_dir, work, hit, ray);
+  else
+    rgba = raycast_t<true, true, true, OWN, SHADE>(f, dir, yscale, atan_dir, work, hit, ray);
+  if (in) {  // an invalid ray: face 0, cell -1, steps 0, all-zero bytes elsewhere
+    if (a.pos) {
+      float* const o = a.pos + 3 * q;
+      o[0] = ok ? ray.end.x : 0.0f;
+      o[1] = ok ? ray.end.y : 0.0f;
+      o[2] = ok ? ray.end.z : 0.0f;
+    }
+    if (a.depth) a.depth[q] = ok ? hit.depth : 0.0f;
+    if (a.cell) a.cell[q] = ok ? hit.cell : -1;
+    if (a.face) a.face[q] = ok ? hit.face : 0;
+    if (a.steps) a.steps[q] = ok ? hit.steps : 0;
+    if constexpr (SHADE) a.rgba[q] = ok ? rgba : 0u;
+  }
+}
+
+// World::LRaycast for ray q, the same shape, through the shading's lraycast_t.  A lane past the
+// end or with an invalid ray (a non-finite component or max_dist, or max_dist past
+// kVoxMaxShadowDist) gets origin 0, direction (1, 1, 1) and max_dist 0: it votes for the
+// reciprocal divisions and its loop never runs.  The reciprocal divisions only under
+// walk_bounded for the ray's own trip limit (lraycast()'s recip_ok alone holds for the shading's
+// rays, normalised and from a hit point; a caller's can leave the integers' range, where a
+// quotient overflows).  `steps` is lraycast_t's work count.
+__global__ __launch_bounds__(64) void k_voxel_shadow_rays(VoxFrame f, VoxShadowRays a) {
+  const int lane = threadIdx.x & 63;
+  const long long q = (long long)blockIdx.x * 64 + lane;
+  const bool in = q < a.count;
+  const long long qc = in ? q : a.count - 1;
+  const float* __restrict__ op = a.origins + 3 * qc;
+  const float* __restrict__ dp = a.dirs + 3 * qc;
+  const float ox = op[0], oy = op[1], oz = op[2];
+  const float rx = dp[0], ry = dp[1], rz = dp[2];
+  const float md = a.max_dists[qc];
+  const bool ok = finite3(ox, oy, oz) && finite3(rx, ry, rz) && fabsf(md) < __builtin_inff() &&
+                  md <= kVoxMaxShadowDist;
+  const V3 org{ok ? ox : 0.0f, ok ? oy : 0.0f, ok ? oz : 0.0f};
+  const V3 dir{ok ? rx : 1.0f, ok ? ry : 1.0f, ok ? rz : 1.0f};
+  const float max_dist = in && ok ? md : 0.0f;
+  const float m2 = max_dist * 2;
+  uint32_t work = 0;
+  bool free_;
+  if (__builtin_amdgcn_ballot_w64(!walk_bounded(org, dir, m2 < 20.0f ? 20.0f : m2)))
+    free_ = lraycast_t<false>(f, org, dir, max_dist, work);
+  else
+    free_ = lraycast_t<true>(f, org, dir, max_dist, work);
+  if (in) {
+    if (a.free_) a.free_[q] = ok ? (free_ ? 1 : 0) : -1;
+    if (a.steps) a.steps[q] = ok ? (int32_t)work : 0;
+  }
+}
+
 // The grid rewrite of launch_voxel_cells: one 256-lane workgroup per (x, y) row of the box, four
 // bytes of the row per lane (a row starts at a 1 KiB boundary, so the full words are aligned
 // dword stores).
@@ -644,6 +798,42 @@ int launch_voxel(const VoxFrame& f, void* stream, void* done_event, const VoxAux
   else
     hipExtLaunchKernelGGL(k_voxel_ordered<false>, grid, dim3(64), 0, (hipStream_t)stream, nullptr,
                           (hipEvent_t)done_event, 0, f, (int)((f.sub_w + 7) / 8), (int)tiles);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+namespace {
+template <bool OWN, bool SHADE>
+void launch_rays(const VoxFrame& f, const VoxRays& a, dim3 grid, void* stream, void* done_event) {
+  hipExtLaunchKernelGGL((k_voxel_cast_rays<OWN, SHADE>), grid, dim3(64), 0, (hipStream_t)stream, nullptr,
+                        (hipEvent_t)done_event, 0, f, a);
+}
+}  // namespace
+
+int launch_voxel_rays(const VoxFrame& f, const VoxRays& a, void* stream, void* done_event) {
+  if (a.count == 0) return 0;
+  // as launch_voxel: the grid through a buffer resource, the tables unguarded
+  if (!f.cells || f.cell_bytes == 0 || !f.status || (f.ndyn > 0 && !f.dyn) || (f.nlights > 0 && !f.lights))
+    return -1;
+  if (!a.dirs || a.count < 0 || a.count > 0x7fffffffLL) return -1;
+  if (!a.pos && !a.depth && !a.cell && !a.face && !a.steps && !a.rgba) return -1;
+  const dim3 grid((unsigned)((a.count + 63) / 64));
+  if (a.origins) {
+    if (a.rgba) launch_rays<true, true>(f, a, grid, stream, done_event);
+    else launch_rays<true, false>(f, a, grid, stream, done_event);
+  } else {
+    if (a.rgba) launch_rays<false, true>(f, a, grid, stream, done_event);
+    else launch_rays<false, false>(f, a, grid, stream, done_event);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_voxel_shadow_rays(const VoxFrame& f, const VoxShadowRays& a, void* stream, void* done_event) {
+  if (a.count == 0) return 0;
+  if (!f.cells || f.cell_bytes == 0) return -1;
+  if (!a.origins || !a.dirs || !a.max_dists || a.count < 0 || a.count > 0x7fffffffLL) return -1;
+  if (!a.free_ && !a.steps) return -1;
+  hipExtLaunchKernelGGL(k_voxel_shadow_rays, dim3((unsigned)((a.count + 63) / 64)), dim3(64), 0,
+                        (hipStream_t)stream, nullptr, (hipEvent_t)done_event, 0, f, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -64,6 +64,8 @@ ABI_SYMBOLS = (
     "sfrt_world_tile_record_bytes", "sfrt_world_render_band_aux", "sfrt_world_update_image_aux",
     "sfrt_world_cast_rays", "sfrt_world_cast_rays_device",
     "sfrt_voxel_render_band_aux", "sfrt_voxel_update_image_aux",
+    "sfrt_voxel_cast_rays", "sfrt_voxel_cast_rays_device",
+    "sfrt_voxel_cast_shadow_rays", "sfrt_voxel_cast_shadow_rays_device",
 )
 
 SFRT_MULTI_AUTO, SFRT_MULTI_RCCL, SFRT_MULTI_PEER = 0, 1, 2
@@ -119,6 +121,18 @@ class RayHits(ctypes.Structure):
 
 
 RAY_OUTPUTS = ("pos", "depth", "sphere", "steps", "rgba")
+
+
+class VoxelRayHits(ctypes.Structure):
+    """sfrt_voxel_ray_hits: the per-ray outputs of sfrt_voxel_cast_rays[_device] (None = not
+    wanted)."""
+    _fields_ = [("pos", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("cell", ctypes.c_void_p),
+                ("face", ctypes.c_void_p), ("steps", ctypes.c_void_p), ("rgba", ctypes.c_void_p)]
+
+
+VOXEL_RAY_OUTPUTS = ("pos", "depth", "cell", "face", "steps", "rgba")
+VOXEL_SHADOW_OUTPUTS = ("free", "steps")
+SFRT_VOXEL_MAX_SHADOW_DIST = 4096.0
 
 _lib = None
 
@@ -200,6 +214,10 @@ def lib() -> ctypes.CDLL:
         "sfrt_voxel_render_band_aux": ([vp, vp, ctypes.c_int64, P(VoxelAuxPlanes), c_int, c_int, vp],
                                        c_int),
         "sfrt_voxel_update_image_aux": ([vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int], c_int),
+        "sfrt_voxel_cast_rays": ([vp, vp, vp, vp, ctypes.c_int64, P(VoxelRayHits)], c_int),
+        "sfrt_voxel_cast_rays_device": ([vp, vp, vp, vp, ctypes.c_int64, P(VoxelRayHits), vp], c_int),
+        "sfrt_voxel_cast_shadow_rays": ([vp, vp, vp, vp, ctypes.c_int64, vp, vp], c_int),
+        "sfrt_voxel_cast_shadow_rays_device": ([vp, vp, vp, vp, ctypes.c_int64, vp, vp, vp], c_int),
         "sfrt_voxel_check": ([vp, vp], c_int),
         "sfrt_voxel_set_option": ([vp, c_int, c_int], c_int),
         "sfrt_voxel_get_option": ([vp, c_int, P(c_int)], c_int),
@@ -701,6 +719,79 @@ class VoxelWorld:
         planes = [np.zeros((h, w), dtype=dt) for _, dt in VOXEL_PLANES]
         self.update_image_aux(rgba, *planes)
         return (rgba, *planes)
+
+    # --- ray queries ---
+    def cast_rays(self, dirs, yscales=None, origins=None, outputs=VOXEL_RAY_OUTPUTS) -> dict:
+        """World::Raycast for a batch of caller-supplied rays (sfrt_voxel_cast_rays).
+
+        dirs: (N, 3) float32, used verbatim; yscales: (N,) float32 or None (1.0); origins: (N, 3)
+        float32, or None for the camera position (then with the billboards).  Returns
+        {name: array} for the requested outputs: pos (N, 3) float32, depth (N,) float32, cell,
+        face and steps (N,) int32, rgba (N, 4) uint8.  An invalid ray (a non-finite component) has
+        face 0, cell -1, steps 0 and zeros elsewhere."""
+        dirs = np.ascontiguousarray(np.asarray(dirs, dtype=np.float32).reshape(-1, 3))
+        n = dirs.shape[0]
+        if yscales is not None:
+            yscales = np.ascontiguousarray(np.asarray(yscales, dtype=np.float32).ravel())
+            if yscales.shape[0] != n:
+                raise ValueError("yscales must hold one value per direction")
+        if origins is not None:
+            origins = np.ascontiguousarray(np.asarray(origins, dtype=np.float32).reshape(-1, 3))
+            if origins.shape[0] != n:
+                raise ValueError("origins must hold one position per direction")
+        shapes = {"pos": ((n, 3), np.float32), "depth": ((n,), np.float32), "cell": ((n,), np.int32),
+                  "face": ((n,), np.int32), "steps": ((n,), np.int32), "rgba": ((n, 4), np.uint8)}
+        res = {name: np.zeros(*shapes[name]) for name in outputs}
+        hits = VoxelRayHits()
+        for name, arr in res.items():
+            # an empty array's pointer still says "requested"
+            setattr(hits, name, arr.ctypes.data if n else 4)
+        ptr = lambda a: None if a is None else (a.ctypes.data if n else 4)
+        _check(lib().sfrt_voxel_cast_rays(self._h, ptr(dirs), ptr(yscales), ptr(origins), n,
+                                          ctypes.byref(hits)), "voxel_cast_rays")
+        return res
+
+    def cast_rays_device(self, dirs_ptr: int, yscales_ptr, origins_ptr, count: int, stream: int = 0,
+                         pos=None, depth=None, cell=None, face=None, steps=None, rgba=None) -> None:
+        """Asynchronous sfrt_voxel_cast_rays_device on `stream`: device pointers (ints) to count*3
+        float32 directions, count yscales (None or 0: 1.0), count*3 origins (None or 0: the
+        camera position) and to each wanted output; the status is left to check(stream)."""
+        hits = VoxelRayHits()
+        for name, ptr in zip(VOXEL_RAY_OUTPUTS, (pos, depth, cell, face, steps, rgba)):
+            if ptr:
+                setattr(hits, name, int(ptr))
+        _check(lib().sfrt_voxel_cast_rays_device(self._h, ctypes.c_void_p(dirs_ptr or None),
+                                                 ctypes.c_void_p(yscales_ptr or None),
+                                                 ctypes.c_void_p(origins_ptr or None), int(count),
+                                                 ctypes.byref(hits), ctypes.c_void_p(stream or None)),
+               "voxel_cast_rays_device")
+
+    def cast_shadow_rays(self, origins, dirs, max_dists, outputs=VOXEL_SHADOW_OUTPUTS) -> dict:
+        """World::LRaycast for a batch of rays (sfrt_voxel_cast_shadow_rays): origins and dirs
+        (N, 3) float32 (dirs verbatim), max_dists (N,) float32.  Returns {name: (N,) int32} for
+        the requested outputs: free (1 free, 0 blocked or out of trips, -1 invalid ray) and steps
+        (trips of the loop's body).  max_dist above SFRT_VOXEL_MAX_SHADOW_DIST is invalid."""
+        origins = np.ascontiguousarray(np.asarray(origins, dtype=np.float32).reshape(-1, 3))
+        dirs = np.ascontiguousarray(np.asarray(dirs, dtype=np.float32).reshape(-1, 3))
+        max_dists = np.ascontiguousarray(np.asarray(max_dists, dtype=np.float32).ravel())
+        n = dirs.shape[0]
+        if origins.shape[0] != n or max_dists.shape[0] != n:
+            raise ValueError("origins, dirs and max_dists must hold one entry per ray")
+        res = {name: np.zeros(n, dtype=np.int32) for name in outputs}
+        ptr = lambda a: None if a is None else (a.ctypes.data if n else 4)
+        _check(lib().sfrt_voxel_cast_shadow_rays(self._h, ptr(origins), ptr(dirs), ptr(max_dists), n,
+                                                 ptr(res.get("free")), ptr(res.get("steps"))),
+               "voxel_cast_shadow_rays")
+        return res
+
+    def cast_shadow_rays_device(self, origins_ptr: int, dirs_ptr: int, max_dists_ptr: int, count: int,
+                                stream: int = 0, free=None, steps=None) -> None:
+        """Asynchronous sfrt_voxel_cast_shadow_rays_device on `stream` (device pointers as ints)."""
+        _check(lib().sfrt_voxel_cast_shadow_rays_device(
+            self._h, ctypes.c_void_p(origins_ptr or None), ctypes.c_void_p(dirs_ptr or None),
+            ctypes.c_void_p(max_dists_ptr or None), int(count), ctypes.c_void_p(free or None),
+            ctypes.c_void_p(steps or None), ctypes.c_void_p(stream or None)),
+            "voxel_cast_shadow_rays_device")
 
     def check(self, stream: int = 0) -> None:
         _check(lib().sfrt_voxel_check(self._h, ctypes.c_void_p(stream or None)), "voxel_check")
