@@ -39,9 +39,11 @@
  *    floor(v * 255 + 0.5).
  *
  * Pinning: no OpenGL context can run here (no EGL/OSMesa/Xvfb),
- * so this row is UNPINNED against the reference's own output; the scene
- * fixture (glsl_scenes.py) is pinned by reproducing the survey's srand(0)
- * default10 wall list.
+ * so the shader's GL output is not held: this file restates the shader and
+ * nothing compares it with a GL frame.  What is held is its input: the
+ * uniform replay (glsl_scenes.ShaderWorld) equals, bit for bit, the uniforms
+ * the reference's own compiled SphereWorld.cpp uploads after 0, 50 and 300
+ * UpdateWorld steps (tests/test_reference_pin.py).
  */
 #include <math.h>
 #include <pthread.h>

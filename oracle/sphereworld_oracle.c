@@ -23,16 +23,15 @@
  * (glibc 2.35 here and on the GPU box: sinf, cosf, atan2f, asinf), exactly
  * what the reference calls through std::sin / std::atan2 / std::asinf.
  *
- * PARITY UNPINNED.  The reference itself cannot be built in this image: it
- * needs SFML 2.4.2 (SphereWorld.h:3 includes <SFML/Graphics.hpp>), which is
- * absent, and stand-in headers are not allowed.  It ships no tests, fixtures or
- * golden data.  So nothing here pins this restatement to the reference's own
- * output.  What exists is a sanity check: the survey's per-pixel march
- * iteration statistics from a stub-SFML build, which
- * tests/test_oracle_golden.py reproduces.  The survey's FNV-1a-64 frame hashes
- * from that stub build do NOT reproduce (the stub's Image/Color semantics are
- * unrecorded).  tests/golden/ holds hashes generated from THIS file.  See
- * DESIGN.md section 3.
+ * PINNING.  tests/test_reference_pin.py holds this file to the reference's own
+ * arithmetic: the unmodified SphereWorld.cpp, compiled with gcc against the
+ * hand-written stand-in oracle/ref/SFML/Graphics.hpp (`make ref`), renders the
+ * same scenes and the frames must agree byte for byte -- live where the
+ * reference's sources exist, against tests/golden/reference/ everywhere.  Not
+ * held: MSVC's code generation, real SFML and stb, and the intermediates the
+ * reference does not expose (this file's dumps of them are pinned only through
+ * the end position and the colour).  tests/golden/golden.json holds hashes
+ * generated from THIS file.  See DESIGN.md section 3.
  */
 #include <math.h>
 #include <pthread.h>

@@ -16,11 +16,16 @@
  * block grid stands for the `blocks` unordered_map (World.cpp:6-32) with the
  * same key semantics, `dyn` and `alights` are passed in list order.
  *
- * Pinning: World.cpp needs SFML (absent) and stand-in headers are not allowed,
- * so it is not built here; it ships no tests.  The survey's single World hash
- * (8a3a61d6af69ddca, its own stub and unrecorded world state) cannot be
- * reproduced.  Parity for this row is therefore UNPINNED against the
- * original build: the GPU kernel is held bit-exact to this restatement.
+ * Pinning: tests/test_reference_pin.py holds this file to the reference's own
+ * arithmetic: the unmodified World.cpp, compiled with gcc against the stand-in
+ * oracle/ref/SFML/Graphics.hpp (`make ref`), renders the constructor's world
+ * and 24 snapshot worlds, and the frames must agree byte for byte (pixels for
+ * which the reference read outside a texture are left out and counted) -- live
+ * where the reference's sources exist, against tests/golden/reference/
+ * everywhere.  Not held: MSVC's code generation, real SFML and stb; the
+ * float -> int conversions outside int range are x86's as gcc emits them.
+ * (The survey's single World hash, 8a3a61d6af69ddca, came from its own stub
+ * and an unrecorded world state and cannot be reproduced.)
  */
 #include <math.h>
 #include <pthread.h>

@@ -5,10 +5,10 @@
 Writes golden.json: per (config, pose) the frame's FNV-1a-64 and SHA-256,
 per-row FNV-1a-64 for frames up to 4K, the march-iteration statistics, and
 ~1000 sampled-pixel float dumps for two configs; plus the full 320x240 frame
-(zlib-compressed RGBA8).  These are oracle outputs, not reference outputs: the oracle is
-parity unpinned (the reference needs SFML and ships no fixtures).  Its iteration statistics
-match the survey's stub-SFML probe (tests/test_oracle_golden.py), a sanity
-check; see DESIGN.md section 3.
+(zlib-compressed RGBA8).  These are oracle outputs, not reference outputs; what the
+reference's own compiled code gives is recorded by make_reference_golden.py into
+tests/golden/reference/, and tests/test_reference_pin.py holds the oracle to it (DESIGN.md
+section 3).
 """
 import hashlib
 import json

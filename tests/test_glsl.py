@@ -6,8 +6,10 @@ CPU: the uniform replay (glsl_scenes.py) reproduces the survey's srand(0)
 scene; the restatement (oracle/glsl_oracle.c) is deterministic across threads
 and bands and matches its committed golden hashes (tests/golden/golden.json
 "glsl").  GPU: libsfrt.so's GLSL kernel equals the restatement byte for byte.
-Parity against the reference's own OpenGL output is unpinned (no GL context
-can run here; DESIGN.md 4b fixes the semantics the shader leaves open).
+The uniforms are held to the reference: tests/test_reference_pin.py compares
+the replay with what the reference's own compiled SphereWorld.cpp uploads.
+The shader's OpenGL output is not held (no GL context can run here;
+DESIGN.md 4b fixes the semantics the shader leaves open).
 """
 import ctypes
 import ctypes.util

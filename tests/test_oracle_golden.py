@@ -1,11 +1,10 @@
 """The CPU restatement (oracle/) against the survey's sanity checks and the committed golden
 fixtures.
 
-PARITY UNPINNED: the reference cannot be built here (it needs SFML,
-SphereWorld.h:3) and ships no tests or fixtures, so nothing pins the oracle to the reference's
-own output.  The survey ran the reference TU against a stub SFML and recorded, per config, the
-march-iteration statistics of every pixel; reproducing them is a sanity
-check of everything up to the shading tail, not a pin.  The shading tail's transcendentals are
+The pin of the oracle to the reference's own compiled arithmetic is tests/test_reference_pin.py
+(DESIGN.md section 3); what is here are the older sanity checks.  The survey ran the reference
+TU against a stub SFML and recorded, per config, the march-iteration statistics of every pixel
+(SURVEY.md 8a, row a2); reproducing them checks everything up to the shading tail.  The shading tail's transcendentals are
 checked against the host libm exhaustively (test_math_exhaustive.py).  The survey's frame
 hashes from the same stub build do not reproduce (its Image/Color semantics are unrecorded).
 tests/golden/ holds hashes generated from the oracle itself (tests/golden/make_golden.py).

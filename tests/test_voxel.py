@@ -4,8 +4,8 @@
 CPU: the restatement (oracle/voxelworld_oracle.c) is deterministic across
 thread counts and interleaves, and matches its committed golden hashes
 (tests/golden/golden.json "voxel").  GPU: libsfrt.so's voxel kernel equals the
-restatement byte for byte (RGBA8).  Parity against the original build is
-unpinned: SFML is absent and the reference ships no World data.
+restatement byte for byte (RGBA8).  The restatement itself is held to the
+reference's own compiled World.cpp by tests/test_reference_pin.py.
 """
 import json
 import os
