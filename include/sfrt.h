@@ -147,8 +147,9 @@ SFRT_API int sfrt_world_check(sfrt_world* w, void* hip_stream);
  * unchanged, and the plain calls keep their behaviour exactly.
  * The planes come from kernels of their own, which compute their ray directions: an aux call
  * neither reads, fills nor invalidates the ray cache (SFRT_OPT_RAY_CACHE_MB) and leaves the
- * counters of sfrt_world_ray_cache_stats alone.  sfrt_world_submit_frame, sfrt_multi_* and the
- * GLSL renderer have no planes; the voxel renderer has its own (sfrt_voxel_render_band_aux). */
+ * counters of sfrt_world_ray_cache_stats alone.  sfrt_world_submit_frame and sfrt_multi_* have no
+ * planes; the voxel renderer has its own (sfrt_voxel_render_band_aux), and the GLSL renderer
+ * reuses this record (sfrt_glsl_draw_aux). */
 typedef struct {
   void* depth;  int64_t depth_pitch_bytes;   /* float   per pixel, or NULL */
   void* sphere; int64_t sphere_pitch_bytes;  /* int32_t per pixel, or NULL */
@@ -718,6 +719,70 @@ SFRT_API int sfrt_glsl_draw(sfrt_glsl* g, void* dev_pixels, int width, int heigh
 /* rt.draw + rt.getTexture().copyToImage() into a host RGBA8 buffer (synchronous). */
 SFRT_API int sfrt_glsl_draw_image(sfrt_glsl* g, uint8_t* pixels, int width, int height);
 SFRT_API int sfrt_glsl_check(sfrt_glsl* g, void* hip_stream);
+
+/* ---- the draw's per-pixel planes: depth, sphere index, march steps ----
+ * sfrt_glsl_draw / sfrt_glsl_draw_image plus the three optional planes of sfrt_aux_planes (4 bytes
+ * per pixel, each with its own pitch), written by the same launch that writes the colour:
+ *   depth  (float):   totalDist after rayShader.frag:117 -- the wall distance of the wall pass
+ *                     (:71-85) for a wall pixel, ballDist for a ball pixel -- before the
+ *                     brightness (:128) and the fog (:156) use it.
+ *   sphere (int32_t): drawSphere after :118, an index into the spheres[] uniform: walls are
+ *                     < sphereCount, then the lights, then the ospheres.
+ *   steps  (int32_t): the trips of the metaball loop :94-112 (0 when it never ran), the count the
+ *                     adaptive tile order uses as a tile's cost.
+ * Any plane may be NULL, but not all three.  SFRT_E_INVALID, with nothing queued or written, when
+ * all three are NULL or (draw_aux) a non-NULL plane's pitch is not a multiple of 4 or is below
+ * 4*width; a NULL plane's pitch is ignored.  The plain calls' own argument checks apply unchanged
+ * and the colour bytes are exactly the plain calls'.  Row r of a plane is at plane + (r - row0) *
+ * its pitch.  With SFRT_OPT_SUPERSAMPLE S = 2 or 4 the colour is box-filtered as always and the
+ * planes describe the output pixel's FIRST SAMPLE, fragment (S*i, S*row) of the S*width x S*height
+ * target: point-sampled; no filtered, minimum or per-sample depth.  A pixel whose march hit the
+ * cap (SFRT_E_MARCH_LIMIT) is unspecified, as its colour is.  Planes must not overlap each other
+ * or the colour target.  sfrt_glsl_draw_aux honours SFRT_OPT_TILE_ORDER and joins its stream's
+ * tile chain exactly as sfrt_glsl_draw does (the two share one chain); sfrt_glsl_draw_image_aux is
+ * row-major with host planes of width*height elements.  Table-slot reuse, ground ordering and the
+ * status word are the plain draw's. */
+SFRT_API int sfrt_glsl_draw_aux(sfrt_glsl* g, void* dev_pixels, int width, int height,
+                                int64_t pitch_bytes, const sfrt_aux_planes* aux,
+                                int row0, int rows, void* hip_stream);
+SFRT_API int sfrt_glsl_draw_image_aux(sfrt_glsl* g, uint8_t* pixels, float* depth,
+                                      int32_t* sphere, int32_t* steps, int width, int height);
+
+/* ---- batched ray queries: the shader's Raycast(campos, dir, 1) (rayShader.frag:63-161) ----
+ * Ray q has the direction dirs[3q..3q+2], un-normalised; :65 normalises it as it does a
+ * fragment's.  EVERY RAY STARTS AT campos.  There are no per-ray origins, on purpose: the
+ * shader's own Raycast marches the metaballs from campos whatever `pos` it is given (:95, :119),
+ * and the tables a draw prepares on the host (the first wall that holds campos, the -0.0 rule,
+ * the wall cull's margin, the shadow cones' bound) are per campos.  rotation, fov, size,
+ * SFRT_OPT_SUPERSAMPLE and SFRT_OPT_TILE_ORDER do not influence a batch (rotation, fov and size
+ * are not even validated for it); a batch joins no tile chain and leaves the recorded tile costs
+ * alone.  The uniforms are snapshotted at the call.
+ * Outputs (sfrt_ray_hits, each NULL or one element per ray, not all NULL):
+ *   pos    pos after :119: the wall pass's point for a wall hit, campos + dir * ballDist for a ball;
+ *   depth, sphere, steps   as the planes above;
+ *   rgba   the fragment's colour through the framebuffer's unorm8 conversion, alpha 255.
+ *          rgba == NULL skips the shading (:123-158) entirely.
+ * An invalid ray.  A ray is invalid when any direction component is not finite, or when
+ * s = (dx*dx + dy*dy) + dz*dz is not a finite normal number.  That covers zero, underflow and
+ * overflow.  It is decided per ray before the march.  It is never marched.  It gets sphere = -1,
+ * and every other requested output is all-zero bytes.  It must not change any other ray's result.
+ * It sets no status bit.
+ * Return codes and edge cases.  count == 0 returns SFRT_OK and writes nothing.  SFRT_E_INVALID,
+ * with nothing queued or written, for: a NULL shader; NULL dirs; a NULL output record; count < 0
+ * or count > 2^31-1; all five outputs NULL; a non-NULL pointer that is not 4-byte aligned; uniforms
+ * a draw would refuse (counts, bounds of campos and the sphere tables).  SFRT_E_NO_TEXTURE only
+ * when rgba is requested: a shader without a ground can still answer pos, depth, sphere and steps.
+ * Overlapping buffers are the caller's responsibility.
+ * Status.  The march-cap bit is the draw's own.  The device call leaves it to
+ * sfrt_glsl_check(g, hip_stream); the host call returns the code with the outputs written, as
+ * sfrt_glsl_draw_image does.  Calls serialise on the shader's mutex. */
+/* device memory on the shader's device, asynchronous on hip_stream */
+SFRT_API int sfrt_glsl_cast_rays_device(sfrt_glsl* g, const float* dev_dirs, int64_t count,
+                                        const sfrt_ray_hits* dev_out, void* hip_stream);
+/* host memory, synchronous */
+SFRT_API int sfrt_glsl_cast_rays(sfrt_glsl* g, const float* dirs, int64_t count,
+                                 const sfrt_ray_hits* out);
+
 /* SFRT_OPT_TILE_ORDER as for sfrt_world, on (1) by default: sfrt_glsl_draw dispatches 8x8
  * tiles longest-first by the metaball-march steps of two frames back (same bytes; 1-6 % faster
  * on the round-4 kernel); 0 = row-major.  sfrt_glsl_draw_image is row-major.

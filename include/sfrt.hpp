@@ -535,6 +535,41 @@ class Shader {
   void drawImage(uint8_t* pixels, int width, int height) {
     check(sfrt_glsl_draw_image(g_, pixels, width, height), "draw_image");
   }
+  // draw plus the per-pixel planes (sfrt.h sfrt_glsl_draw_aux): depth (totalDist), sphere
+  // (drawSphere) and steps (the metaball loop's trips), device memory, any of them null, not all.
+  void drawAux(void* dev_pixels, int width, int height, int64_t pitch_bytes,
+               const sfrt_aux_planes& aux, int row0, int rows, void* hip_stream) {
+    check(sfrt_glsl_draw_aux(g_, dev_pixels, width, height, pitch_bytes, &aux, row0, rows, hip_stream),
+          "draw_aux");
+  }
+  // drawImage plus host planes of width*height elements, any of them null, not all.
+  void drawImageAux(uint8_t* pixels, float* depth, int32_t* sphere, int32_t* steps, int width,
+                    int height) {
+    check(sfrt_glsl_draw_image_aux(g_, pixels, depth, sphere, steps, width, height), "draw_image_aux");
+  }
+  // The shader's Raycast(campos, r->dir, 1) (rayShader.frag:63-161) for one ray: reads r->dir
+  // (un-normalised), fills r->pos and r->c.  Every ray starts at the campos uniform: r->pos is
+  // not read (sfrt.h sfrt_glsl_cast_rays).  One launch and one wait per call; batches go
+  // through CastRays.
+  void Raycast(Ray* r) {
+    const float dir[3] = {r->dir.x, r->dir.y, r->dir.z};
+    float pos[3] = {0, 0, 0};
+    sfrt_ray_hits out{};
+    out.pos = pos;
+    out.rgba = r->c;
+    check(sfrt_glsl_cast_rays(g_, dir, 1, &out), "Raycast");
+    r->pos = Vector3f{pos[0], pos[1], pos[2]};
+  }
+  // `count` rays at once: dirs 3 floats per ray; any member of out may be null, not all.
+  void CastRays(const float* dirs, int64_t count, const sfrt_ray_hits& out) {
+    check(sfrt_glsl_cast_rays(g_, dirs, count, &out), "CastRays");
+  }
+  // The same on device memory, asynchronous on hip_stream (status through Check).
+  void CastRaysDevice(const float* dev_dirs, int64_t count, const sfrt_ray_hits& dev_out,
+                      void* hip_stream) {
+    check(sfrt_glsl_cast_rays_device(g_, dev_dirs, count, &dev_out, hip_stream), "CastRaysDevice");
+  }
+  void Check(void* hip_stream = nullptr) { check(sfrt_glsl_check(g_, hip_stream), "check"); }
   // SFRT_OPT_TILE_ORDER, SFRT_OPT_SUPERSAMPLE (sfrt.h): the latter, 2 or 4, box-filters the
   // fragments of the S*width x S*height target inside the kernel; draw's sizes stay in output pixels.
   void SetOption(int option, int value) { check(sfrt_glsl_set_option(g_, option, value), "set_option"); }

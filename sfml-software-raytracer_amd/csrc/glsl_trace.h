@@ -84,9 +84,38 @@ struct GlslFrame {
   int32_t ss;
 };
 
+// The per-pixel planes of sfrt_glsl_draw_aux / sfrt_glsl_draw_image_aux: device
+// pointers, null = not wanted, pitches in elements.  A kernel argument of its own behind the
+// frame record: the plain kernels' arguments stay what they were.  Addressed as f.out is, in
+// output pixels relative to row0.
+struct GlslAux {
+  float* depth;                        // totalDist after rayShader.frag:117
+  int32_t* sphere;                     // drawSphere after :118
+  int32_t* steps;                      // trips of the metaball loop :94-112
+  long long depth_pitch, sphere_pitch, steps_pitch;
+};
+
+// A batch of caller-supplied rays (sfrt_glsl_cast_rays[_device]): ray q's direction
+// at dirs + 3 q, un-normalised, every ray from f.campos.  Outputs null = not wanted, at least one.
+struct GlslRays {
+  const float* dirs;
+  long long count;
+  float* pos;                          // 3 floats per ray: pos after :119
+  float* depth;
+  int32_t* sphere;                     // -1: invalid ray
+  int32_t* steps;
+  uint32_t* rgba;
+};
+
 // Tile grid of the ordered GLSL kernel for f: key (> 0) and tile count.
 long long glsl_tile_key(const GlslFrame& f, long long* tiles);
 // done_event (hipEvent_t, may be null): recorded by the launch's own completion (its stop event).
-int launch_glsl(const GlslFrame& f, void* stream, void* done_event = nullptr);
+// aux (may be null): the plane-writing kernels on the same grid; not all of its planes null.
+int launch_glsl(const GlslFrame& f, void* stream, void* done_event = nullptr,
+                const GlslAux* aux = nullptr);
+// One wave per 64 consecutive rays (k_glsl_cast_rays).  Of f it reads campos, the counts, the
+// wall pass's host terms (cam_negzero, wall_start, wall_cull_margin), the tables and the status
+// word; the ground's mip chain only when rays.rgba is set.  rays.count in [1, 2^31).
+int launch_glsl_rays(const GlslFrame& f, const GlslRays& rays, void* stream, void* done_event = nullptr);
 
 }  // namespace sfrt

@@ -130,6 +130,15 @@ __device__ __forceinline__ uint64_t wall_mask(const GlslFrame& f, float dx, floa
   return __builtin_amdgcn_ballot_w64(keep);
 }
 
+// The lane's totalDist, drawSphere and march trips into the planes of `aux` at output pixel
+// (row r of the band, column c): one dword per non-null plane, where f.out's pixel goes.
+__device__ __forceinline__ void store_planes(const GlslAux& aux, int r, int c, float depth,
+                                             int sphere, int steps) {
+  if (aux.depth) aux.depth[(long long)r * aux.depth_pitch + c] = depth;
+  if (aux.sphere) aux.sphere[(long long)r * aux.sphere_pitch + c] = sphere;
+  if (aux.steps) aux.steps[(long long)r * aux.steps_pitch + c] = steps;
+}
+
 // SS (SFRT_OPT_SUPERSAMPLE, S = 1 << SS = 2 or 4): f is the S * width x S * height render target
 // (width, height, row0, rows, tiles_x, hk and vk of the sample grid: the host, sfrt_glsl.cpp), the
 // lane's fragment one of its samples; the tile's samples are box-filtered over each S x S group
@@ -138,17 +147,41 @@ __device__ __forceinline__ uint64_t wall_mask(const GlslFrame& f, float dx, floa
 // lanes a clamped duplicate, store false): the filter's adds read the lanes of the lane's own
 // group, and width and rows being multiples of S and tiles starting at multiples of 8, a group
 // is wholly inside the frame or wholly duplicates.
-template <bool CULL, int SS = 0>
+//
+// MODE, the one body for every kernel:
+//  kAux      the frame kernels that also write the planes of tap->aux at the colour's store site
+//            (supersampled: the group's leader lane, whose fragment is the output pixel's first
+//            sample (S * i, S * row)): totalDist and drawSphere after :117-118, the march's trips;
+//  kRay      a caller's ray (k_glsl_cast_rays): the un-normalised direction comes in tap->d
+//            instead of from (i, row), :65 normalises it as any fragment's, nothing is stored
+//            here and pos, depth, sphere, steps and the pixel go back in *tap;
+//  kRayBare  kRay without the shading (:123-158): rgba not wanted.
+enum { kPlain = 0, kAux = 1, kRay = 2, kRayBare = 3 };
+struct GlslTap {
+  const GlslAux* aux;      // kAux
+  float d[3];              // kRay: in
+  float pos[3], depth;     // kRay: out
+  int32_t sphere, steps;
+  uint32_t rgba;
+};
+
+template <bool CULL, int SS = 0, int MODE = kPlain>
 __device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall> walls,
                                          const_ptr<GlslBall> balls, int i, int row,
-                                         uint32_t& work, bool store = true) {
-  const float fx = (float)i + 0.5f;
-  const float fy = (float)(f.height - 1 - row) + 0.5f;
-  const float ax = -f.fov_x + f.hk * fx;                                   // :172-173
-  const float ay = -f.fov_y + f.vk * fy;
-  float dx = (f.fwd[0] + f.right[0] * ax) + f.up[0] * ay;                 // :175
-  float dy = (f.fwd[1] + f.right[1] * ax) + f.up[1] * ay;
-  float dz = (f.fwd[2] + f.right[2] * ax) + f.up[2] * ay;
+                                         uint32_t& work, bool store = true,
+                                         GlslTap* tap = nullptr) {
+  float dx, dy, dz;
+  if constexpr (MODE >= kRay) {
+    dx = tap->d[0]; dy = tap->d[1]; dz = tap->d[2];
+  } else {
+    const float fx = (float)i + 0.5f;
+    const float fy = (float)(f.height - 1 - row) + 0.5f;
+    const float ax = -f.fov_x + f.hk * fx;                                   // :172-173
+    const float ay = -f.fov_y + f.vk * fy;
+    dx = (f.fwd[0] + f.right[0] * ax) + f.up[0] * ay;                       // :175
+    dy = (f.fwd[1] + f.right[1] * ax) + f.up[1] * ay;
+    dz = (f.fwd[2] + f.right[2] * ax) + f.up[2] * ay;
+  }
   {
     const float l = len3(dx, dy, dz);                                     // :65
     const float a[3] = {dx, dy, dz};
@@ -309,6 +342,13 @@ __device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall>
   py = cw * py + cb * (cy + dy * ball_dist);
   pz = cw * pz + cb * (cz + dz * ball_dist);
   const float nsign = cw * -1.0f + cb;
+  if constexpr (MODE >= kRay) {
+    tap->pos[0] = px; tap->pos[1] = py; tap->pos[2] = pz;
+    tap->depth = total;
+    tap->sphere = draw;
+    tap->steps = steps;
+    if constexpr (MODE == kRayBare) return;
+  }
 
   // ---- texture (:123-126) ----
   const GlslMat& m = f.mats[draw];
@@ -421,18 +461,25 @@ __device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall>
   cr *= fog;
   cg *= fog;
   cbl *= fog;
-  if constexpr (SS == 0) {
-    if (store)
+  if constexpr (MODE == kRay) {
+    tap->rgba = unorm8(cr) | (unorm8(cg) << 8) | (unorm8(cbl) << 16) | (255u << 24);
+  } else if constexpr (SS == 0) {
+    if (store) {
       f.out[(long long)(row - f.row0) * f.out_pitch + i] =
           unorm8(cr) | (unorm8(cg) << 8) | (unorm8(cbl) << 16) | (255u << 24);
+      if constexpr (MODE == kAux) store_planes(*tap->aux, row - f.row0, i, total, draw, steps);
+    }
   } else {
     // the wave has reconverged (every branch above is wave-uniform or rejoins); alpha 255 in
     // every sample stays 255
     const uint32_t px =
         group_box_rgba8<SS>(unorm8(cr) | (unorm8(cg) << 8) | (unorm8(cbl) << 16) | (255u << 24));
     const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    if (group_leader<SS>(lane) && store)
+    if (group_leader<SS>(lane) && store) {
       f.out[(long long)((row - f.row0) >> SS) * f.out_pitch + (i >> SS)] = px;
+      if constexpr (MODE == kAux)
+        store_planes(*tap->aux, (row - f.row0) >> SS, i >> SS, total, draw, steps);
+    }
   }
 }
 
@@ -461,9 +508,10 @@ __global__ __launch_bounds__(256) void k_glsl(GlslFrame f) {
 // stays in the kernels' own bodies: inlined through here the compiler turned tile_bucket's chain
 // into other scalar code, and k_glsl_ordered is to compile to what it did before the
 // supersampling kernels came.
-template <int SS>
+template <int SS, int MODE = kPlain>
 __device__ __forceinline__ bool glsl_ordered_tile(const GlslFrame& f, int ntiles, int& tile,
-                                                  uint32_t& cls, uint32_t& work) {
+                                                  uint32_t& cls, uint32_t& work,
+                                                  GlslTap* tap = nullptr) {
   const int lane = threadIdx.x & 63;
   int slot = (int)blockIdx.x;
   if (f.prev_cost) {
@@ -481,8 +529,8 @@ __device__ __forceinline__ bool glsl_ordered_tile(const GlslFrame& f, int ntiles
   // branch around fragment() would cost its wave-uniform skips their uniformity.
   const bool in = i < f.width && r < f.rows;
   work = 0;
-  fragment<true, SS>(f, as_const(f.walls), as_const(f.balls), i < f.width ? i : f.width - 1,
-                      f.row0 + (r < f.rows ? r : f.rows - 1), work, in);
+  fragment<true, SS, MODE>(f, as_const(f.walls), as_const(f.balls), i < f.width ? i : f.width - 1,
+                            f.row0 + (r < f.rows ? r : f.rows - 1), work, in, tap);
   return true;
 }
 
@@ -525,6 +573,90 @@ __global__ __launch_bounds__(64) void k_glsl_ordered_ss(GlslFrame f, int ntiles)
   }
 }
 
+// The plane-writing instantiations (sfrt_glsl_draw_aux, sfrt_glsl_draw_image_aux),
+// kernels of their own for SS = 0, 1, 2: the eight above compile to what they did without them.
+// The planes travel as an argument behind the frame record.  The row-major one keeps its edge
+// lanes as clamped duplicates at every SS, as k_glsl_ss does.
+template <int SS>
+__global__ __launch_bounds__(256) void k_glsl_aux(GlslFrame f, GlslAux aux) {
+  const int lane = threadIdx.x & 63;
+  const int tile = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  const int tx = tile % f.tiles_x, ty = tile / f.tiles_x;
+  if (ty * 8 >= f.rows) return;  // wave-uniform
+  const int i = tx * 8 + (lane & 7);
+  const int r = ty * 8 + (lane >> 3);
+  const bool in = i < f.width && r < f.rows;
+  uint32_t work = 0;
+  GlslTap tap;
+  tap.aux = &aux;
+  fragment<false, SS, kAux>(f, as_const(f.walls), as_const(f.balls), i < f.width ? i : f.width - 1,
+                            f.row0 + (r < f.rows ? r : f.rows - 1), work, in, &tap);
+}
+
+template <int SS>
+__global__ __launch_bounds__(64) void k_glsl_ordered_aux(GlslFrame f, int ntiles, GlslAux aux) {
+  int tile;
+  uint32_t cls, work;
+  GlslTap tap;
+  tap.aux = &aux;
+  if (!glsl_ordered_tile<SS, kAux>(f, ntiles, tile, cls, work, &tap)) return;
+  if (f.tile_cost) {  // as k_glsl_ordered: the same cost record, the same chain
+    const uint32_t w = wave_max_u32(work);
+    if ((threadIdx.x & 63) == 0) store_cost(f.tile_cost, tile, tile_bucket(w), cls, f.cost_diff);
+  }
+}
+
+// ---- Ray batches: the shader's Raycast(campos, dir, 1) for caller-supplied directions
+// (sfrt_glsl_cast_rays) ----
+//
+// One wave per 64 consecutive rays, ray q = 64 * block + lane, through fragment() itself.  A ray
+// is valid when s = (x*x + y*y) + z*z is a finite normal number (finite only if every component
+// is).  fragment()'s wave helpers (wall_mask, the dominance ballots, div_shared) want all 64 lanes
+// running it with sane directions, so a lane past the batch's end and a lane with an invalid ray
+// run a duplicate of the wave's first valid ray and store nothing of it: a duplicate changes no
+// ballot's outcome for the lanes it copies, sets no status bit its original does not set, and
+// widens no cone.  A wave without a valid ray marches nothing.  CULL: wall_mask's cone is built
+// from the lanes' own unit directions and guarded by its own `wide` / sin_t tests, whatever the
+// directions are.  SHADE: rgba requested; without it the body ends after :119
+// (no texel, no light loop).  Each output is stored under a wave-uniform null test.
+template <bool SHADE>
+__global__ __launch_bounds__(64) void k_glsl_cast_rays(GlslFrame f, GlslRays a) {
+  const int lane = threadIdx.x & 63;
+  const long long q = (long long)blockIdx.x * 64 + lane;
+  const bool in = q < a.count;
+  const long long qc = in ? q : a.count - 1;
+  const float* __restrict__ dp = a.dirs + 3 * qc;
+  float rx = dp[0], ry = dp[1], rz = dp[2];
+  const float s = (rx * rx + ry * ry) + rz * rz;
+  const bool ok = s >= 0x1.0p-126f && s < __builtin_inff();
+  const uint64_t valid = __builtin_amdgcn_ballot_w64(ok);
+  GlslTap tap{};
+  if (valid) {  // wave-uniform
+    const int src = (int)__builtin_ctzll(valid);
+    const float sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rx), src));
+    const float sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ry), src));
+    const float sz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rz), src));
+    tap.d[0] = ok ? rx : sx;
+    tap.d[1] = ok ? ry : sy;
+    tap.d[2] = ok ? rz : sz;
+    uint32_t work = 0;
+    fragment<true, 0, SHADE ? kRay : kRayBare>(f, as_const(f.walls), as_const(f.balls), 0, 0, work,
+                                               false, &tap);
+  }
+  if (in) {  // an invalid ray: sphere -1, all-zero bytes elsewhere
+    if (a.pos) {
+      float* const o = a.pos + 3 * q;
+      o[0] = ok ? tap.pos[0] : 0.0f;
+      o[1] = ok ? tap.pos[1] : 0.0f;
+      o[2] = ok ? tap.pos[2] : 0.0f;
+    }
+    if (a.depth) a.depth[q] = ok ? tap.depth : 0.0f;
+    if (a.sphere) a.sphere[q] = ok ? tap.sphere : -1;
+    if (a.steps) a.steps[q] = ok ? tap.steps : 0;
+    if constexpr (SHADE) a.rgba[q] = ok ? tap.rgba : 0u;
+  }
+}
+
 }  // namespace
 
 long long glsl_tile_key(const GlslFrame& f, long long* tiles) {
@@ -535,13 +667,53 @@ long long glsl_tile_key(const GlslFrame& f, long long* tiles) {
   return (1ll << 62) | ((long long)(f.ss & 3) << 59) | ((long long)f.tiles_x << 28) | ty;
 }
 
-int launch_glsl(const GlslFrame& f, void* stream, void* done_event) {
+namespace {
+
+// The plane-writing kernels on the plain launch's grid: ordered (one wave per tile, the sorter in
+// front when prev_cost is set) or row-major (four tiles per workgroup).
+template <int SS>
+void launch_glsl_aux(const GlslFrame& f, const GlslAux& aux, long long tiles, void* stream,
+                     void* done_event) {
+  if (f.tile_cost)
+    hipExtLaunchKernelGGL(k_glsl_ordered_aux<SS>, dim3((unsigned)(tiles + (f.prev_cost ? 1 : 0))),
+                          dim3(64), 0, (hipStream_t)stream, nullptr, (hipEvent_t)done_event, 0, f,
+                          (int)tiles, aux);
+  else
+    hipExtLaunchKernelGGL(k_glsl_aux<SS>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0,
+                          (hipStream_t)stream, nullptr, (hipEvent_t)done_event, 0, f, aux);
+}
+
+}  // namespace
+
+int launch_glsl_rays(const GlslFrame& f, const GlslRays& rays, void* stream, void* done_event) {
+  if (!rays.dirs || rays.count < 1 || rays.count > 0x7fffffffLL) return -1;
+  if (!rays.pos && !rays.depth && !rays.sphere && !rays.steps && !rays.rgba) return -1;
+  if (rays.rgba && !f.mip) return -1;
+  const dim3 grid((unsigned)((rays.count + 63) / 64));
+  if (rays.rgba)
+    hipExtLaunchKernelGGL(k_glsl_cast_rays<true>, grid, dim3(64), 0, (hipStream_t)stream, nullptr,
+                          (hipEvent_t)done_event, 0, f, rays);
+  else
+    hipExtLaunchKernelGGL(k_glsl_cast_rays<false>, grid, dim3(64), 0, (hipStream_t)stream, nullptr,
+                          (hipEvent_t)done_event, 0, f, rays);
+  return hipGetLastError() != hipSuccess;
+}
+
+int launch_glsl(const GlslFrame& f, void* stream, void* done_event, const GlslAux* aux) {
   const int tiles_y = (f.rows + 7) / 8;
   const long long tiles = (long long)f.tiles_x * tiles_y;
   if (tiles == 0) return 0;
   if (f.ss < 0 || f.ss > 2) return -1;
   // whole S x S groups: the filter's cross-lane adds rely on it
   if (f.ss && ((f.width | f.row0 | f.rows) & ((1 << f.ss) - 1))) return -1;
+  if (aux) {  // the same grid, the plane-writing kernels
+    if (!aux->depth && !aux->sphere && !aux->steps) return -1;
+    if (f.tile_cost && tiles > 0x7ffffffeLL) return -1;
+    if (f.ss == 0) launch_glsl_aux<0>(f, *aux, tiles, stream, done_event);
+    else if (f.ss == 1) launch_glsl_aux<1>(f, *aux, tiles, stream, done_event);
+    else launch_glsl_aux<2>(f, *aux, tiles, stream, done_event);
+    return hipGetLastError() != hipSuccess;
+  }
   if (f.tile_cost) {  // adaptive tile order (the host linked this launch into its chain)
     if (tiles > 0x7ffffffeLL) return -1;
     if (f.ss) {

@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <vector>
 
@@ -128,6 +129,14 @@ struct sfrt_glsl {
   int* d_status = nullptr;
   uint32_t* d_frame = nullptr;
   size_t d_frame_px = 0;
+  // sfrt_glsl_draw_image_aux: per requested plane (depth, sphere, steps) a compact device plane,
+  // grown the way d_frame is (stream-ordered on `stream`)
+  uint32_t* d_aux[3] = {};
+  size_t d_aux_px[3] = {};
+  // Staging of sfrt_glsl_cast_rays (the host call): one device buffer holding a batch's
+  // directions and its requested outputs, grown on demand
+  uint8_t* d_rays = nullptr;
+  size_t d_rays_bytes = 0;
   sfrt::Relay relay;         // events recorded on callers' streams, relayed (sfrt_host.h)
   mutable std::mutex mu;
 
@@ -148,22 +157,28 @@ struct sfrt_glsl {
     relay.release();
     (void)hipFree(d_status);
     (void)hipFree(d_frame);
+    for (uint32_t* p : d_aux) (void)hipFree(p);
+    (void)hipFree(d_rays);
     if (stream) (void)hipStreamDestroy(stream);
   }
 
-  int validate() const {
+  // view: the uniforms only a frame reads (rotation, fov, size); a ray batch reads none of them
+  int validate(bool view = true) const {
     const sfrt_glsl_uniforms& v = u;
     if (v.sphere_count < 0 || v.light_count < 0 || v.all_spheres_count > SFRT_GLSL_MAX_SPHERES ||
         v.sphere_count + v.light_count > v.all_spheres_count)
       return SFRT_E_INVALID;
-    for (float c : {v.campos[0], v.campos[1], v.campos[2], v.rotation[0], v.rotation[1], v.fov[0],
-                    v.fov[1]})
+    for (float c : {v.campos[0], v.campos[1], v.campos[2]})
       if (!bounded(c)) return SFRT_E_INVALID;
-    if (!(v.size[0] > 0.0f && v.size[1] > 0.0f && bounded(v.size[0]) && bounded(v.size[1])))
-      return SFRT_E_INVALID;
-    // the `size` the supersampled fragments see
-    if (!bounded(v.size[0] * (float)(1 << ss)) || !bounded(v.size[1] * (float)(1 << ss)))
-      return SFRT_E_INVALID;
+    if (view) {
+      for (float c : {v.rotation[0], v.rotation[1], v.fov[0], v.fov[1]})
+        if (!bounded(c)) return SFRT_E_INVALID;
+      if (!(v.size[0] > 0.0f && v.size[1] > 0.0f && bounded(v.size[0]) && bounded(v.size[1])))
+        return SFRT_E_INVALID;
+      // the `size` the supersampled fragments see
+      if (!bounded(v.size[0] * (float)(1 << ss)) || !bounded(v.size[1] * (float)(1 << ss)))
+        return SFRT_E_INVALID;
+    }
     for (int k = 0; k < v.all_spheres_count; k++)
       for (int c = 0; c < 4; c++)
         if (!bounded(v.spheres[k][c]) || !bounded(v.uvs[k][c]) || !bounded(v.lights[k][c]))
@@ -171,10 +186,11 @@ struct sfrt_glsl {
     return SFRT_OK;
   }
 
-  // Frame record + per-draw tables on stream s (stream-ordered reuse).
-  int prepare(sfrt::GlslFrame& f, hipStream_t s) {
-    if (!d_mip) return SFRT_E_NO_TEXTURE;
-    int rc = validate();
+  // Frame record + per-draw tables on stream s (stream-ordered reuse).  frame false: for a ray
+  // batch that reads neither the view uniforms nor (textured false) the ground.
+  int prepare(sfrt::GlslFrame& f, hipStream_t s, bool frame = true, bool textured = true) {
+    if (textured && !d_mip) return SFRT_E_NO_TEXTURE;
+    int rc = validate(frame);
     if (rc) return rc;
     HIP_TRY(ground.before_read(s));  // a set_ground queued on another stream lands first
     std::memset(&f, 0, sizeof f);
@@ -205,8 +221,10 @@ struct sfrt_glsl {
     f.fov_y = v.fov[1];
     // size of the S * width x S * height target when supersampled (a power of two: exact)
     f.ss = ss;
-    f.hk = v.fov[0] / (v.size[0] * (float)(1 << ss)) * 2.0f;
-    f.vk = v.fov[1] / (v.size[1] * (float)(1 << ss)) * 2.0f;
+    if (frame) {
+      f.hk = v.fov[0] / (v.size[0] * (float)(1 << ss)) * 2.0f;
+      f.vk = v.fov[1] / (v.size[1] * (float)(1 << ss)) * 2.0f;
+    }
     f.sc = sc;
     f.lc = lc;
     f.all = all;
@@ -480,12 +498,29 @@ int sfrt_glsl_set_uniform_int(sfrt_glsl* g, const char* name, int value) {
   return SFRT_OK;
 }
 
-int sfrt_glsl_draw(sfrt_glsl* g, void* dev_pixels, int width, int height, int64_t pitch_bytes,
-                   int row0, int rows, void* hip_stream) {
+}  // extern "C"
+
+// sfrt_glsl_draw and sfrt_glsl_draw_aux (with_aux false for the plain call).
+static int draw_body(sfrt_glsl* g, void* dev_pixels, int width, int height, int64_t pitch_bytes,
+                     const sfrt_aux_planes* aux, bool with_aux, int row0, int rows,
+                     void* hip_stream) {
   if (!g || !dev_pixels || width <= 0 || height <= 0 || row0 < 0 || rows < 0 ||
       row0 + rows > height || pitch_bytes < (int64_t)width * 4 || pitch_bytes % 4 != 0 ||
       height >= (1 << 24) || width >= (1 << 24))
     return SFRT_E_INVALID;
+  sfrt::GlslAux a{};
+  if (with_aux) {
+    if (!aux || (!aux->depth && !aux->sphere && !aux->steps)) return SFRT_E_INVALID;
+    const auto pitch_ok = [&](const void* p, int64_t pitch) {
+      return !p || (pitch % 4 == 0 && pitch >= (int64_t)width * 4);
+    };
+    if (!pitch_ok(aux->depth, aux->depth_pitch_bytes) || !pitch_ok(aux->sphere, aux->sphere_pitch_bytes) ||
+        !pitch_ok(aux->steps, aux->steps_pitch_bytes))
+      return SFRT_E_INVALID;
+    a.depth = (float*)aux->depth; a.depth_pitch = aux->depth ? aux->depth_pitch_bytes / 4 : 0;
+    a.sphere = (int32_t*)aux->sphere; a.sphere_pitch = aux->sphere ? aux->sphere_pitch_bytes / 4 : 0;
+    a.steps = (int32_t*)aux->steps; a.steps_pitch = aux->steps ? aux->steps_pitch_bytes / 4 : 0;
+  }
   std::lock_guard<std::mutex> lk(g->mu);
   // supersampled: the fragments of the S * width x S * height target, gl_FragCoord exact below 2^24
   const int ss = g->ss;
@@ -504,6 +539,7 @@ int sfrt_glsl_draw(sfrt_glsl* g, void* dev_pixels, int width, int height, int64_
   f.out = (uint32_t*)dev_pixels;
   f.out_pitch = pitch_bytes / 4;
   long long tiles = 0;
+  // the same key with and without planes: an aux draw and a plain draw of one stream share a chain
   const long long key = g->tile_order_on ? sfrt::glsl_tile_key(f, &tiles) : 0;
   sfrt::TileSchedPtrs p;
   sfrt::TileSched& sched = g->scheds.chain[g->scheds.pick(s)];
@@ -513,16 +549,19 @@ int sfrt_glsl_draw(sfrt_glsl* g, void* dev_pixels, int width, int height, int64_
   f.prev_cost = p.prev_cost;
   f.next_order = p.next_order;
   f.cost_diff = p.cost_diff ? 1 : 0;
-  const bool queued = sfrt::launch_glsl(f, s, g->launch_event()) == 0;
+  const bool queued = sfrt::launch_glsl(f, s, g->launch_event(), with_aux ? &a : nullptr) == 0;
   HIP_TRY(sched.end(p, s, queued));
   if (!queued) return SFRT_E_HIP;
   HIP_TRY(g->launched(s));
   return SFRT_OK;
 }
 
-int sfrt_glsl_draw_image(sfrt_glsl* g, uint8_t* pixels, int width, int height) {
+// sfrt_glsl_draw_image and sfrt_glsl_draw_image_aux (planes null for the plain call): depth,
+// sphere, steps, host planes of width * height elements.
+static int draw_image_body(sfrt_glsl* g, uint8_t* pixels, void* const* planes, int width, int height) {
   if (!g || !pixels || width <= 0 || height <= 0 || height >= (1 << 24) || width >= (1 << 24))
     return SFRT_E_INVALID;
+  if (planes && !planes[0] && !planes[1] && !planes[2]) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(g->mu);
   const int ss = g->ss;  // supersampled: the sample grid; d_frame and the copy stay width x height
   if ((height << ss) >= (1 << 24) || (width << ss) >= (1 << 24)) return SFRT_E_INVALID;
@@ -535,6 +574,21 @@ int sfrt_glsl_draw_image(sfrt_glsl* g, uint8_t* pixels, int width, int height) {
     HIP_TRY(hipMallocAsync((void**)&g->d_frame, px * 4, g->stream));
     g->d_frame_px = px;
   }
+  for (int q = 0; planes && q < 3; q++) {  // compact planes beside the compact frame, as d_frame
+    if (!planes[q] || g->d_aux_px[q] >= px) continue;
+    if (g->d_aux[q]) HIP_TRY(hipFreeAsync(g->d_aux[q], g->stream));
+    g->d_aux[q] = nullptr;
+    g->d_aux_px[q] = 0;
+    HIP_TRY(hipMallocAsync((void**)&g->d_aux[q], px * 4, g->stream));
+    g->d_aux_px[q] = px;
+  }
+  sfrt::GlslAux a{};
+  if (planes) {
+    a.depth = planes[0] ? (float*)g->d_aux[0] : nullptr;
+    a.sphere = planes[1] ? (int32_t*)g->d_aux[1] : nullptr;
+    a.steps = planes[2] ? (int32_t*)g->d_aux[2] : nullptr;
+    a.depth_pitch = a.sphere_pitch = a.steps_pitch = width;
+  }
   sfrt::GlslFrame f;
   int rc = g->prepare(f, g->stream);
   if (rc) return rc;
@@ -545,10 +599,126 @@ int sfrt_glsl_draw_image(sfrt_glsl* g, uint8_t* pixels, int width, int height) {
   f.tiles_x = (f.width + 7) / 8;
   f.out = g->d_frame;
   f.out_pitch = width;
-  if (sfrt::launch_glsl(f, g->stream, g->launch_event())) return SFRT_E_HIP;
+  if (sfrt::launch_glsl(f, g->stream, g->launch_event(), planes ? &a : nullptr)) return SFRT_E_HIP;
   HIP_TRY(g->launched(g->stream));
   HIP_TRY(hipMemcpyAsync(pixels, g->d_frame, px * 4, hipMemcpyDeviceToHost, g->stream));
+  for (int q = 0; planes && q < 3; q++)
+    if (planes[q])
+      HIP_TRY(hipMemcpyAsync(planes[q], g->d_aux[q], px * 4, hipMemcpyDeviceToHost, g->stream));
   return g->read_status(g->stream);
+}
+
+// ---- batched ray queries (include/sfrt.h) ----
+namespace {
+
+bool aligned4(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if ((uintptr_t)p & 3u) return false;
+  return true;
+}
+
+// The argument checks the host and the device call share.
+int cast_rays_args(const sfrt_glsl* g, const float* dirs, int64_t count, const sfrt_ray_hits* out) {
+  if (!g || !dirs || !out || count < 0 || count > 0x7fffffffLL) return SFRT_E_INVALID;
+  if (!out->pos && !out->depth && !out->sphere && !out->steps && !out->rgba) return SFRT_E_INVALID;
+  if (!aligned4({dirs, out->pos, out->depth, out->sphere, out->steps, out->rgba})) return SFRT_E_INVALID;
+  return SFRT_OK;
+}
+
+// One launch of the ray-batch kernel on s with the shader's mutex held: the draw's snapshot of the
+// uniforms (prepare: the staged tables, the per-campos host terms) and nothing of the view, the
+// options or the tile-order chains.
+int cast_rays_launch(sfrt_glsl* g, const float* dev_dirs, int64_t count, const sfrt_ray_hits& out,
+                     hipStream_t s) {
+  sfrt::GlslFrame f;
+  const int rc = g->prepare(f, s, false, out.rgba != nullptr);
+  if (rc) return rc;
+  sfrt::GlslRays a{};
+  a.dirs = dev_dirs;
+  a.count = count;
+  a.pos = out.pos;
+  a.depth = out.depth;
+  a.sphere = out.sphere;
+  a.steps = out.steps;
+  a.rgba = (uint32_t*)out.rgba;
+  if (sfrt::launch_glsl_rays(f, a, s, g->launch_event())) return SFRT_E_HIP;
+  HIP_TRY(g->launched(s));
+  return SFRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sfrt_glsl_draw(sfrt_glsl* g, void* dev_pixels, int width, int height, int64_t pitch_bytes,
+                   int row0, int rows, void* hip_stream) {
+  return draw_body(g, dev_pixels, width, height, pitch_bytes, nullptr, false, row0, rows, hip_stream);
+}
+
+int sfrt_glsl_draw_aux(sfrt_glsl* g, void* dev_pixels, int width, int height, int64_t pitch_bytes,
+                       const sfrt_aux_planes* aux, int row0, int rows, void* hip_stream) {
+  return draw_body(g, dev_pixels, width, height, pitch_bytes, aux, true, row0, rows, hip_stream);
+}
+
+int sfrt_glsl_draw_image(sfrt_glsl* g, uint8_t* pixels, int width, int height) {
+  return draw_image_body(g, pixels, nullptr, width, height);
+}
+
+int sfrt_glsl_draw_image_aux(sfrt_glsl* g, uint8_t* pixels, float* depth, int32_t* sphere,
+                             int32_t* steps, int width, int height) {
+  void* const planes[3] = {depth, sphere, steps};
+  return draw_image_body(g, pixels, planes, width, height);
+}
+
+int sfrt_glsl_cast_rays_device(sfrt_glsl* g, const float* dev_dirs, int64_t count,
+                               const sfrt_ray_hits* dev_out, void* hip_stream) {
+  const int rc = cast_rays_args(g, dev_dirs, count, dev_out);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g->mu);
+  if (count == 0) return SFRT_OK;
+  sfrt::DeviceGuard dg(g->device);
+  return cast_rays_launch(g, dev_dirs, count, *dev_out, (hipStream_t)hip_stream);
+}
+
+int sfrt_glsl_cast_rays(sfrt_glsl* g, const float* dirs, int64_t count, const sfrt_ray_hits* out) {
+  int rc = cast_rays_args(g, dirs, count, out);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g->mu);
+  if (count == 0) return SFRT_OK;
+  if (out->rgba && !g->d_mip) return SFRT_E_NO_TEXTURE;  // before anything is staged
+  if ((rc = g->validate(false))) return rc;
+  sfrt::DeviceGuard dg(g->device);
+  // The staging layout: dirs, then the requested outputs, 4-byte elements; one device buffer on
+  // the object's stream (the last host call waited for its own copies), grown on demand.
+  const size_t n = (size_t)count;
+  const size_t in_bytes = n * 12;
+  void* const host_out[5] = {out->pos, out->depth, out->sphere, out->steps, out->rgba};
+  const size_t elem[5] = {12, 4, 4, 4, 4};
+  size_t off[5] = {}, bytes = in_bytes;
+  for (int q = 0; q < 5; q++) {
+    off[q] = bytes;
+    if (host_out[q]) bytes += n * elem[q];
+  }
+  if (g->d_rays_bytes < bytes) {
+    if (g->d_rays) HIP_TRY(hipFreeAsync(g->d_rays, g->stream));
+    g->d_rays = nullptr;
+    g->d_rays_bytes = 0;
+    HIP_TRY(hipMallocAsync((void**)&g->d_rays, bytes, g->stream));
+    g->d_rays_bytes = bytes;
+  }
+  HIP_TRY(hipMemcpyAsync(g->d_rays, dirs, in_bytes, hipMemcpyHostToDevice, g->stream));
+  sfrt_ray_hits dev{};
+  dev.pos = host_out[0] ? (float*)(g->d_rays + off[0]) : nullptr;
+  dev.depth = host_out[1] ? (float*)(g->d_rays + off[1]) : nullptr;
+  dev.sphere = host_out[2] ? (int32_t*)(g->d_rays + off[2]) : nullptr;
+  dev.steps = host_out[3] ? (int32_t*)(g->d_rays + off[3]) : nullptr;
+  dev.rgba = host_out[4] ? g->d_rays + off[4] : nullptr;
+  if ((rc = cast_rays_launch(g, (const float*)g->d_rays, count, dev, g->stream))) return rc;
+  for (int q = 0; q < 5; q++)
+    if (host_out[q])
+      HIP_TRY(hipMemcpyAsync(host_out[q], g->d_rays + off[q], n * elem[q], hipMemcpyDeviceToHost,
+                             g->stream));
+  return g->read_status(g->stream);  // SFRT_E_MARCH_LIMIT: the outputs are written, as draw_image's
 }
 
 int sfrt_glsl_set_option(sfrt_glsl* g, int option, int value) {

@@ -1415,7 +1415,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 9; }
+int sfrt_version(void) { return 10; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

@@ -66,6 +66,8 @@ ABI_SYMBOLS = (
     "sfrt_voxel_render_band_aux", "sfrt_voxel_update_image_aux",
     "sfrt_voxel_cast_rays", "sfrt_voxel_cast_rays_device",
     "sfrt_voxel_cast_shadow_rays", "sfrt_voxel_cast_shadow_rays_device",
+    "sfrt_glsl_draw_aux", "sfrt_glsl_draw_image_aux",
+    "sfrt_glsl_cast_rays", "sfrt_glsl_cast_rays_device",
 )
 
 SFRT_MULTI_AUTO, SFRT_MULTI_RCCL, SFRT_MULTI_PEER = 0, 1, 2
@@ -230,6 +232,11 @@ def lib() -> ctypes.CDLL:
         "sfrt_glsl_set_uniform_int": ([vp, ctypes.c_char_p, c_int], c_int),
         "sfrt_glsl_draw": ([vp, vp, c_int, c_int, ctypes.c_int64, c_int, c_int, vp], c_int),
         "sfrt_glsl_draw_image": ([vp, vp, c_int, c_int], c_int),
+        "sfrt_glsl_draw_aux": ([vp, vp, c_int, c_int, ctypes.c_int64, P(AuxPlanes), c_int, c_int, vp],
+                               c_int),
+        "sfrt_glsl_draw_image_aux": ([vp, vp, vp, vp, vp, c_int, c_int], c_int),
+        "sfrt_glsl_cast_rays": ([vp, vp, ctypes.c_int64, P(RayHits)], c_int),
+        "sfrt_glsl_cast_rays_device": ([vp, vp, ctypes.c_int64, P(RayHits), vp], c_int),
         "sfrt_glsl_check": ([vp, vp], c_int),
         "sfrt_glsl_set_option": ([vp, c_int, c_int], c_int),
         "sfrt_glsl_get_option": ([vp, c_int, P(c_int)], c_int),
@@ -1049,6 +1056,72 @@ class GlslShader:
         _check(lib().sfrt_glsl_draw_image(self._h, out.ctypes.data, int(width), int(height)),
                "glsl_draw_image")
         return out
+
+    def draw_aux(self, dev_ptr: int, width: int, height: int, pitch_bytes: int, row0: int = 0,
+                 rows: int | None = None, stream: int = 0, depth=None, sphere=None,
+                 steps=None) -> None:
+        """draw plus the per-pixel planes (sfrt_glsl_draw_aux): depth (float32), sphere and steps
+        (int32), each None or a (device pointer, pitch in bytes) pair."""
+        rows = height - row0 if rows is None else rows
+        planes = AuxPlanes()
+        for name, plane in (("depth", depth), ("sphere", sphere), ("steps", steps)):
+            if plane is not None:
+                setattr(planes, name, int(plane[0]))
+                setattr(planes, name + "_pitch_bytes", int(plane[1]))
+        _check(lib().sfrt_glsl_draw_aux(self._h, ctypes.c_void_p(dev_ptr), int(width), int(height),
+                                        int(pitch_bytes), ctypes.byref(planes), int(row0),
+                                        int(rows), ctypes.c_void_p(stream or None)),
+               "glsl_draw_aux")
+
+    def draw_image_aux(self, width: int, height: int, depth: bool = True, sphere: bool = True,
+                       steps: bool = True) -> dict:
+        """draw_image plus the wanted planes (sfrt_glsl_draw_image_aux): {"rgba": uint8
+        (width*height*4,), "depth": float32 (height, width), "sphere", "steps": int32}."""
+        res = {"rgba": np.zeros(width * height * 4, dtype=np.uint8)}
+        for name, want, dtype in (("depth", depth, np.float32), ("sphere", sphere, np.int32),
+                                  ("steps", steps, np.int32)):
+            if want:
+                res[name] = np.zeros((height, width), dtype=dtype)
+        ptrs = [res[name].ctypes.data if name in res else None
+                for name in ("depth", "sphere", "steps")]
+        _check(lib().sfrt_glsl_draw_image_aux(self._h, res["rgba"].ctypes.data, *ptrs, int(width),
+                                              int(height)), "glsl_draw_image_aux")
+        return res
+
+    # --- ray queries ---
+    def cast_rays(self, dirs, outputs=RAY_OUTPUTS) -> dict:
+        """The shader's Raycast(campos, dir, 1) for a batch of caller-supplied directions
+        (sfrt_glsl_cast_rays); every ray starts at the campos uniform.
+
+        dirs: (N, 3) float32, un-normalised.  Returns {name: array} for the requested outputs:
+        pos (N, 3) float32, depth (N,) float32, sphere and steps (N,) int32, rgba (N, 4) uint8.
+        An invalid ray (non-finite component, zero / underflowing / overflowing length) has
+        sphere == -1 and zeros elsewhere."""
+        dirs = np.ascontiguousarray(np.asarray(dirs, dtype=np.float32).reshape(-1, 3))
+        n = dirs.shape[0]
+        shapes = {"pos": ((n, 3), np.float32), "depth": ((n,), np.float32),
+                  "sphere": ((n,), np.int32), "steps": ((n,), np.int32), "rgba": ((n, 4), np.uint8)}
+        res = {name: np.zeros(*shapes[name]) for name in outputs}
+        hits = RayHits()
+        for name, arr in res.items():
+            # an empty array's pointer still says "requested"
+            setattr(hits, name, arr.ctypes.data if n else 4)
+        _check(lib().sfrt_glsl_cast_rays(self._h, dirs.ctypes.data if n else 4, n,
+                                         ctypes.byref(hits)), "glsl_cast_rays")
+        return res
+
+    def cast_rays_device(self, dirs_ptr: int, count: int, stream: int = 0, pos=None, depth=None,
+                         sphere=None, steps=None, rgba=None) -> None:
+        """Asynchronous sfrt_glsl_cast_rays_device on `stream`: device pointers (ints) to count*3
+        float32 directions and to each wanted output; the status is left to check(stream)."""
+        hits = RayHits()
+        for name, ptr in zip(RAY_OUTPUTS, (pos, depth, sphere, steps, rgba)):
+            if ptr:
+                setattr(hits, name, int(ptr))
+        _check(lib().sfrt_glsl_cast_rays_device(self._h, ctypes.c_void_p(dirs_ptr or None),
+                                                int(count), ctypes.byref(hits),
+                                                ctypes.c_void_p(stream or None)),
+               "glsl_cast_rays_device")
 
     def check(self, stream: int = 0) -> None:
         _check(lib().sfrt_glsl_check(self._h, ctypes.c_void_p(stream or None)), "glsl_check")
