@@ -108,13 +108,24 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) { return wave_reduc
 // v_sqrt_f32 (within 1 ulp) corrected by the two fma residual tests that the
 // compiler's own correctly rounded lowering uses -- minus its tiny-input
 // rescaling and special-value selects, which these inputs never need.
+// That lowering picks q = (fma(-rm, r, x) <= 0 ? rm : r), then
+// (fma(-rp, r, x) > 0 ? rp : q), for r's neighbours rm = r - 1 ulp and
+// rp = r + 1 ulp: two compares into SGPR pairs and two selects.  Here
+// (sfrt_math.h sqrt_select) the same two residuals are taken negated,
+// hm = rm * r - x and hp = rp * r - x (exact before the one rounding, so
+// exactly the negations), and the result's bit
+// pattern is bits(rm) + sign(hm) + sign(hp): an fma whose exact sum is zero
+// returns +0 in round-to-nearest, so sign(hm) is set exactly when x > rm * r
+// (the first select keeps r) and sign(hp) exactly when x > rp * r (the second
+// takes rp), and the second implies the first.  8 VALU, no compare, no select.
+// The subtraction saturates, so x = +0 gives rm = r = +0 and both residuals
+// +0: +0.  x = +inf gives +inf (rm * r - x is this chip's NaN, sign set; hp
+// carries rp's own NaN pattern, sign clear).  Every pattern from 2^-96 to
+// +inf returns the bits of the select form (tests/native/sqrt_select_check.hip);
+// below 2^-96 the two differ where a residual is denormal, and x = -0 and NaN
+// return NaN patterns of their own.
 __device__ __forceinline__ float sqrt_cr_normal(float x) {
-  const float r = __builtin_amdgcn_sqrtf(x);
-  const float rm = sfrt_math::u2f(sfrt_math::f2u(r) - 1u);
-  const float rp = sfrt_math::u2f(sfrt_math::f2u(r) + 1u);
-  float q = __builtin_fmaf(-rm, r, x) <= 0.0f ? rm : r;
-  q = __builtin_fmaf(-rp, r, x) > 0.0f ? rp : q;
-  return q;
+  return sfrt_math::sqrt_select(x, __builtin_amdgcn_sqrtf(x));
 }
 
 // a / b, correctly rounded, for operands that need none of the hardware division's

@@ -166,10 +166,28 @@ SFRT_HD float asinf_tail_div(float a, float b) {
 #endif
 }
 
+// The correctly rounded sqrtf(x) chosen among r - 1 ulp, r and r + 1 ulp, for r within 1 ulp of
+// the root (x >= 2^-96, or +0 with r = +0): the bit pattern of rm = r - 1 ulp plus the sign bits
+// of the residuals rm * r - x and rp * r - x.  The argument is at sfrt_device.h sqrt_cr_normal,
+// which takes r from v_sqrt_f32; kept here so that a host program can drive the same lines with
+// every r (tests/native/sqrt_select_host_check.cpp).  The subtraction saturates at 0.
+SFRT_HD float sqrt_select(float x, float r) {
+  const uint32_t rb = f2u(r);
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t rmb = __builtin_elementwise_sub_sat(rb, 1u);  // v_sub_u32 ... clamp
+#else
+  const uint32_t rmb = rb - (rb != 0u ? 1u : 0u);
+#endif
+  const float hm = __builtin_fmaf(u2f(rmb), r, -x);
+  const float hp = __builtin_fmaf(u2f(rb + 1u), r, -x);
+  return u2f(rmb + (f2u(hm) >> 31) + (f2u(hp) >> 31));
+}
+
 // sqrtf(t) for e_asinf.c's t = (1 - |x|) / 2 in [2^-25, 0.25]: on the device the raw
 // v_sqrt_f32 corrected by the compiler's own two fma residual tests, without its rescaling
 // for arguments below 2^-96 and its special-value selects, which such t never need (the
-// same sequence as sfrt_device.h sqrt_cr_normal); `sqrtf` elsewhere.  Same bits.
+// two residuals of sfrt_device.h sqrt_cr_normal, which selects by their sign bits and
+// returns the same bits for such t); `sqrtf` elsewhere.  Same bits.
 SFRT_HD float asinf_sqrt(float t) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const float r = __builtin_amdgcn_sqrtf(t);
