@@ -127,16 +127,11 @@ struct sfrt_glsl {
   uint64_t u_version = 1, staged_version = 0;
   size_t staged_off[3] = {0, 0, 0};  // byte offsets of balls | pairs | mats in the staged slot
   int* d_status = nullptr;
-  uint32_t* d_frame = nullptr;
-  size_t d_frame_px = 0;
-  // sfrt_glsl_draw_image_aux: per requested plane (depth, sphere, steps) a compact device plane,
-  // grown the way d_frame is (stream-ordered on `stream`)
-  uint32_t* d_aux[3] = {};
-  size_t d_aux_px[3] = {};
-  // Staging of sfrt_glsl_cast_rays (the host call): one device buffer holding a batch's
-  // directions and its requested outputs, grown on demand
-  uint8_t* d_rays = nullptr;
-  size_t d_rays_bytes = 0;
+  // draw_image's device frame and, per requested plane of sfrt_glsl_draw_image_aux (depth, sphere,
+  // steps), a compact device plane; the staging of sfrt_glsl_cast_rays (the host call): a batch's
+  // directions and its requested outputs.  All on `stream` (sfrt_host.h DeviceBuf); the host side
+  // of each copy is the caller's pageable memory (left as it is).
+  sfrt::DeviceBuf d_frame, d_aux[3], d_rays;
   sfrt::Relay relay;         // events recorded on callers' streams, relayed (sfrt_host.h)
   mutable std::mutex mu;
 
@@ -156,9 +151,9 @@ struct sfrt_glsl {
     for (auto& t : slots) t.release();
     relay.release();
     (void)hipFree(d_status);
-    (void)hipFree(d_frame);
-    for (uint32_t* p : d_aux) (void)hipFree(p);
-    (void)hipFree(d_rays);
+    d_frame.release();
+    for (sfrt::DeviceBuf& p : d_aux) p.release();
+    d_rays.release();
     if (stream) (void)hipStreamDestroy(stream);
   }
 
@@ -268,7 +263,7 @@ struct sfrt_glsl {
     }
     if (staged_version == u_version && cur_slot >= 0) {  // launched() re-marks the slot
       HIP_TRY(slots[cur_slot].use_on(s));  // staged, or last read, on another stream: wait for it
-      fill_tables(f, (uint8_t*)slots[cur_slot].d, staged_off);
+      fill_tables(f, slots[cur_slot].d.ptr<uint8_t>(), staged_off);
       return SFRT_OK;
     }
     std::vector<sfrt::GlslBall> balls(nb > 0 ? nb : 1);
@@ -318,12 +313,12 @@ struct sfrt_glsl {
     sfrt::TableSlot& t = slots[next_slot];
     HIP_TRY(t.reclaim());
     HIP_TRY(t.grow(bytes, s));  // no wait on other streams (sfrt_host.h)
-    uint8_t* blob = (uint8_t*)t.h;
+    uint8_t* blob = t.h.ptr<uint8_t>();
     std::memcpy(blob, walls.data(), bw);
     std::memcpy(blob + bw, balls.data(), bb);
     std::memcpy(blob + bw + bb, pairs.data(), bp);
     std::memcpy(blob + bw + bb + bp, mats.data(), bm);
-    HIP_TRY(hipMemcpyAsync(t.d, blob, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(t.d.ptr(), blob, bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(t.staged(s));
     cur_slot = next_slot;
     next_slot = (next_slot + 1) % kSlots;
@@ -331,7 +326,7 @@ struct sfrt_glsl {
     staged_off[0] = bw;
     staged_off[1] = bw + bb;
     staged_off[2] = bw + bb + bp;
-    fill_tables(f, (uint8_t*)t.d, staged_off);
+    fill_tables(f, t.d.ptr<uint8_t>(), staged_off);
     return SFRT_OK;
   }
 
@@ -356,16 +351,9 @@ struct sfrt_glsl {
   void* launch_event() const { return slots[cur_slot].launch_event(); }
   hipError_t launched(hipStream_t s) { return slots[cur_slot].launched_with(s); }
 
-  // On s itself: hipMemcpy / hipMemset run on the null stream, which also waits for every blocking
-  // stream of the process (a caller's hipStreamCreate streams), not just s.
   int read_status(hipStream_t s) {
     int st = 0;
-    HIP_TRY(hipMemcpyAsync(&st, d_status, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (st) {
-      HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int), s));
-      HIP_TRY(hipStreamSynchronize(s));
-    }
+    HIP_TRY(sfrt::read_status(d_status, s, &st));
     return (st & 1) ? SFRT_E_MARCH_LIMIT : SFRT_OK;
   }
 };
@@ -511,15 +499,10 @@ static int draw_body(sfrt_glsl* g, void* dev_pixels, int width, int height, int6
   sfrt::GlslAux a{};
   if (with_aux) {
     if (!aux || (!aux->depth && !aux->sphere && !aux->steps)) return SFRT_E_INVALID;
-    const auto pitch_ok = [&](const void* p, int64_t pitch) {
-      return !p || (pitch % 4 == 0 && pitch >= (int64_t)width * 4);
-    };
-    if (!pitch_ok(aux->depth, aux->depth_pitch_bytes) || !pitch_ok(aux->sphere, aux->sphere_pitch_bytes) ||
-        !pitch_ok(aux->steps, aux->steps_pitch_bytes))
+    if (!sfrt::aux_plane(aux->depth, aux->depth_pitch_bytes, width, a.depth, a.depth_pitch) ||
+        !sfrt::aux_plane(aux->sphere, aux->sphere_pitch_bytes, width, a.sphere, a.sphere_pitch) ||
+        !sfrt::aux_plane(aux->steps, aux->steps_pitch_bytes, width, a.steps, a.steps_pitch))
       return SFRT_E_INVALID;
-    a.depth = (float*)aux->depth; a.depth_pitch = aux->depth ? aux->depth_pitch_bytes / 4 : 0;
-    a.sphere = (int32_t*)aux->sphere; a.sphere_pitch = aux->sphere ? aux->sphere_pitch_bytes / 4 : 0;
-    a.steps = (int32_t*)aux->steps; a.steps_pitch = aux->steps ? aux->steps_pitch_bytes / 4 : 0;
   }
   std::lock_guard<std::mutex> lk(g->mu);
   // supersampled: the fragments of the S * width x S * height target, gl_FragCoord exact below 2^24
@@ -544,11 +527,7 @@ static int draw_body(sfrt_glsl* g, void* dev_pixels, int width, int height, int6
   sfrt::TileSchedPtrs p;
   sfrt::TileSched& sched = g->scheds.chain[g->scheds.pick(s)];
   HIP_TRY(sched.begin(key, tiles, s, g->tile_order_on, p));
-  f.tile_order = p.tile_order;
-  f.tile_cost = p.tile_cost;
-  f.prev_cost = p.prev_cost;
-  f.next_order = p.next_order;
-  f.cost_diff = p.cost_diff ? 1 : 0;
+  p.link(f);
   const bool queued = sfrt::launch_glsl(f, s, g->launch_event(), with_aux ? &a : nullptr) == 0;
   HIP_TRY(sched.end(p, s, queued));
   if (!queued) return SFRT_E_HIP;
@@ -567,26 +546,15 @@ static int draw_image_body(sfrt_glsl* g, uint8_t* pixels, void* const* planes, i
   if ((height << ss) >= (1 << 24) || (width << ss) >= (1 << 24)) return SFRT_E_INVALID;
   sfrt::DeviceGuard dg(g->device);
   const size_t px = (size_t)width * height;
-  if (g->d_frame_px < px) {  // stream-ordered behind the last draw_image on the object's stream
-    if (g->d_frame) HIP_TRY(hipFreeAsync(g->d_frame, g->stream));
-    g->d_frame = nullptr;
-    g->d_frame_px = 0;
-    HIP_TRY(hipMallocAsync((void**)&g->d_frame, px * 4, g->stream));
-    g->d_frame_px = px;
-  }
-  for (int q = 0; planes && q < 3; q++) {  // compact planes beside the compact frame, as d_frame
-    if (!planes[q] || g->d_aux_px[q] >= px) continue;
-    if (g->d_aux[q]) HIP_TRY(hipFreeAsync(g->d_aux[q], g->stream));
-    g->d_aux[q] = nullptr;
-    g->d_aux_px[q] = 0;
-    HIP_TRY(hipMallocAsync((void**)&g->d_aux[q], px * 4, g->stream));
-    g->d_aux_px[q] = px;
-  }
+  // stream-ordered behind the last draw_image on the object's stream
+  HIP_TRY(g->d_frame.reserve(px * 4, g->stream));
+  for (int q = 0; planes && q < 3; q++)  // compact planes beside the compact frame
+    if (planes[q]) HIP_TRY(g->d_aux[q].reserve(px * 4, g->stream));
   sfrt::GlslAux a{};
   if (planes) {
-    a.depth = planes[0] ? (float*)g->d_aux[0] : nullptr;
-    a.sphere = planes[1] ? (int32_t*)g->d_aux[1] : nullptr;
-    a.steps = planes[2] ? (int32_t*)g->d_aux[2] : nullptr;
+    a.depth = planes[0] ? g->d_aux[0].ptr<float>() : nullptr;
+    a.sphere = planes[1] ? g->d_aux[1].ptr<int32_t>() : nullptr;
+    a.steps = planes[2] ? g->d_aux[2].ptr<int32_t>() : nullptr;
     a.depth_pitch = a.sphere_pitch = a.steps_pitch = width;
   }
   sfrt::GlslFrame f;
@@ -597,33 +565,19 @@ static int draw_image_body(sfrt_glsl* g, uint8_t* pixels, void* const* planes, i
   f.row0 = 0;
   f.rows = f.height;
   f.tiles_x = (f.width + 7) / 8;
-  f.out = g->d_frame;
+  f.out = g->d_frame.ptr<uint32_t>();
   f.out_pitch = width;
   if (sfrt::launch_glsl(f, g->stream, g->launch_event(), planes ? &a : nullptr)) return SFRT_E_HIP;
   HIP_TRY(g->launched(g->stream));
-  HIP_TRY(hipMemcpyAsync(pixels, g->d_frame, px * 4, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipMemcpyAsync(pixels, g->d_frame.ptr(), px * 4, hipMemcpyDeviceToHost, g->stream));
   for (int q = 0; planes && q < 3; q++)
     if (planes[q])
-      HIP_TRY(hipMemcpyAsync(planes[q], g->d_aux[q], px * 4, hipMemcpyDeviceToHost, g->stream));
+      HIP_TRY(hipMemcpyAsync(planes[q], g->d_aux[q].ptr(), px * 4, hipMemcpyDeviceToHost, g->stream));
   return g->read_status(g->stream);
 }
 
 // ---- batched ray queries (include/sfrt.h) ----
 namespace {
-
-bool aligned4(std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs)
-    if ((uintptr_t)p & 3u) return false;
-  return true;
-}
-
-// The argument checks the host and the device call share.
-int cast_rays_args(const sfrt_glsl* g, const float* dirs, int64_t count, const sfrt_ray_hits* out) {
-  if (!g || !dirs || !out || count < 0 || count > 0x7fffffffLL) return SFRT_E_INVALID;
-  if (!out->pos && !out->depth && !out->sphere && !out->steps && !out->rgba) return SFRT_E_INVALID;
-  if (!aligned4({dirs, out->pos, out->depth, out->sphere, out->steps, out->rgba})) return SFRT_E_INVALID;
-  return SFRT_OK;
-}
 
 // One launch of the ray-batch kernel on s with the shader's mutex held: the draw's snapshot of the
 // uniforms (prepare: the staged tables, the per-campos host terms) and nothing of the view, the
@@ -672,7 +626,7 @@ int sfrt_glsl_draw_image_aux(sfrt_glsl* g, uint8_t* pixels, float* depth, int32_
 
 int sfrt_glsl_cast_rays_device(sfrt_glsl* g, const float* dev_dirs, int64_t count,
                                const sfrt_ray_hits* dev_out, void* hip_stream) {
-  const int rc = cast_rays_args(g, dev_dirs, count, dev_out);
+  const int rc = sfrt::ray_hits_args(g, dev_dirs, nullptr, count, dev_out);
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(g->mu);
   if (count == 0) return SFRT_OK;
@@ -681,43 +635,28 @@ int sfrt_glsl_cast_rays_device(sfrt_glsl* g, const float* dev_dirs, int64_t coun
 }
 
 int sfrt_glsl_cast_rays(sfrt_glsl* g, const float* dirs, int64_t count, const sfrt_ray_hits* out) {
-  int rc = cast_rays_args(g, dirs, count, out);
+  int rc = sfrt::ray_hits_args(g, dirs, nullptr, count, out);
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(g->mu);
   if (count == 0) return SFRT_OK;
   if (out->rgba && !g->d_mip) return SFRT_E_NO_TEXTURE;  // before anything is staged
   if ((rc = g->validate(false))) return rc;
   sfrt::DeviceGuard dg(g->device);
-  // The staging layout: dirs, then the requested outputs, 4-byte elements; one device buffer on
-  // the object's stream (the last host call waited for its own copies), grown on demand.
-  const size_t n = (size_t)count;
-  const size_t in_bytes = n * 12;
-  void* const host_out[5] = {out->pos, out->depth, out->sphere, out->steps, out->rgba};
-  const size_t elem[5] = {12, 4, 4, 4, 4};
-  size_t off[5] = {}, bytes = in_bytes;
-  for (int q = 0; q < 5; q++) {
-    off[q] = bytes;
-    if (host_out[q]) bytes += n * elem[q];
-  }
-  if (g->d_rays_bytes < bytes) {
-    if (g->d_rays) HIP_TRY(hipFreeAsync(g->d_rays, g->stream));
-    g->d_rays = nullptr;
-    g->d_rays_bytes = 0;
-    HIP_TRY(hipMallocAsync((void**)&g->d_rays, bytes, g->stream));
-    g->d_rays_bytes = bytes;
-  }
-  HIP_TRY(hipMemcpyAsync(g->d_rays, dirs, in_bytes, hipMemcpyHostToDevice, g->stream));
-  sfrt_ray_hits dev{};
-  dev.pos = host_out[0] ? (float*)(g->d_rays + off[0]) : nullptr;
-  dev.depth = host_out[1] ? (float*)(g->d_rays + off[1]) : nullptr;
-  dev.sphere = host_out[2] ? (int32_t*)(g->d_rays + off[2]) : nullptr;
-  dev.steps = host_out[3] ? (int32_t*)(g->d_rays + off[3]) : nullptr;
-  dev.rgba = host_out[4] ? g->d_rays + off[4] : nullptr;
-  if ((rc = cast_rays_launch(g, (const float*)g->d_rays, count, dev, g->stream))) return rc;
-  for (int q = 0; q < 5; q++)
-    if (host_out[q])
-      HIP_TRY(hipMemcpyAsync(host_out[q], g->d_rays + off[q], n * elem[q], hipMemcpyDeviceToHost,
-                             g->stream));
+  // The layout only: one device buffer on the object's stream (the last host call waited for its
+  // own copies), copied straight from and to the caller's memory.
+  const sfrt::BatchLayout l((size_t)count, {{dirs, 12}},
+                            {{out->pos, 12}, {out->depth, 4}, {out->sphere, 4}, {out->steps, 4},
+                             {out->rgba, 4}});
+  HIP_TRY(g->d_rays.reserve(l.bytes, g->stream));
+  void* const d = g->d_rays.ptr();
+  HIP_TRY(hipMemcpyAsync(d, dirs, l.in_bytes, hipMemcpyHostToDevice, g->stream));
+  const sfrt_ray_hits dev{l.out_at<float>(d, 0), l.out_at<float>(d, 1), l.out_at<int32_t>(d, 2),
+                          l.out_at<int32_t>(d, 3), l.out_at<uint8_t>(d, 4)};
+  if ((rc = cast_rays_launch(g, l.in_at<float>(d, 0), count, dev, g->stream))) return rc;
+  for (int q = 0; q < l.n_out; q++)
+    if (l.out[q].host)
+      HIP_TRY(hipMemcpyAsync((void*)l.out[q].host, l.out_at<uint8_t>(d, q), l.n * l.out[q].elem,
+                             hipMemcpyDeviceToHost, g->stream));
   return g->read_status(g->stream);  // SFRT_E_MARCH_LIMIT: the outputs are written, as draw_image's
 }
 

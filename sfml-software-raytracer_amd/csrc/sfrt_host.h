@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "sfrt.h"
+#include "sfrt_hostmem.h"
 
 namespace sfrt {
 
@@ -19,7 +20,10 @@ namespace sfrt {
 // while frames run -- per-frame tables, staging, device frames -- are stream-ordered device memory
 // (hipMallocAsync / hipFreeAsync behind the waits that make the old buffer idle), and a replaced
 // pinned host buffer is retired until its owner is destroyed (capacities grow geometrically, so the
-// retired bytes stay below the live ones).
+// retired bytes stay below twice the live ones).  DeviceBuf and PinnedBuf below are that rule's one
+// implementation: both are CacheBuf (sfrt_hostmem.h: keep if large enough, else
+// free, null, allocate) with the two ways to free and allocate; their release() is for the owner's
+// destructor, once the device has drained.
 struct RetiredHost {
   std::vector<void*> bufs;
   void add(void* h) {
@@ -30,10 +34,117 @@ struct RetiredHost {
     bufs.clear();
   }
 };
-inline size_t grown_capacity(size_t cap, size_t need) {
-  size_t c = cap > 256 ? cap : 256;
-  while (c < need) c += c / 2;
-  return c;
+
+// A device buffer grown in the order of the stream that last used it, to the exact size asked.
+struct DeviceBuf {
+  CacheBuf buf;
+  template <class T = void>
+  T* ptr() const { return (T*)buf.ptr; }
+  size_t bytes() const { return (size_t)buf.bytes; }
+  // fresh (optional): whether the buffer is a new one, its contents undefined.
+  hipError_t reserve(size_t need, hipStream_t s, bool* fresh = nullptr) {
+    if (fresh) *fresh = false;
+    if (need <= bytes()) return hipSuccess;
+    hipError_t e = hipSuccess;
+    const bool ok = buf.reserve(
+        (long long)need, [&](void* p) { return (e = hipFreeAsync(p, s)) == hipSuccess; },
+        [&](long long n) {
+          void* p = nullptr;
+          e = hipMallocAsync(&p, (size_t)n, s);
+          return e == hipSuccess ? p : nullptr;
+        });
+    if (fresh) *fresh = ok;
+    return ok ? hipSuccess : e;
+  }
+  void release() {
+    buf.release([](void* p) { return hipFree(p) == hipSuccess; });
+  }
+};
+
+// A pinned host buffer that retires what it replaces, grown geometrically.
+struct PinnedBuf {
+  CacheBuf buf;
+  template <class T = void>
+  T* ptr() const { return (T*)buf.ptr; }
+  size_t bytes() const { return (size_t)buf.bytes; }
+  hipError_t reserve(size_t need) {
+    if (need <= bytes()) return hipSuccess;
+    hipError_t e = hipSuccess;
+    const bool ok = buf.reserve(
+        (long long)grown_capacity(bytes(), need),
+        [&](void* p) {
+          retired.add(p);
+          return true;
+        },
+        [&](long long n) {
+          void* p = nullptr;
+          e = hipHostMalloc(&p, (size_t)n, hipHostMallocDefault);
+          return e == hipSuccess ? p : nullptr;
+        });
+    return ok ? hipSuccess : e;
+  }
+  void release() {
+    buf.release([](void* p) { return hipHostFree(p) == hipSuccess; });
+    retired.release();
+  }
+
+ private:
+  RetiredHost retired;
+};
+
+// The staging of a host ray batch (BatchLayout): one device and one pinned buffer, used on the
+// owner's stream s by synchronous calls (the last one waited for its own copies).
+struct BatchStage {
+  DeviceBuf d;
+  PinnedBuf h;
+  // Room for the batch in both, the caller's inputs staged and on their way to the device.
+  hipError_t upload(const BatchLayout& l, hipStream_t s) {
+    hipError_t e;
+    if ((e = d.reserve(l.bytes, s)) != hipSuccess || (e = h.reserve(l.bytes)) != hipSuccess) return e;
+    l.stage_inputs(h.ptr());
+    return hipMemcpyAsync(d.ptr(), h.ptr(), l.in_bytes, hipMemcpyHostToDevice, s);
+  }
+  // The outputs on their way back; once s has drained, l.copy_outputs(h.ptr()) hands them over.
+  hipError_t download(const BatchLayout& l, hipStream_t s) {
+    return hipMemcpyAsync(h.ptr<uint8_t>() + l.in_bytes, d.ptr<uint8_t>() + l.in_bytes,
+                          l.bytes - l.in_bytes, hipMemcpyDeviceToHost, s);
+  }
+  void release() {
+    d.release();
+    h.release();
+  }
+};
+
+// A renderer's status word: its bits, cleared once read.  On s itself: hipMemcpy / hipMemset run
+// on the null stream, which also waits for every blocking stream of the process (a caller's
+// hipStreamCreate streams), not just s.  Each object maps the bits to its own codes.
+inline hipError_t read_status(int* d_status, hipStream_t s, int* bits) {
+  hipError_t e;
+  *bits = 0;
+  if ((e = hipMemcpyAsync(bits, d_status, sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess || !*bits) return e;
+  if ((e = hipMemsetAsync(d_status, 0, sizeof(int), s)) != hipSuccess) return e;
+  return hipStreamSynchronize(s);
+}
+
+// The argument checks of a batch that answers into sfrt_ray_hits (the sphere world's and the GLSL
+// renderer's, host and device calls): the object, the count, at least one output, 4-byte alignment.
+inline int ray_hits_args(const void* obj, const float* dirs, const float* origins, int64_t count,
+                         const sfrt_ray_hits* out) {
+  if (!obj || !dirs || !out || count < 0 || count > 0x7fffffffLL) return SFRT_E_INVALID;
+  if (!out->pos && !out->depth && !out->sphere && !out->steps && !out->rgba) return SFRT_E_INVALID;
+  return aligned4({dirs, origins, out->pos, out->depth, out->sphere, out->steps, out->rgba})
+             ? SFRT_OK : SFRT_E_INVALID;
+}
+
+// One plane of sfrt_aux_planes / sfrt_voxel_aux_planes into a kernel's aux record: a plane that is
+// set needs a pitch that is a multiple of 4 and at least 4 * width; a null plane's pitch is ignored.
+template <class T, class P>
+bool aux_plane(void* plane, int64_t pitch_bytes, int width, T*& out, P& out_pitch) {
+  if (plane && (pitch_bytes % 4 != 0 || pitch_bytes < (int64_t)width * 4)) return false;
+  out = (T*)plane;
+  out_pitch = plane ? pitch_bytes / 4 : 0;
+  return true;
 }
 
 // Makes `dev` the calling thread's current HIP device for the guard's scope and
@@ -100,9 +211,8 @@ struct Relay {
 // tables before the staging copy landed and (2) the event it records afterwards still covers the
 // earlier users: restaging waits on it alone.
 struct TableSlot {
-  void* d = nullptr;
-  void* h = nullptr;
-  size_t cap = 0;
+  DeviceBuf d;
+  PinnedBuf h;
   hipEvent_t ev = nullptr;     // relayed (Relay): completes after every earlier user
   hipEvent_t stop = nullptr;   // the launch's own stop event, on the caller's stream
   hipStream_t last = nullptr;  // stream of the last user (compared only, valid while pending)
@@ -127,21 +237,13 @@ struct TableSlot {
   // After queuing a launch on s that reads the slot (use_on(s) came first).
   hipError_t launched(hipStream_t s) { return mark(s); }
   // Room for `bytes` (after reclaim(): every earlier user has finished), waiting for no other
-  // stream: the device tables reallocated in the order of s, the staging stream; the old pinned
-  // copy retired (RetiredHost).
+  // stream: the device tables reallocated in the order of s, the staging stream, at the pinned
+  // copy's geometric capacity (tables grow a little at a time: a sphere, a light more).
   hipError_t grow(size_t bytes, hipStream_t s) {
-    if (cap >= bytes) return hipSuccess;
-    const size_t c = grown_capacity(cap, bytes);
-    hipError_t e;
-    if (d && (e = hipFreeAsync(d, s)) != hipSuccess) return e;
-    d = nullptr;
-    retired.add(h);
-    h = nullptr;
-    cap = 0;
-    if ((e = hipMallocAsync(&d, c, s)) != hipSuccess) return e;
-    if ((e = hipHostMalloc(&h, c, hipHostMallocDefault)) != hipSuccess) return e;
-    cap = c;
-    return hipSuccess;
+    if (h.bytes() >= bytes) return hipSuccess;
+    const size_t c = grown_capacity(h.bytes(), bytes);  // (h.reserve(c) then allocates exactly c)
+    const hipError_t e = d.reserve(c, s);
+    return e != hipSuccess ? e : h.reserve(c);
   }
   // The same through the launch itself: the event to pass to the kernel launch as its stop event
   // (hipExtLaunchKernelGGL: the dispatch packet's own completion signal records it, so no marker
@@ -156,19 +258,15 @@ struct TableSlot {
     return hipSuccess;
   }
   void release() {
-    (void)hipFree(d);
-    (void)hipHostFree(h);
-    retired.release();
+    d.release();
+    h.release();
     if (ev) (void)hipEventDestroy(ev);
     if (stop) (void)hipEventDestroy(stop);
-    d = h = nullptr;
     ev = stop = nullptr;
-    cap = 0;
     pending = false;
   }
 
  private:
-  RetiredHost retired;
   hipError_t mark(hipStream_t s) {
     const hipError_t e = relay->record(s, ev);
     if (e != hipSuccess) return e;
@@ -243,8 +341,7 @@ struct SharedBuffer {
 // only after its last device copy has run (a host wait on that copy alone, never on the device).
 // The copy runs on a stream the owner keeps alive (its own): `ev` is waited on later (Relay).
 struct PinnedStage {
-  void* h = nullptr;
-  size_t cap = 0;
+  PinnedBuf h;
   hipEvent_t ev = nullptr;
   bool pending = false;
 
@@ -261,16 +358,9 @@ struct PinnedStage {
       if ((e = hipEventSynchronize(ev)) != hipSuccess) return e;
       pending = false;
     }
-    if (cap < bytes) {  // the old buffer retired, not freed (RetiredHost)
-      const size_t c = grown_capacity(cap, bytes);
-      retired.add(h);
-      h = nullptr;
-      cap = 0;
-      if ((e = hipHostMalloc(&h, c, hipHostMallocDefault)) != hipSuccess) return e;
-      cap = c;
-    }
+    if ((e = h.reserve(bytes)) != hipSuccess) return e;
     if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
-    *out = h;
+    *out = h.ptr();
     return hipSuccess;
   }
   // After the device copy from the staging buffer was queued on s.
@@ -280,17 +370,11 @@ struct PinnedStage {
     return e;
   }
   void release() {
-    (void)hipHostFree(h);
-    retired.release();
+    h.release();
     if (ev) (void)hipEventDestroy(ev);
-    h = nullptr;
     ev = nullptr;
-    cap = 0;
     pending = false;
   }
-
- private:
-  RetiredHost retired;
 };
 
 }  // namespace sfrt

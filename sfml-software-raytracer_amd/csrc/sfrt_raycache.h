@@ -7,11 +7,14 @@
 // (sphere_trace.hip: k_ray_fill, the CACHED kernels).  This header decides when; it makes no
 // HIP call, so the policy is tested on the host (tests/native/raycache_check.cpp).  The tile
 // records (TileRec, below) are filled, read and dropped by the same decisions; their layout and
-// the chain's buffer bookkeeping (CacheBuf) are tested in tests/native/tilerec_check.cpp.
+// the chain's buffer bookkeeping (sfrt_hostmem.h CacheBuf) are tested in
+// tests/native/tilerec_check.cpp.
 #pragma once
 
 #include <cstdint>
 #include <cstring>
+
+#include "sfrt_hostmem.h"  // CacheBuf: a chain's two buffers, for every user of this header
 
 namespace sfrt {
 
@@ -61,36 +64,6 @@ static_assert(sizeof(TileRec) == 32 && alignof(TileRec) == 32, "one s_load_dword
 // kept and dropped with them -- and are not counted against SFRT_OPT_RAY_CACHE_MB (0.3 % of
 // the directions' size at four pixels per lane, 1 % at one).
 inline long long tile_rec_bytes(long long tiles) { return tiles * (long long)sizeof(TileRec); }
-
-// One grow-only device buffer of a chain's cache and its size, without a HIP call of its own:
-// the caller passes how to free and how to allocate (sfrt_world.cpp: stream-ordered, on the
-// chain's stream; tests/native/tilerec_check.cpp: counters).
-struct CacheBuf {
-  void* ptr = nullptr;
-  long long bytes = 0;
-
-  // Room for `need` bytes: a buffer that is large enough stays (its contents too), a smaller
-  // one is freed (free_fn(ptr) -> bool) and replaced (alloc_fn(need) -> pointer or null).
-  // false: the buffer may be gone (bytes == 0) and nothing may be read from it.
-  template <class Free, class Alloc>
-  bool reserve(long long need, Free&& free_fn, Alloc&& alloc_fn) {
-    if (need <= 0) return false;
-    if (need <= bytes) return true;
-    if (ptr && !free_fn(ptr)) return false;
-    ptr = nullptr;
-    bytes = 0;
-    ptr = alloc_fn(need);
-    if (!ptr) return false;
-    bytes = need;
-    return true;
-  }
-  template <class Free>
-  void release(Free&& free_fn) {
-    if (ptr) (void)free_fn(ptr);
-    ptr = nullptr;
-    bytes = 0;
-  }
-};
 
 enum class RayAction {
   kTrace,  // today's kernel; the cache is neither read nor written

@@ -16,6 +16,7 @@
 
 #include <cstdint>
 
+#include "sfrt_hostmem.h"
 #include "sfrt_raycache.h"
 
 namespace sfrt {
@@ -35,6 +36,16 @@ struct TileSchedPtrs {
   // tile_order's entries carry the classes now in tile_cost (the buffer they were sorted from,
   // untouched since): the launch stores only the classes that changed
   bool cost_diff = false;
+
+  // Into a renderer's frame record (FrameRec, VoxFrame, GlslFrame: the same five members).
+  template <class Frame>
+  void link(Frame& f) const {
+    f.tile_order = tile_order;
+    f.tile_cost = tile_cost;
+    f.prev_cost = prev_cost;
+    f.next_order = next_order;
+    f.cost_diff = cost_diff ? 1 : 0;
+  }
 };
 
 struct TileSched {

@@ -113,8 +113,7 @@ struct sfrt_voxel {
   // --- device resources ---
   hipStream_t stream = nullptr;
   DevTex tex[sfrt::kVoxSlots], dyn_tex[sfrt::kVoxSlots];
-  uint8_t* d_cells = nullptr;  // the key-indexed byte grid (voxel_trace.h, cell_hit)
-  size_t d_cells_cap = 0;
+  sfrt::DeviceBuf d_cells;  // the key-indexed byte grid (voxel_trace.h, cell_hit)
   // Every byte of d_cells outside planes x < box[0], rows y < box[1], columns z < box[2] is 0.
   int box[3] = {0, 0, 0};
   bool blocks_dirty = true;
@@ -123,15 +122,13 @@ struct sfrt_voxel {
   // do not wait on the host for the previous rewrite (which may sit behind other work on its
   // stream); an upload reuses a pair only after that pair's previous rewrite has run.
   struct CodeStage {
-    uint8_t* h = nullptr;
-    uint8_t* d = nullptr;
-    size_t cap = 0;
+    sfrt::PinnedBuf h;
+    sfrt::DeviceBuf d;
     hipEvent_t ev = nullptr;
     bool pending = false;
   };
   CodeStage stage[2];
   int stage_next = 0;
-  sfrt::RetiredHost retired_host;  // replaced pinned buffers (sfrt_host.h: hipHostFree waits for all)
   // d_cells' and the textures' rewrites ordered against their readers (sfrt_host.h)
   sfrt::SharedBuffer shared;
   sfrt::PinnedStage tex_stage;  // texture uploads from the caller's memory
@@ -150,21 +147,13 @@ struct sfrt_voxel {
   size_t staged_off[3] = {0, 0, 0};  // byte offsets of row | dyn | lights in the staged slot
   float staged_xmax = 0.0f;          // max finite |component| of the staged ray directions
   int* d_status = nullptr;
-  uint32_t* d_frame = nullptr;
-  size_t d_frame_px = 0;
-  // sfrt_voxel_update_image_aux: per requested plane (depth, cell, face, steps) a compact device
-  // plane, grown the way d_frame is (stream-ordered on `stream`), and its pinned staging (a
-  // replaced one retired, sfrt_host.h: no hipHostFree while frames run)
-  uint32_t* d_aux[4] = {};
-  size_t d_aux_px[4] = {};
-  uint32_t* h_aux[4] = {};
-  size_t h_aux_px[4] = {};
-  // Staging of sfrt_voxel_cast_rays and sfrt_voxel_cast_shadow_rays (the host calls): one device
-  // and one pinned buffer holding a batch's inputs and its requested outputs, grown on demand
-  uint8_t* d_rays = nullptr;
-  size_t d_rays_bytes = 0;
-  uint8_t* h_rays = nullptr;
-  size_t h_rays_bytes = 0;
+  // The host path (update_image): the compact subset's device buffer on `stream` and, per
+  // requested plane of sfrt_voxel_update_image_aux (depth, cell, face, steps), a compact device
+  // plane with its pinned staging (sfrt_host.h DeviceBuf, PinnedBuf)
+  sfrt::DeviceBuf d_frame, d_aux[4];
+  sfrt::PinnedBuf h_aux[4];
+  // Staging of sfrt_voxel_cast_rays and sfrt_voxel_cast_shadow_rays (the host calls)
+  sfrt::BatchStage ray_stage;
   int tile_order_on = 0;    // SFRT_OPT_TILE_ORDER: off by default here (slower)
   // SFRT_OPT_SUPERSAMPLE: log2 of the factor S (0, 1, 2).  S > 1: the frame's samples are the
   // pixels of World::UpdateImage at S * width x S * height (prepare() builds the tables for that
@@ -187,25 +176,23 @@ struct sfrt_voxel {
     for (auto& t : tex) (void)hipFree(t.d);
     for (auto& t : dyn_tex) (void)hipFree(t.d);
     (void)hipDeviceSynchronize();
-    (void)hipFree(d_cells);
+    d_cells.release();
     for (CodeStage& c : stage) {
-      (void)hipFree(c.d);
-      (void)hipHostFree(c.h);
+      c.d.release();
+      c.h.release();
       if (c.ev) (void)hipEventDestroy(c.ev);
     }
-    retired_host.release();
     shared.release();
     tex_stage.release();
     for (auto& t : slots) t.release();
     relay.release();
     (void)hipFree(d_status);
-    (void)hipFree(d_frame);
+    d_frame.release();
     for (int q = 0; q < 4; q++) {
-      (void)hipFree(d_aux[q]);
-      (void)hipHostFree(h_aux[q]);
+      d_aux[q].release();
+      h_aux[q].release();
     }
-    (void)hipFree(d_rays);
-    (void)hipHostFree(h_rays);
+    ray_stage.release();
     if (stream) (void)hipStreamDestroy(stream);
   }
 
@@ -235,7 +222,7 @@ struct sfrt_voxel {
       if (rc != SFRT_OK) return rc;
       HIP_TRY(shared.before_read(s));
       HIP_TRY(t.use_on(s));  // staged, or last read, on another stream: wait for it
-      fill_frame(f, (uint8_t*)t.d, staged_off);
+      fill_frame(f, t.d.ptr<uint8_t>(), staged_off);
       return SFRT_OK;
     }
     std::vector<float> col((size_t)W * 3), row((size_t)H * 2);
@@ -289,13 +276,13 @@ struct sfrt_voxel {
     sfrt::TableSlot& t = slots[next_slot];
     HIP_TRY(t.reclaim());
     HIP_TRY(t.grow(bytes, s));  // no wait on other streams (sfrt_host.h)
-    uint8_t* h = (uint8_t*)t.h;
+    uint8_t* h = t.h.ptr<uint8_t>();
     std::memcpy(h, col.data(), col.size() * sizeof(float));
     std::memcpy(h + b_col, row.data(), row.size() * sizeof(float));
     if (!vd.empty()) std::memcpy(h + b_col + b_row, vd.data(), vd.size() * sizeof(sfrt::VoxDyn));
     if (!vl.empty())
       std::memcpy(h + b_col + b_row + b_dyn, vl.data(), vl.size() * sizeof(sfrt::VoxLight));
-    HIP_TRY(hipMemcpyAsync(t.d, t.h, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(t.d.ptr(), h, bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(t.staged(s));
     cur_slot = next_slot;
     next_slot = (next_slot + 1) % kSlots;
@@ -307,7 +294,7 @@ struct sfrt_voxel {
     const int rc = blocks_upload(s);  // first: fill_frame reads d_cells
     if (rc != SFRT_OK) return rc;
     HIP_TRY(shared.before_read(s));
-    fill_frame(f, (uint8_t*)t.d, staged_off);
+    fill_frame(f, t.d.ptr<uint8_t>(), staged_off);
     return SFRT_OK;
   }
 
@@ -328,36 +315,29 @@ struct sfrt_voxel {
       c.pending = false;
     }
     HIP_TRY(shared.before_write(s, slots));
-    if (c.cap < n) {  // grows to the largest world seen (the pair is not in use: above)
+    HIP_TRY(c.h.reserve(n));
+    if (c.d.bytes() < n) {  // grows to the largest world seen (the pair is not in use: above)
       size_t cap = 1;
       while (cap < n) cap <<= 1;
-      retired_host.add(c.h);  // not hipHostFree: it would wait for the whole device
-      c.h = nullptr;
-      if (c.d) HIP_TRY(hipFreeAsync(c.d, s));
-      c.d = nullptr;
-      c.cap = 0;
-      HIP_TRY(hipHostMalloc(&c.h, cap, hipHostMallocDefault));
-      HIP_TRY(hipMallocAsync((void**)&c.d, cap, s));
-      c.cap = cap;
+      HIP_TRY(c.d.reserve(cap, s));
     }
     if (!c.ev) HIP_TRY(hipEventCreateWithFlags(&c.ev, hipEventDisableTiming));
     const size_t bytes = (size_t)nx << 20;
-    if (d_cells_cap < bytes) {  // a fresh grid (stream-ordered on s), all zero
-      if (d_cells) HIP_TRY(hipFreeAsync(d_cells, s));
-      d_cells = nullptr;
-      d_cells_cap = 0;
-      HIP_TRY(hipMallocAsync((void**)&d_cells, bytes, s));
-      d_cells_cap = bytes;
-      HIP_TRY(hipMemsetAsync(d_cells, 0, bytes, s));
+    bool fresh = false;
+    HIP_TRY(d_cells.reserve(bytes, s, &fresh));
+    if (fresh) {  // a fresh grid (stream-ordered on s), all zero
+      HIP_TRY(hipMemsetAsync(d_cells.ptr(), 0, bytes, s));
       box[0] = box[1] = box[2] = 0;
     }
+    uint8_t* codes = c.h.ptr<uint8_t>();
     for (size_t k = 0; k < n; k++)
-      c.h[k] = blocks[k] == sfrt::kVoxEmpty ? 0 : (uint8_t)(blocks[k] + sfrt::kVoxCellBias);
-    HIP_TRY(hipMemcpyAsync(c.d, c.h, n, hipMemcpyHostToDevice, s));
+      codes[k] = blocks[k] == sfrt::kVoxEmpty ? 0 : (uint8_t)(blocks[k] + sfrt::kVoxCellBias);
+    HIP_TRY(hipMemcpyAsync(c.d.ptr(), codes, n, hipMemcpyHostToDevice, s));
     // planes past the new nx are outside the kernel's buffer range, but a later, larger world
     // would see them: the box covers them too while they may hold codes
     const int bx = std::max(nx, box[0]), by = std::max(ny, box[1]), bz = std::max(nz, box[2]);
-    if (sfrt::launch_voxel_cells(d_cells, c.d, nx, ny, nz, bx, by, bz, s)) return SFRT_E_HIP;
+    if (sfrt::launch_voxel_cells(d_cells.ptr<uint8_t>(), c.d.ptr<uint8_t>(), nx, ny, nz, bx, by, bz, s))
+      return SFRT_E_HIP;
     HIP_TRY(relay.record(s, c.ev));  // s may be a caller's stream
     c.pending = true;
     stage_next ^= 1;
@@ -396,7 +376,7 @@ struct sfrt_voxel {
   void fill_frame(sfrt::VoxFrame& f, uint8_t* d, const size_t* off) {
     f.col = (const float*)d;
     f.row = (const float*)(d + off[0]);
-    f.cells = d_cells;
+    f.cells = d_cells.ptr<uint8_t>();
     f.cell_bytes = (uint32_t)nx << 20;
     f.dda_qlim = dda_qlim(f.cam, f.maxiter, staged_xmax);
     for (int k = 0; k < sfrt::kVoxSlots; k++) {
@@ -425,16 +405,9 @@ struct sfrt_voxel {
   void* launch_event() const { return slots[cur_slot].launch_event(); }
   hipError_t launched(hipStream_t s) { return slots[cur_slot].launched_with(s); }
 
-  // On s itself: hipMemcpy / hipMemset run on the null stream, which also waits for every blocking
-  // stream of the process (a caller's hipStreamCreate streams), not just s.
   int read_status(hipStream_t s) {
     int st = 0;
-    HIP_TRY(hipMemcpyAsync(&st, d_status, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (st) {
-      HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int), s));
-      HIP_TRY(hipStreamSynchronize(s));
-    }
+    HIP_TRY(sfrt::read_status(d_status, s, &st));
     return (st & 2) ? SFRT_E_TEXEL : SFRT_OK;
   }
 };
@@ -567,37 +540,19 @@ static int update_image_body(sfrt_voxel* v, uint8_t* pixels, void* const* planes
   if (!v->sample_grid_ok(sub_w, sub_h)) return SFRT_E_INVALID;
   sfrt::DeviceGuard g(v->device);
   const size_t px = (size_t)sub_w * sub_h;
-  if (v->d_frame_px < px) {  // the last update_image finished with it (it waits for its copy)
-    if (v->d_frame) HIP_TRY(hipFreeAsync(v->d_frame, v->stream));
-    v->d_frame = nullptr;
-    v->d_frame_px = 0;
-    HIP_TRY(hipMallocAsync((void**)&v->d_frame, px * 4, v->stream));
-    v->d_frame_px = px;
-  }
+  // the last update_image finished with the buffers (it waits for its copies)
+  HIP_TRY(v->d_frame.reserve(px * 4, v->stream));
+  for (int q = 0; planes && q < 4; q++)
+    if (planes[q]) {
+      HIP_TRY(v->d_aux[q].reserve(px * 4, v->stream));
+      HIP_TRY(v->h_aux[q].reserve(px * 4));
+    }
   sfrt::VoxAux aux{};
-  for (int q = 0; planes && q < 4; q++) {
-    if (!planes[q]) continue;
-    if (v->d_aux_px[q] < px) {  // as d_frame
-      if (v->d_aux[q]) HIP_TRY(hipFreeAsync(v->d_aux[q], v->stream));
-      v->d_aux[q] = nullptr;
-      v->d_aux_px[q] = 0;
-      HIP_TRY(hipMallocAsync((void**)&v->d_aux[q], px * 4, v->stream));
-      v->d_aux_px[q] = px;
-    }
-    if (v->h_aux_px[q] < px) {
-      const size_t cap = sfrt::grown_capacity(v->h_aux_px[q], px);
-      v->retired_host.add(v->h_aux[q]);  // not hipHostFree: it would wait for the whole device
-      v->h_aux[q] = nullptr;
-      v->h_aux_px[q] = 0;
-      HIP_TRY(hipHostMalloc((void**)&v->h_aux[q], cap * 4, hipHostMallocDefault));
-      v->h_aux_px[q] = cap;
-    }
-  }
   if (planes) {  // compact planes beside the compact frame
-    aux.depth = planes[0] ? (float*)v->d_aux[0] : nullptr;
-    aux.cell = planes[1] ? (int32_t*)v->d_aux[1] : nullptr;
-    aux.face = planes[2] ? (int32_t*)v->d_aux[2] : nullptr;
-    aux.steps = planes[3] ? (int32_t*)v->d_aux[3] : nullptr;
+    aux.depth = planes[0] ? v->d_aux[0].ptr<float>() : nullptr;
+    aux.cell = planes[1] ? v->d_aux[1].ptr<int32_t>() : nullptr;
+    aux.face = planes[2] ? v->d_aux[2].ptr<int32_t>() : nullptr;
+    aux.steps = planes[3] ? v->d_aux[3].ptr<int32_t>() : nullptr;
     aux.depth_pitch = aux.cell_pitch = aux.face_pitch = aux.steps_pitch = sub_w;
   }
   sfrt::VoxFrame f;
@@ -613,28 +568,24 @@ static int update_image_body(sfrt_voxel* v, uint8_t* pixels, void* const* planes
   f.sub_w = sub_w << ss;
   f.sub_row0 = 0;
   f.sub_rows = sub_h << ss;
-  f.out = v->d_frame;
+  f.out = v->d_frame.ptr<uint32_t>();
   f.out_pitch = sub_w;
   if (sfrt::launch_voxel(f, v->stream, v->launch_event(), planes ? &aux : nullptr)) return SFRT_E_HIP;
   HIP_TRY(v->launched(v->stream));
-  std::vector<uint32_t> stage(px);
-  HIP_TRY(hipMemcpyAsync(stage.data(), v->d_frame, px * 4, hipMemcpyDeviceToHost, v->stream));
+  std::vector<uint32_t> stage(px);  // pageable colour staging (left as it is)
+  HIP_TRY(hipMemcpyAsync(stage.data(), v->d_frame.ptr(), px * 4, hipMemcpyDeviceToHost, v->stream));
   for (int q = 0; planes && q < 4; q++)
     if (planes[q])
-      HIP_TRY(hipMemcpyAsync(v->h_aux[q], v->d_aux[q], px * 4, hipMemcpyDeviceToHost, v->stream));
+      HIP_TRY(hipMemcpyAsync(v->h_aux[q].ptr(), v->d_aux[q].ptr(), px * 4, hipMemcpyDeviceToHost,
+                             v->stream));
   rc = v->read_status(v->stream);
   if (rc) return rc;  // SFRT_E_TEXEL included: neither pixels nor any plane is written
-  const size_t W = (size_t)v->width;
-  const auto scatter = [&](const uint32_t* src, uint8_t* dst) {
-    for (int b = 0; b < sub_h; b++) {
-      const size_t j = (size_t)ystart + (size_t)b * yadd;
-      for (int a = 0; a < sub_w; a++)
-        std::memcpy(dst + (j * W + (size_t)xstart + (size_t)a * xadd) * 4, &src[(size_t)b * sub_w + a], 4);
-    }
+  const auto scatter = [&](const uint32_t* src, void* dst) {
+    sfrt::scatter_subset(src, (uint8_t*)dst, (size_t)v->width, sub_w, sub_h, xstart, xadd, ystart, yadd);
   };
   scatter(stage.data(), pixels);
   for (int q = 0; planes && q < 4; q++)
-    if (planes[q]) scatter(v->h_aux[q], (uint8_t*)planes[q]);
+    if (planes[q]) scatter(v->h_aux[q].ptr<uint32_t>(), planes[q]);
   return SFRT_OK;
 }
 
@@ -660,18 +611,12 @@ static int render_band_body(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes
   std::lock_guard<std::mutex> lk(v->mu);
   if (pitch_bytes < (int64_t)v->width * 4 || row0 + rows > v->height) return SFRT_E_INVALID;
   sfrt::VoxAux a{};
-  if (with_aux) {
-    const auto pitch_ok = [&](const void* p, int64_t pitch) {
-      return !p || (pitch % 4 == 0 && pitch >= (int64_t)v->width * 4);
-    };
-    if (!pitch_ok(aux->depth, aux->depth_pitch_bytes) || !pitch_ok(aux->cell, aux->cell_pitch_bytes) ||
-        !pitch_ok(aux->face, aux->face_pitch_bytes) || !pitch_ok(aux->steps, aux->steps_pitch_bytes))
-      return SFRT_E_INVALID;
-    a.depth = (float*)aux->depth; a.depth_pitch = aux->depth ? aux->depth_pitch_bytes / 4 : 0;
-    a.cell = (int32_t*)aux->cell; a.cell_pitch = aux->cell ? aux->cell_pitch_bytes / 4 : 0;
-    a.face = (int32_t*)aux->face; a.face_pitch = aux->face ? aux->face_pitch_bytes / 4 : 0;
-    a.steps = (int32_t*)aux->steps; a.steps_pitch = aux->steps ? aux->steps_pitch_bytes / 4 : 0;
-  }
+  if (with_aux &&
+      (!sfrt::aux_plane(aux->depth, aux->depth_pitch_bytes, v->width, a.depth, a.depth_pitch) ||
+       !sfrt::aux_plane(aux->cell, aux->cell_pitch_bytes, v->width, a.cell, a.cell_pitch) ||
+       !sfrt::aux_plane(aux->face, aux->face_pitch_bytes, v->width, a.face, a.face_pitch) ||
+       !sfrt::aux_plane(aux->steps, aux->steps_pitch_bytes, v->width, a.steps, a.steps_pitch)))
+    return SFRT_E_INVALID;
   if (rows == 0) return SFRT_OK;
   if (!v->sample_grid_ok(v->width, rows)) return SFRT_E_INVALID;
   sfrt::DeviceGuard g(v->device);
@@ -694,11 +639,7 @@ static int render_band_body(sfrt_voxel* v, void* dev_pixels, int64_t pitch_bytes
   sfrt::TileSchedPtrs p;
   sfrt::TileSched& sched = v->scheds.chain[v->scheds.pick(s)];
   HIP_TRY(sched.begin(key, tiles, s, v->tile_order_on, p));
-  f.tile_order = p.tile_order;
-  f.tile_cost = p.tile_cost;
-  f.prev_cost = p.prev_cost;
-  f.next_order = p.next_order;
-  f.cost_diff = p.cost_diff ? 1 : 0;
+  p.link(f);
   const bool queued = sfrt::launch_voxel(f, s, v->launch_event(), with_aux ? &a : nullptr) == 0;
   HIP_TRY(sched.end(p, s, queued));
   if (!queued) return SFRT_E_HIP;
@@ -721,19 +662,13 @@ namespace {
 
 static_assert(SFRT_VOXEL_MAX_SHADOW_DIST == sfrt::kVoxMaxShadowDist, "one bound, two headers");
 
-bool aligned4(std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs)
-    if ((uintptr_t)p & 3u) return false;
-  return true;
-}
-
 // The argument checks the host and the device call share; the world's own come with its mutex held.
 int cast_rays_args(const sfrt_voxel* v, const float* dirs, const float* yscales, const float* origins,
                    int64_t count, const sfrt_voxel_ray_hits* out) {
   if (!v || !dirs || !out || count < 0 || count > 0x7fffffffLL) return SFRT_E_INVALID;
   if (!out->pos && !out->depth && !out->cell && !out->face && !out->steps && !out->rgba)
     return SFRT_E_INVALID;
-  if (!aligned4({dirs, yscales, origins, out->pos, out->depth, out->cell, out->face, out->steps, out->rgba}))
+  if (!sfrt::aligned4({dirs, yscales, origins, out->pos, out->depth, out->cell, out->face, out->steps, out->rgba}))
     return SFRT_E_INVALID;
   return SFRT_OK;
 }
@@ -741,7 +676,7 @@ int shadow_rays_args(const sfrt_voxel* v, const float* origins, const float* dir
                      const float* max_dists, int64_t count, const int32_t* free_, const int32_t* steps) {
   if (!v || !origins || !dirs || !max_dists || count < 0 || count > 0x7fffffffLL) return SFRT_E_INVALID;
   if (!free_ && !steps) return SFRT_E_INVALID;
-  if (!aligned4({origins, dirs, max_dists, free_, steps})) return SFRT_E_INVALID;
+  if (!sfrt::aligned4({origins, dirs, max_dists, free_, steps})) return SFRT_E_INVALID;
   return SFRT_OK;
 }
 // What a batch needs of the world (mutex held), before anything is queued.
@@ -794,27 +729,6 @@ int shadow_rays_launch(sfrt_voxel* v, const float* dev_origins, const float* dev
   return SFRT_OK;
 }
 
-// The host calls' staging buffers at `bytes` or more.  Growth waits for no other stream, as
-// update_image's: the device buffer stream-ordered on the world's stream (the last host call
-// waited for its own copies), the old pinned one retired.
-int grow_rays(sfrt_voxel* v, size_t bytes) {
-  if (v->d_rays_bytes < bytes) {
-    if (v->d_rays) HIP_TRY(hipFreeAsync(v->d_rays, v->stream));
-    v->d_rays = nullptr;
-    v->d_rays_bytes = 0;
-    HIP_TRY(hipMallocAsync((void**)&v->d_rays, bytes, v->stream));
-    v->d_rays_bytes = bytes;
-  }
-  if (v->h_rays_bytes < bytes) {
-    v->retired_host.add(v->h_rays);
-    v->h_rays = nullptr;
-    v->h_rays_bytes = 0;
-    HIP_TRY(hipHostMalloc((void**)&v->h_rays, bytes, hipHostMallocDefault));
-    v->h_rays_bytes = bytes;
-  }
-  return SFRT_OK;
-}
-
 }  // namespace
 
 int sfrt_voxel_cast_rays_device(sfrt_voxel* v, const float* dev_dirs, const float* dev_yscales,
@@ -837,40 +751,20 @@ int sfrt_voxel_cast_rays(sfrt_voxel* v, const float* dirs, const float* yscales,
   if (count == 0) return SFRT_OK;
   if ((rc = rays_world(v))) return rc;
   sfrt::DeviceGuard g(v->device);
-  // The staging layout: dirs, yscales, origins, then the requested outputs, 4-byte elements.
-  const size_t n = (size_t)count;
-  const size_t off_ys = n * 12, off_org = off_ys + (yscales ? n * 4 : 0);
-  const size_t in_bytes = off_org + (origins ? n * 12 : 0);
-  void* const host_out[6] = {out->pos, out->depth, out->cell, out->face, out->steps, out->rgba};
-  const size_t elem[6] = {12, 4, 4, 4, 4, 4};
-  size_t off[6] = {}, bytes = in_bytes;
-  for (int q = 0; q < 6; q++) {
-    off[q] = bytes;
-    if (host_out[q]) bytes += n * elem[q];
-  }
-  if ((rc = grow_rays(v, bytes))) return rc;
-  std::memcpy(v->h_rays, dirs, n * 12);
-  if (yscales) std::memcpy(v->h_rays + off_ys, yscales, n * 4);
-  if (origins) std::memcpy(v->h_rays + off_org, origins, n * 12);
-  HIP_TRY(hipMemcpyAsync(v->d_rays, v->h_rays, in_bytes, hipMemcpyHostToDevice, v->stream));
-  sfrt_voxel_ray_hits dev{};
-  dev.pos = host_out[0] ? (float*)(v->d_rays + off[0]) : nullptr;
-  dev.depth = host_out[1] ? (float*)(v->d_rays + off[1]) : nullptr;
-  dev.cell = host_out[2] ? (int32_t*)(v->d_rays + off[2]) : nullptr;
-  dev.face = host_out[3] ? (int32_t*)(v->d_rays + off[3]) : nullptr;
-  dev.steps = host_out[4] ? (int32_t*)(v->d_rays + off[4]) : nullptr;
-  dev.rgba = host_out[5] ? v->d_rays + off[5] : nullptr;
-  if ((rc = cast_rays_launch(v, (const float*)v->d_rays,
-                             yscales ? (const float*)(v->d_rays + off_ys) : nullptr,
-                             origins ? (const float*)(v->d_rays + off_org) : nullptr, count, dev,
-                             v->stream)))
+  const sfrt::BatchLayout l((size_t)count, {{dirs, 12}, {yscales, 4}, {origins, 12}},
+                            {{out->pos, 12}, {out->depth, 4}, {out->cell, 4}, {out->face, 4},
+                             {out->steps, 4}, {out->rgba, 4}});
+  HIP_TRY(v->ray_stage.upload(l, v->stream));
+  void* const d = v->ray_stage.d.ptr();
+  const sfrt_voxel_ray_hits dev{l.out_at<float>(d, 0), l.out_at<float>(d, 1), l.out_at<int32_t>(d, 2),
+                                l.out_at<int32_t>(d, 3), l.out_at<int32_t>(d, 4), l.out_at<uint8_t>(d, 5)};
+  if ((rc = cast_rays_launch(v, l.in_at<float>(d, 0), l.in_at<float>(d, 1), l.in_at<float>(d, 2),
+                             count, dev, v->stream)))
     return rc;
-  HIP_TRY(hipMemcpyAsync(v->h_rays + in_bytes, v->d_rays + in_bytes, bytes - in_bytes,
-                         hipMemcpyDeviceToHost, v->stream));
+  HIP_TRY(v->ray_stage.download(l, v->stream));
   rc = v->read_status(v->stream);
   if (rc) return rc;  // SFRT_E_TEXEL included: no output is written, as sfrt_voxel_update_image_aux
-  for (int q = 0; q < 6; q++)
-    if (host_out[q]) std::memcpy(host_out[q], v->h_rays + off[q], n * elem[q]);
+  l.copy_outputs(v->ray_stage.h.ptr());
   return SFRT_OK;
 }
 
@@ -895,26 +789,16 @@ int sfrt_voxel_cast_shadow_rays(sfrt_voxel* v, const float* origins, const float
   if (count == 0) return SFRT_OK;
   if ((rc = rays_world(v))) return rc;
   sfrt::DeviceGuard g(v->device);
-  // origins, dirs, max_dists, then the requested outputs
-  const size_t n = (size_t)count;
-  const size_t in_bytes = n * 28;
-  const size_t off_free = in_bytes, off_steps = off_free + (free_ ? n * 4 : 0);
-  const size_t bytes = off_steps + (steps ? n * 4 : 0);
-  if ((rc = grow_rays(v, bytes))) return rc;
-  std::memcpy(v->h_rays, origins, n * 12);
-  std::memcpy(v->h_rays + n * 12, dirs, n * 12);
-  std::memcpy(v->h_rays + n * 24, max_dists, n * 4);
-  HIP_TRY(hipMemcpyAsync(v->d_rays, v->h_rays, in_bytes, hipMemcpyHostToDevice, v->stream));
-  if ((rc = shadow_rays_launch(v, (const float*)v->d_rays, (const float*)(v->d_rays + n * 12),
-                               (const float*)(v->d_rays + n * 24), count,
-                               free_ ? (int32_t*)(v->d_rays + off_free) : nullptr,
-                               steps ? (int32_t*)(v->d_rays + off_steps) : nullptr, v->stream)))
+  const sfrt::BatchLayout l((size_t)count, {{origins, 12}, {dirs, 12}, {max_dists, 4}},
+                            {{free_, 4}, {steps, 4}});
+  HIP_TRY(v->ray_stage.upload(l, v->stream));
+  void* const d = v->ray_stage.d.ptr();
+  if ((rc = shadow_rays_launch(v, l.in_at<float>(d, 0), l.in_at<float>(d, 1), l.in_at<float>(d, 2),
+                               count, l.out_at<int32_t>(d, 0), l.out_at<int32_t>(d, 1), v->stream)))
     return rc;
-  HIP_TRY(hipMemcpyAsync(v->h_rays + in_bytes, v->d_rays + in_bytes, bytes - in_bytes,
-                         hipMemcpyDeviceToHost, v->stream));
+  HIP_TRY(v->ray_stage.download(l, v->stream));
   HIP_TRY(hipStreamSynchronize(v->stream));  // no status: a shadow ray reads no texel
-  if (free_) std::memcpy(free_, v->h_rays + off_free, n * 4);
-  if (steps) std::memcpy(steps, v->h_rays + off_steps, n * 4);
+  l.copy_outputs(v->ray_stage.h.ptr());
   return SFRT_OK;
 }
 

@@ -168,28 +168,17 @@ struct sfrt_world {
   int d_spheres_cap = 0;
   int ring = 0;
   int staged = -1;  // slot staged for the launch being prepared, or -1
-  uint32_t* d_frame = nullptr;  // compact subset buffer for the host path
-  size_t d_frame_px = 0;
-  uint32_t* h_stage = nullptr;  // pinned D2H staging
-  size_t h_stage_px = 0;
-  // The same pair per plane of sfrt_world_update_image_aux (depth, sphere, steps), grown the
-  // same way by the first call that asks for the plane.
-  uint32_t* d_aux[3] = {};
-  size_t d_aux_px[3] = {};
-  uint32_t* h_aux[3] = {};
-  size_t h_aux_px[3] = {};
-  // Staging of sfrt_world_cast_rays (the host call): one device and one pinned buffer holding
-  // the batch's inputs and outputs back to back, grown like d_frame / h_stage.
-  uint8_t* d_rays = nullptr;
-  size_t d_rays_bytes = 0;
-  uint8_t* h_rays = nullptr;
-  size_t h_rays_bytes = 0;
-  sfrt::RetiredHost retired_host;  // replaced pinned buffers (sfrt_host.h)
+  // The host path (update_image): the compact subset's device buffer, on the world's stream, and
+  // its pinned D2H staging (sfrt_host.h DeviceBuf, PinnedBuf).  The same pair per plane of
+  // sfrt_world_update_image_aux (depth, sphere, steps), grown by the first call that asks for it.
+  sfrt::DeviceBuf d_frame, d_aux[3];
+  sfrt::PinnedBuf h_stage, h_aux[3];
+  sfrt::BatchStage ray_stage;  // staging of sfrt_world_cast_rays (the host call)
+  sfrt::RetiredHost retired_host;  // the record ring's replaced pinned buffers (sfrt_host.h)
   std::vector<void*> retired_device;  // replaced record rings, freed with the world
   // --- frame pipeline (display path): render k+1 while frame k is copied ---
   struct PipeSlot {
-    uint32_t* d_buf = nullptr;
-    size_t px = 0;
+    sfrt::DeviceBuf d_buf;  // the frame, stream-ordered on the world's stream
     hipEvent_t rendered = nullptr, copied = nullptr;
     int* d_status = nullptr;    // this frame's march/texel flags
     int* h_status = nullptr;    // pinned copy, valid once `copied` completes
@@ -206,7 +195,7 @@ struct sfrt_world {
     if (stream) (void)hipStreamSynchronize(stream);
     if (copy_stream) (void)hipStreamSynchronize(copy_stream);
     for (PipeSlot& p : pipe) {
-      (void)hipFree(p.d_buf);
+      p.d_buf.release();
       (void)hipFree(p.d_status);
       (void)hipHostFree(p.h_status);
       if (p.rendered) (void)hipEventDestroy(p.rendered);
@@ -228,14 +217,13 @@ struct sfrt_world {
       if (spheres_stop[k]) (void)hipEventDestroy(spheres_stop[k]);
     }
     relay.release();
-    (void)hipFree(d_frame);
-    (void)hipHostFree(h_stage);
+    d_frame.release();
+    h_stage.release();
     for (int q = 0; q < 3; q++) {
-      (void)hipFree(d_aux[q]);
-      (void)hipHostFree(h_aux[q]);
+      d_aux[q].release();
+      h_aux[q].release();
     }
-    (void)hipFree(d_rays);
-    (void)hipHostFree(h_rays);
+    ray_stage.release();
     retired_host.release();
     for (void* p : retired_device) (void)hipFree(p);
     if (stream) (void)hipStreamDestroy(stream);
@@ -421,11 +409,7 @@ struct sfrt_world {
     HIP_TRY(sched.begin(key, tiles, s, tile_order_on, p));
     if (sched.cap != cap0 && last_fill.chain == cur_chain)
       last_fill.valid = false;  // the cost buffers were reallocated
-    f.tile_order = p.tile_order;
-    f.tile_cost = p.tile_cost;
-    f.prev_cost = p.prev_cost;
-    f.next_order = p.next_order;
-    f.cost_diff = p.cost_diff ? 1 : 0;
+    p.link(f);
     // a moving camera: the recorded classes are a frame or two off
     f.order_dilate = p.prev_cost && chain_last.valid &&
                      std::memcmp(&chain_last.cam, &cam, sizeof cam) != 0;
@@ -559,16 +543,9 @@ struct sfrt_world {
   };
   ChainCam chain_cam[sfrt::TileChains::kChains];  // per chain
 
-  // On s itself: hipMemcpy / hipMemset run on the null stream, which also waits for every blocking
-  // stream of the process (a caller's hipStreamCreate streams), not just s.
   int read_status(hipStream_t s) {
     int st = 0;
-    HIP_TRY(hipMemcpyAsync(&st, d_status, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (st) {
-      HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int), s));
-      HIP_TRY(hipStreamSynchronize(s));
-    }
+    HIP_TRY(sfrt::read_status(d_status, s, &st));
     if (st & 1) return SFRT_E_MARCH_LIMIT;
     if (st & 2) return SFRT_E_TEXEL;
     return SFRT_OK;
@@ -932,29 +909,15 @@ static int update_image_body(sfrt_world* w, uint8_t* pixels, void* const* planes
   if (sub_w == 0 || sub_h == 0) return SFRT_OK;
   sfrt::DeviceGuard g(w->device);
   const size_t px = (size_t)sub_w * sub_h;
-  // Growth waits for no other stream (sfrt_host.h: hipFree / hipHostFree wait for the whole
-  // device): the device frame stream-ordered on the world's stream, behind the last update_image
-  // (which waited for its own copy); the old pinned staging retired.
-  const auto grow = [&](uint32_t*& dev, size_t& dev_px, uint32_t*& host, size_t& host_px) -> int {
-    if (dev_px < px) {
-      if (dev) HIP_TRY(hipFreeAsync(dev, w->stream));
-      dev = nullptr;
-      dev_px = 0;
-      HIP_TRY(hipMallocAsync((void**)&dev, px * 4, w->stream));
-      dev_px = px;
-    }
-    if (host_px < px) {
-      w->retired_host.add(host);
-      host = nullptr;
-      host_px = 0;
-      HIP_TRY(hipHostMalloc(&host, px * 4, hipHostMallocDefault));
-      host_px = px;
-    }
-    return SFRT_OK;
-  };
-  if ((rc = grow(w->d_frame, w->d_frame_px, w->h_stage, w->h_stage_px))) return rc;
+  // Growth waits for no other stream (sfrt_host.h): the device frame in the order of the world's
+  // stream, behind the last update_image (which waited for its own copy).
+  HIP_TRY(w->d_frame.reserve(px * 4, w->stream));
+  HIP_TRY(w->h_stage.reserve(px * 4));
   for (int q = 0; planes && q < 3; q++)
-    if (planes[q] && (rc = grow(w->d_aux[q], w->d_aux_px[q], w->h_aux[q], w->h_aux_px[q]))) return rc;
+    if (planes[q]) {
+      HIP_TRY(w->d_aux[q].reserve(px * 4, w->stream));
+      HIP_TRY(w->h_aux[q].reserve(px * 4));
+    }
   sfrt::FrameRec f;
   std::vector<sfrt::SphereRec> recs;
   // Supersampled (S = 1 << ss): S x S samples per addressed pixel, start and strides in samples
@@ -969,13 +932,13 @@ static int update_image_body(sfrt_world* w, uint8_t* pixels, void* const* planes
   f.sub_row0 = 0;
   f.sub_rows = sub_h << ss;
   f.tiles_x = (f.sub_w + sfrt::kTile - 1) / sfrt::kTile;
-  f.out = w->d_frame;
+  f.out = w->d_frame.ptr<uint32_t>();
   f.out_pitch = sub_w;
   sfrt::AuxArgs aux{};
   if (planes) {  // compact planes beside the compact frame
-    aux.depth = planes[0] ? (float*)w->d_aux[0] : nullptr;
-    aux.sphere = planes[1] ? (int32_t*)w->d_aux[1] : nullptr;
-    aux.steps = planes[2] ? (int32_t*)w->d_aux[2] : nullptr;
+    aux.depth = planes[0] ? w->d_aux[0].ptr<float>() : nullptr;
+    aux.sphere = planes[1] ? w->d_aux[1].ptr<int32_t>() : nullptr;
+    aux.steps = planes[2] ? w->d_aux[2].ptr<int32_t>() : nullptr;
     aux.depth_pitch = aux.sphere_pitch = aux.steps_pitch = sub_w;
   }
   if ((rc = w->launchable(f))) return rc;
@@ -985,31 +948,22 @@ static int update_image_body(sfrt_world* w, uint8_t* pixels, void* const* planes
                          planes ? &aux : nullptr))
     return SFRT_E_HIP;
   if ((rc = w->launched_with())) return rc;
-  HIP_TRY(hipMemcpyAsync(w->h_stage, w->d_frame, px * 4, hipMemcpyDeviceToHost, w->stream));
+  HIP_TRY(hipMemcpyAsync(w->h_stage.ptr(), w->d_frame.ptr(), px * 4, hipMemcpyDeviceToHost, w->stream));
   for (int q = 0; planes && q < 3; q++)
     if (planes[q])
-      HIP_TRY(hipMemcpyAsync(w->h_aux[q], w->d_aux[q], px * 4, hipMemcpyDeviceToHost, w->stream));
+      HIP_TRY(hipMemcpyAsync(w->h_aux[q].ptr(), w->d_aux[q].ptr(), px * 4, hipMemcpyDeviceToHost,
+                             w->stream));
   rc = w->read_status(w->stream);
   // the planes do not depend on the texel: a frame whose status is SFRT_E_TEXEL has them defined
   if (rc && !(planes && rc == SFRT_E_TEXEL)) return rc;
   // Scatter the subset into the caller's frame: only addressed pixels are written.
-  const size_t W = (size_t)w->width;
-  const auto scatter = [&](const uint32_t* stage, uint8_t* dst) {
-    for (int bb = 0; bb < sub_h; bb++) {
-      const size_t j = (size_t)ystart + (size_t)bb * yadd;
-      const uint32_t* src = stage + (size_t)bb * sub_w;
-      uint8_t* row = dst + j * W * 4;
-      if (xadd == 1) {
-        std::memcpy(row + (size_t)xstart * 4, src, (size_t)sub_w * 4);
-      } else {
-        for (int a = 0; a < sub_w; a++)
-          std::memcpy(row + ((size_t)xstart + (size_t)a * xadd) * 4, src + a, 4);
-      }
-    }
+  const auto scatter = [&](const sfrt::PinnedBuf& stage, void* dst) {
+    sfrt::scatter_subset(stage.ptr<uint32_t>(), (uint8_t*)dst, (size_t)w->width, sub_w, sub_h,
+                         xstart, xadd, ystart, yadd);
   };
   if (!rc) scatter(w->h_stage, pixels);
   for (int q = 0; planes && q < 3; q++)
-    if (planes[q]) scatter(w->h_aux[q], (uint8_t*)planes[q]);
+    if (planes[q]) scatter(w->h_aux[q], planes[q]);
   return rc;
 }
 
@@ -1035,18 +989,11 @@ static int render_band_body(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes
   if (rc) return rc;
   if (pitch_bytes < (int64_t)w->width * 4 || row0 + rows > w->height) return SFRT_E_INVALID;
   sfrt::AuxArgs a{};
-  if (with_aux) {
-    const auto pitch_ok = [&](const void* p, int64_t pitch) {
-      return !p || (pitch % 4 == 0 && pitch >= (int64_t)w->width * 4);
-    };
-    if (!pitch_ok(aux->depth, aux->depth_pitch_bytes) ||
-        !pitch_ok(aux->sphere, aux->sphere_pitch_bytes) ||
-        !pitch_ok(aux->steps, aux->steps_pitch_bytes))
-      return SFRT_E_INVALID;
-    a.depth = (float*)aux->depth; a.depth_pitch = aux->depth ? aux->depth_pitch_bytes / 4 : 0;
-    a.sphere = (int32_t*)aux->sphere; a.sphere_pitch = aux->sphere ? aux->sphere_pitch_bytes / 4 : 0;
-    a.steps = (int32_t*)aux->steps; a.steps_pitch = aux->steps ? aux->steps_pitch_bytes / 4 : 0;
-  }
+  if (with_aux &&
+      (!sfrt::aux_plane(aux->depth, aux->depth_pitch_bytes, w->width, a.depth, a.depth_pitch) ||
+       !sfrt::aux_plane(aux->sphere, aux->sphere_pitch_bytes, w->width, a.sphere, a.sphere_pitch) ||
+       !sfrt::aux_plane(aux->steps, aux->steps_pitch_bytes, w->width, a.steps, a.steps_pitch)))
+    return SFRT_E_INVALID;
   if (rows == 0) {
     w->last_fill.valid = false;  // the last fill covered no rows (sfrt_world_row_costs)
     return SFRT_OK;
@@ -1114,16 +1061,7 @@ static int cast_rays_launch(sfrt_world* w, const float* dev_dirs, const float* d
   return w->launched_with();
 }
 
-// The argument checks both calls share; the world's own come with its mutex held.
-static int cast_rays_args(const sfrt_world* w, const float* dirs, const float* origins,
-                          int64_t count, const sfrt_ray_hits* out) {
-  if (!w || !dirs || !out || count < 0 || count > 0x7fffffffLL) return SFRT_E_INVALID;
-  if (!out->pos && !out->depth && !out->sphere && !out->steps && !out->rgba) return SFRT_E_INVALID;
-  const void* const ptrs[7] = {dirs, origins, out->pos, out->depth, out->sphere, out->steps, out->rgba};
-  for (const void* p : ptrs)
-    if ((uintptr_t)p & 3u) return SFRT_E_INVALID;
-  return SFRT_OK;
-}
+// What a batch needs of the world (mutex held); the argument checks: sfrt_host.h ray_hits_args.
 static int cast_rays_world(const sfrt_world* w, bool rgba) {
   if (w->spheres.empty()) return SFRT_E_EMPTY;
   if ((int)w->spheres.size() > SFRT_MAX_SPHERES) return SFRT_E_TOO_MANY;
@@ -1136,7 +1074,7 @@ static int cast_rays_world(const sfrt_world* w, bool rgba) {
 
 int sfrt_world_cast_rays_device(sfrt_world* w, const float* dev_dirs, const float* dev_origins,
                                 int64_t count, const sfrt_ray_hits* dev_out, void* hip_stream) {
-  int rc = cast_rays_args(w, dev_dirs, dev_origins, count, dev_out);
+  int rc = sfrt::ray_hits_args(w, dev_dirs, dev_origins, count, dev_out);
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(w->mu);
   if (count == 0) return SFRT_OK;
@@ -1147,58 +1085,26 @@ int sfrt_world_cast_rays_device(sfrt_world* w, const float* dev_dirs, const floa
 
 int sfrt_world_cast_rays(sfrt_world* w, const float* dirs, const float* origins, int64_t count,
                          const sfrt_ray_hits* out) {
-  int rc = cast_rays_args(w, dirs, origins, count, out);
+  int rc = sfrt::ray_hits_args(w, dirs, origins, count, out);
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(w->mu);
   if (count == 0) return SFRT_OK;
   if ((rc = cast_rays_world(w, out->rgba != nullptr))) return rc;
   sfrt::DeviceGuard g(w->device);
-  // The staging layout: dirs, origins, then the requested outputs, 4-byte elements throughout.
-  const size_t n = (size_t)count;
-  const size_t in_bytes = n * 12 * (origins ? 2 : 1);
-  void* const host_out[5] = {out->pos, out->depth, out->sphere, out->steps, out->rgba};
-  const size_t elem[5] = {12, 4, 4, 4, 4};
-  size_t off[5] = {}, bytes = in_bytes;
-  for (int q = 0; q < 5; q++) {
-    off[q] = bytes;
-    if (host_out[q]) bytes += n * elem[q];
-  }
-  // Growth waits for no other stream, as update_image's: the device buffer stream-ordered on the
-  // world's stream (the last host call waited for its own copies), the old pinned one retired.
-  if (w->d_rays_bytes < bytes) {
-    if (w->d_rays) HIP_TRY(hipFreeAsync(w->d_rays, w->stream));
-    w->d_rays = nullptr;
-    w->d_rays_bytes = 0;
-    HIP_TRY(hipMallocAsync((void**)&w->d_rays, bytes, w->stream));
-    w->d_rays_bytes = bytes;
-  }
-  if (w->h_rays_bytes < bytes) {
-    w->retired_host.add(w->h_rays);
-    w->h_rays = nullptr;
-    w->h_rays_bytes = 0;
-    HIP_TRY(hipHostMalloc((void**)&w->h_rays, bytes, hipHostMallocDefault));
-    w->h_rays_bytes = bytes;
-  }
-  std::memcpy(w->h_rays, dirs, n * 12);
-  if (origins) std::memcpy(w->h_rays + n * 12, origins, n * 12);
-  HIP_TRY(hipMemcpyAsync(w->d_rays, w->h_rays, in_bytes, hipMemcpyHostToDevice, w->stream));
-  sfrt_ray_hits dev{};
-  dev.pos = host_out[0] ? (float*)(w->d_rays + off[0]) : nullptr;
-  dev.depth = host_out[1] ? (float*)(w->d_rays + off[1]) : nullptr;
-  dev.sphere = host_out[2] ? (int32_t*)(w->d_rays + off[2]) : nullptr;
-  dev.steps = host_out[3] ? (int32_t*)(w->d_rays + off[3]) : nullptr;
-  dev.rgba = host_out[4] ? w->d_rays + off[4] : nullptr;
-  if ((rc = cast_rays_launch(w, (const float*)w->d_rays,
-                             origins ? (const float*)(w->d_rays + n * 12) : nullptr, count, dev,
-                             w->stream)))
+  const sfrt::BatchLayout l((size_t)count, {{dirs, 12}, {origins, 12}},
+                            {{out->pos, 12}, {out->depth, 4}, {out->sphere, 4}, {out->steps, 4},
+                             {out->rgba, 4}});
+  HIP_TRY(w->ray_stage.upload(l, w->stream));
+  void* const d = w->ray_stage.d.ptr();
+  const sfrt_ray_hits dev{l.out_at<float>(d, 0), l.out_at<float>(d, 1), l.out_at<int32_t>(d, 2),
+                          l.out_at<int32_t>(d, 3), l.out_at<uint8_t>(d, 4)};
+  if ((rc = cast_rays_launch(w, l.in_at<float>(d, 0), l.in_at<float>(d, 1), count, dev, w->stream)))
     return rc;
-  HIP_TRY(hipMemcpyAsync(w->h_rays + in_bytes, w->d_rays + in_bytes, bytes - in_bytes,
-                         hipMemcpyDeviceToHost, w->stream));
+  HIP_TRY(w->ray_stage.download(l, w->stream));
   rc = w->read_status(w->stream);
-  // pos, depth, sphere and steps do not depend on the texel
+  // pos, depth, sphere and steps do not depend on the texel: all but rgba (output 4) are written
   if (rc && rc != SFRT_E_TEXEL) return rc;
-  for (int q = 0; q < 5; q++)
-    if (host_out[q] && !(rc && q == 4)) std::memcpy(host_out[q], w->h_rays + off[q], n * elem[q]);
+  l.copy_outputs(w->ray_stage.h.ptr(), rc ? 1u << 4 : 0u);
   return rc;
 }
 
@@ -1271,11 +1177,7 @@ int sfrt_world_trace_points(sfrt_world* w, const int32_t* ij, int count, sfrt_pi
         long long tiles = 0;
         const long long key = sfrt::trace_tile_key(f, &tiles);
         HIP_TRY(w->dump_sched.begin(key, tiles, w->stream, w->tile_order_on, p));
-        f.tile_order = p.tile_order;
-        f.tile_cost = p.tile_cost;
-        f.prev_cost = p.prev_cost;
-        f.next_order = p.next_order;
-        f.cost_diff = p.cost_diff ? 1 : 0;
+        p.link(f);
       }
       const bool queued = sfrt::launch_trace(f, recs.data(), w->stream, &dump) == 0;
       if (w->tile_order_on) HIP_TRY(w->dump_sched.end(p, w->stream, queued));
@@ -1324,13 +1226,9 @@ int sfrt_world_submit_frame(sfrt_world* w, uint8_t* pixels, int64_t* ticket) {
     HIP_TRY(hipHostMalloc(&slot.h_status, sizeof(int), hipHostMallocDefault));
   }
   const size_t px = (size_t)w->width * w->height;
-  if (slot.px < px) {  // stream-ordered: freed behind its last copy, no device-wide wait
+  if (slot.d_buf.bytes() < px * 4) {  // stream-ordered: freed behind its last copy
     if (slot.used) HIP_TRY(hipStreamWaitEvent(w->stream, slot.copied, 0));
-    if (slot.d_buf) HIP_TRY(hipFreeAsync(slot.d_buf, w->stream));
-    slot.d_buf = nullptr;
-    slot.px = 0;
-    HIP_TRY(hipMallocAsync(&slot.d_buf, px * 4, w->stream));
-    slot.px = px;
+    HIP_TRY(slot.d_buf.reserve(px * 4, w->stream));
   }
   // The slot's previous frame must have left d_buf before this render writes it.
   if (slot.used) HIP_TRY(hipStreamWaitEvent(w->stream, slot.copied, 0));
@@ -1344,7 +1242,7 @@ int sfrt_world_submit_frame(sfrt_world* w, uint8_t* pixels, int64_t* ticket) {
   f.sub_row0 = 0;
   f.sub_rows = w->height << ss;
   f.tiles_x = (f.sub_w + sfrt::kTile - 1) / sfrt::kTile;
-  f.out = slot.d_buf;
+  f.out = slot.d_buf.ptr<uint32_t>();
   f.out_pitch = w->width;
   f.status = slot.d_status;
   if ((rc = w->launchable(f))) return rc;
@@ -1358,7 +1256,7 @@ int sfrt_world_submit_frame(sfrt_world* w, uint8_t* pixels, int64_t* ticket) {
   if ((rc = w->launched_with())) return rc;
   HIP_TRY(hipEventRecord(slot.rendered, w->stream));
   HIP_TRY(hipStreamWaitEvent(w->copy_stream, slot.rendered, 0));
-  HIP_TRY(hipMemcpyAsync(pixels, slot.d_buf, px * 4, hipMemcpyDeviceToHost, w->copy_stream));
+  HIP_TRY(hipMemcpyAsync(pixels, slot.d_buf.ptr(), px * 4, hipMemcpyDeviceToHost, w->copy_stream));
   HIP_TRY(hipMemcpyAsync(slot.h_status, slot.d_status, sizeof(int), hipMemcpyDeviceToHost,
                          w->copy_stream));
   HIP_TRY(hipEventRecord(slot.copied, w->copy_stream));

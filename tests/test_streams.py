@@ -233,6 +233,127 @@ def test_growth_waits_for_no_other_stream(built, floor):
         g.close()
 
 
+def _world_frames(sfrt, floor, stack):
+    world = stack.enter_context(sfrt.World(0))
+    world.load_texture(*floor)
+
+    def frame(w, h):
+        world.set_scene(scenes.default10(), w, h)
+        return world.render_aux()  # update_image_aux, all three planes
+    return lambda: frame(320, 240), lambda: frame(640, 360)
+
+
+def _voxel_frames(aux):
+    def make(sfrt, floor, stack):
+        vw = stack.enter_context(sfrt.VoxelWorld(0))
+        vw.load_assets(*vs.load_textures(), vs.COLORS)
+        scene = vs.default_world((20.5, 2.2, 40.5), 1.0, 0.1)
+
+        def frame(w, h):
+            vw.set_scene(scene, w, h)
+            return vw.render_aux() if aux else (vw.render(),)  # update_image[_aux], four planes
+        return lambda: frame(160, 90), lambda: frame(320, 180)
+    return make
+
+
+def _glsl_frames(sfrt, floor, stack):
+    g = stack.enter_context(sfrt.GlslShader(0))
+    g.set_ground(*floor)
+
+    def frame(w, h):
+        g.set_uniforms(gs.default_uniforms(w, h, 0.3, 0.1, frames=20))
+        return tuple(g.draw_image_aux(w, h).values())
+    return lambda: frame(160, 90), lambda: frame(320, 180)
+
+
+def _rays(n, seed, center):
+    rng = np.random.default_rng(seed)
+    dirs = rng.standard_normal((n, 3)).astype(np.float32)
+    origins = (np.asarray(center, np.float32) + rng.uniform(-0.3, 0.3, (n, 3))).astype(np.float32)
+    return dirs, origins
+
+
+def _world_rays(own):
+    def make(sfrt, floor, stack):
+        world = stack.enter_context(sfrt.World(0))
+        world.load_texture(*floor)
+        sc = scenes.default10()
+        world.set_scene(sc, 320, 240)
+
+        def batch(n):
+            dirs, origins = _rays(n, 11, sc.cam_pos)
+            return tuple(world.cast_rays(dirs, origins if own else None).values())
+        return lambda: batch(64), lambda: batch(4096)
+    return make
+
+
+def _voxel_rays(kind):
+    def make(sfrt, floor, stack):
+        vw = stack.enter_context(sfrt.VoxelWorld(0))
+        vw.load_assets(*vs.load_textures(), vs.COLORS)
+        vw.set_scene(vs.default_world((20.5, 2.2, 40.5), 1.0, 0.1), 160, 90)
+
+        def batch(n):
+            dirs, origins = _rays(n, 12, (20.5, 2.2, 40.5))
+            if kind == "shadow":
+                dists = np.linspace(1.0, 16.0, n, dtype=np.float32)
+                return tuple(vw.cast_shadow_rays(origins, dirs, dists).values())
+            return tuple(vw.cast_rays(dirs, None, origins if kind == "own" else None).values())
+        return lambda: batch(64), lambda: batch(4096)
+    return make
+
+
+def _glsl_rays(sfrt, floor, stack):
+    g = stack.enter_context(sfrt.GlslShader(0))
+    g.set_ground(*floor)
+    g.set_uniforms(gs.default_uniforms(160, 90, 0.3, 0.1, frames=20))
+    return (lambda: tuple(g.cast_rays(_rays(64, 13, (0, 0, 0))[0]).values()),
+            lambda: tuple(g.cast_rays(_rays(4096, 13, (0, 0, 0))[0]).values()))
+
+
+HOST_GROWTH = {
+    "world_update_image_aux": _world_frames,
+    "voxel_update_image": _voxel_frames(False),
+    "voxel_update_image_aux": _voxel_frames(True),
+    "glsl_draw_image_aux": _glsl_frames,
+    "world_cast_rays_origins": _world_rays(True),
+    "world_cast_rays_camera": _world_rays(False),
+    "voxel_cast_rays_origins": _voxel_rays("own"),
+    "voxel_cast_rays_camera": _voxel_rays("camera"),
+    "voxel_cast_shadow_rays": _voxel_rays("shadow"),
+    "glsl_cast_rays": _glsl_rays,
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", sorted(HOST_GROWTH))
+def test_host_path_growth_waits_for_no_other_stream(built, floor, path):
+    """The synchronous host paths test_growth_waits_for_no_other_stream does not reach, by the
+    same scheme: the plane staging of update_image_aux (sphere, voxel) and draw_image_aux, the
+    voxel update_image's device frame, and the staging of the host ray batches (sphere and voxel,
+    with the caller's origins and from the camera; shadow; GLSL).  Each grows from a warm small
+    call to one more than 1.5x larger -- past the pinned buffers' geometric capacity -- with
+    ~50 ms of work queued on an unrelated stream: the call returns while that work is still
+    pending, and its results equal the same call repeated on an idle device."""
+    import contextlib
+    import sfrt
+    import torch
+    busy_stream = torch.cuda.Stream(priority=-1)  # (as in the test above)
+    with contextlib.ExitStack() as stack:
+        small, large = HOST_GROWTH[path](sfrt, floor, stack)
+        small()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(busy_stream):
+            torch.cuda._sleep(100_000_000)
+        got = large()
+        assert not busy_stream.query(), f"{path} waited for an unrelated stream"
+        torch.cuda.synchronize()
+        want = large()
+        assert len(got) == len(want) and len(got) > 0
+        for a, b in zip(got, want):
+            assert a.shape == b.shape and a.tobytes() == b.tobytes(), path
+
+
 @pytest.mark.gpu
 def test_destroyed_stream_is_forgotten(built, floor):
     """A caller may destroy a stream once its frames are done (HIP leaves work still queued on a
