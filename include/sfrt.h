@@ -170,6 +170,34 @@ SFRT_API int sfrt_world_update_image_aux(sfrt_world* w, uint8_t* pixels, float* 
                                          int32_t* sphere, int32_t* steps, int ystart, int yadd,
                                          int xstart, int xadd);
 
+/* ---- UpdateImage's pixel subsets in place in a device-resident frame ----
+ * sfrt_world_update_image for a frame that stays on the GPU between calls, as the reference's
+ * gameImage stays alive between its RenderThreads' UpdateImage(&gameImage, num, 8, cycle, 4)
+ * calls.  `dev_frame` is the WHOLE width x height frame in device memory on this world's device,
+ * row j at dev_frame + j * pitch_bytes.  The call writes the 4 bytes of every pixel
+ * {i = xstart + k*xadd < width} x {j = ystart + l*yadd < height} -- the bytes
+ * sfrt_world_update_image writes for the same arguments and state -- and no other byte: not the
+ * unaddressed pixels, not the padding past 4*width of a row.  The aux call writes the same
+ * elements of every non-NULL plane (whole-frame planes, each with its own pitch; the values of
+ * sfrt_world_update_image_aux) and nothing of a NULL one.
+ * Asynchronous on `hip_stream` with sfrt_world_render_band's stream semantics (NULL = the null
+ * stream, ordered behind the last texture upload, status through sfrt_world_check).
+ * SFRT_OPT_SUPERSAMPLE, SFRT_OPT_CULL and SFRT_OPT_RAYS_PER_LANE are honoured as
+ * sfrt_world_update_image honours them.  The launch is row-major and stands outside the
+ * adaptive tile order and the ray cache: it leaves sfrt_world_row_costs and
+ * sfrt_world_ray_cache_stats as they were.
+ * SFRT_E_INVALID, with nothing queued or written: a NULL world or frame, ystart < 0, xstart < 0,
+ * yadd <= 0, xadd <= 0, pitch_bytes not a multiple of 4 or below 4*width, and for the aux call
+ * render_band_aux's plane rules.  The arguments that need no world are checked first, then the
+ * world's own validation (SFRT_E_EMPTY, SFRT_E_NO_TEXTURE, ...: as for render_band), then the
+ * pitches against the world's width -- the same order in both worlds.  An
+ * empty subset (xstart >= width or ystart >= height) returns SFRT_OK with nothing queued. */
+SFRT_API int sfrt_world_render_subset(sfrt_world* w, void* dev_frame, int64_t pitch_bytes,
+                                      int ystart, int yadd, int xstart, int xadd, void* hip_stream);
+SFRT_API int sfrt_world_render_subset_aux(sfrt_world* w, void* dev_frame, int64_t pitch_bytes,
+                                          const sfrt_aux_planes* aux, int ystart, int yadd,
+                                          int xstart, int xadd, void* hip_stream);
+
 /* Estimated work per pixel row of the world's last frame fill that ran in the adaptive
  * tile order (sfrt_world_render_band, sfrt_world_submit_frame; SFRT_OPT_TILE_ORDER on):
  * *row0, *rows = the global rows it covered, costs[i] (i < *rows <= capacity) = the
@@ -564,6 +592,17 @@ SFRT_API int sfrt_voxel_render_band_aux(sfrt_voxel* v, void* dev_pixels, int64_t
 SFRT_API int sfrt_voxel_update_image_aux(sfrt_voxel* v, uint8_t* pixels, float* depth, int32_t* cell,
                                          int32_t* face, int32_t* steps, int ystart, int yadd,
                                          int xstart, int xadd);
+
+/* World::UpdateImage's pixel subsets in place in a device-resident frame: sfrt_world_render_subset
+ * for the voxel world, with the same semantics -- `dev_frame` is the whole width x height frame,
+ * only the addressed pixels' bytes (those of sfrt_voxel_update_image[_aux]) are written, in the
+ * colour and in every non-NULL whole-frame plane; asynchronous on `hip_stream`, status through
+ * sfrt_voxel_check; the same refusals; row-major, in no tile-order chain. */
+SFRT_API int sfrt_voxel_render_subset(sfrt_voxel* v, void* dev_frame, int64_t pitch_bytes,
+                                      int ystart, int yadd, int xstart, int xadd, void* hip_stream);
+SFRT_API int sfrt_voxel_render_subset_aux(sfrt_voxel* v, void* dev_frame, int64_t pitch_bytes,
+                                          const sfrt_voxel_aux_planes* aux, int ystart, int yadd,
+                                          int xstart, int xadd, void* hip_stream);
 
 /* ---- batched ray queries: World::Raycast (World.cpp:302-453) for caller-supplied rays ----
  * sfrt_voxel_cast_rays[_device] runs Raycast for ray q of a batch.  Line numbers are World.cpp's.

@@ -191,6 +191,34 @@ class SphereWorld {
     check(sfrt_world_render_band_aux(w_, dev_pixels, pitch_bytes, &aux, row0, rows, hip_stream),
           "render_band_aux");
   }
+  // UpdateImage's subset in place in a whole width x height frame that stays in device memory
+  // (sfrt.h sfrt_world_render_subset): only the addressed pixels are written; asynchronous on
+  // hip_stream.  The Aux call writes the same elements of the non-null whole-frame planes.
+  void UpdateImageDevice(void* dev_frame, int64_t pitch_bytes, short ystart, short yadd,
+                         short xstart, short xadd, void* hip_stream) {
+    push_state();
+    check(sfrt_world_render_subset(w_, dev_frame, pitch_bytes, ystart, yadd, xstart, xadd, hip_stream),
+          "render_subset");
+  }
+  void UpdateImageDeviceAux(void* dev_frame, int64_t pitch_bytes, const sfrt_aux_planes& aux,
+                            short ystart, short yadd, short xstart, short xadd, void* hip_stream) {
+    push_state();
+    check(sfrt_world_render_subset_aux(w_, dev_frame, pitch_bytes, &aux, ystart, yadd, xstart, xadd,
+                                       hip_stream),
+          "render_subset_aux");
+  }
+  // The reference's eight RenderThreads together (Source.cpp:17-28): each of the `cycles` steps
+  // fills the columns == cycle (mod fullCycles) of every row, one launch, then steps cycle back by
+  // one -- at fullCycles = 4 Source.cpp:23's (cycle + 3) % 4.  How many cycles a displayed frame
+  // gets (the reference's adaptive cyclesPerFrame) is the caller's choice.
+  int fullCycles = 4;
+  int cycle = 0;
+  void RenderCycles(void* dev_frame, int64_t pitch_bytes, int cycles, void* hip_stream) {
+    for (int k = 0; k < cycles; k++) {
+      UpdateImageDevice(dev_frame, pitch_bytes, 0, 1, (short)cycle, (short)fullCycles, hip_stream);
+      cycle = (cycle + fullCycles - 1) % fullCycles;
+    }
+  }
   // SphereWorld::Raycast (SphereWorld.cpp:355-382), the reference's own signature: r->dir is
   // the un-normalised direction, the ray starts at cam.pos; writes r->pos and r->c (r->dir is
   // left as given: the normalised copy lives in the kernel).  One ray per call, synchronous:
@@ -414,6 +442,29 @@ class VoxelWorld {
     push_state();
     check(sfrt_voxel_render_band_aux(v_, dev_pixels, pitch_bytes, &aux, row0, rows, hip_stream),
           "render_band_aux");
+  }
+  // UpdateImage's subset in place in a whole width x height device frame, and the RenderThreads'
+  // cycle over its column phases: as SphereWorld's (sfrt.h sfrt_voxel_render_subset).
+  void UpdateImageDevice(void* dev_frame, int64_t pitch_bytes, short ystart, short yadd,
+                         short xstart, short xadd, void* hip_stream) {
+    push_state();
+    check(sfrt_voxel_render_subset(v_, dev_frame, pitch_bytes, ystart, yadd, xstart, xadd, hip_stream),
+          "render_subset");
+  }
+  void UpdateImageDeviceAux(void* dev_frame, int64_t pitch_bytes, const sfrt_voxel_aux_planes& aux,
+                            short ystart, short yadd, short xstart, short xadd, void* hip_stream) {
+    push_state();
+    check(sfrt_voxel_render_subset_aux(v_, dev_frame, pitch_bytes, &aux, ystart, yadd, xstart, xadd,
+                                       hip_stream),
+          "render_subset_aux");
+  }
+  int fullCycles = 4;
+  int cycle = 0;
+  void RenderCycles(void* dev_frame, int64_t pitch_bytes, int cycles, void* hip_stream) {
+    for (int k = 0; k < cycles; k++) {
+      UpdateImageDevice(dev_frame, pitch_bytes, 0, 1, (short)cycle, (short)fullCycles, hip_stream);
+      cycle = (cycle + fullCycles - 1) % fullCycles;
+    }
   }
   // World::Raycast (World.cpp:302-453), the reference's own signature: r->dir verbatim (never
   // normalised), r->yscale, from cam.pos with the billboards; fills r->c and r->pos (where the

@@ -151,6 +151,10 @@ int launch_cast_rays(const FrameRec& f, const SphereRec* host_spheres, const Ray
 // sphere_trace.hip.  dump != nullptr: the DUMP instantiation of the kernel the table picks.
 // aux != nullptr (with at least one plane set): its AUX instantiation -- never with dump or
 // the ray cache.
+// place_xstride > 0 (sfrt_world_render_subset): the placing kernels -- the subset stored in place
+// in a whole frame, compact column a at element (a >> ss) * place_xstride of its row, f.out the
+// subset's first pixel and f.out_pitch (and aux's pitches) the elements between two subset rows;
+// a row-major launch only (no tile order, no ray cache, no dump), with or without aux.
 // done_event (hipEvent_t, may be null): recorded by the list kernel's own completion (its stop
 // event; the inline kernel, which reads no device records, takes none).
 // ray_cache, tile_recs (both null, or both set): the chain's ray cache and tile records, filled
@@ -160,7 +164,7 @@ int launch_cast_rays(const FrameRec& f, const SphereRec* host_spheres, const Ray
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump = nullptr, void* done_event = nullptr,
                  const float* ray_cache = nullptr, const TileRec* tile_recs = nullptr,
-                 const AuxArgs* aux = nullptr);
+                 const AuxArgs* aux = nullptr, int place_xstride = 0);
 // Fills ray_cache (ray_cache_bytes(tiles, rays) bytes, sfrt_raycache.h, of the grid
 // trace_tile_key names) with the primary directions of f's rays, tile-major, and tile_recs
 // (tile_rec_bytes(tiles) bytes) with the tiles' records.

@@ -657,6 +657,79 @@ int sfrt_voxel_render_band_aux(sfrt_voxel* v, void* dev_pixels, int64_t pitch_by
   return render_band_body(v, dev_pixels, pitch_bytes, aux, true, row0, rows, hip_stream);
 }
 
+// sfrt_voxel_render_subset and sfrt_voxel_render_subset_aux (with_aux false for the plain call):
+// update_image's subset walk, stored in place in the caller's whole device frame (the placing
+// kernels, voxel_trace.h launch_voxel) on the caller's stream; row-major, no tile-order chain.
+static int render_subset_body(sfrt_voxel* v, void* dev_frame, int64_t pitch_bytes,
+                              const sfrt_voxel_aux_planes* aux, bool with_aux, int ystart, int yadd,
+                              int xstart, int xadd, void* hip_stream) {
+  if (!v || !dev_frame || ystart < 0 || xstart < 0 || yadd <= 0 || xadd <= 0 || pitch_bytes % 4 != 0)
+    return SFRT_E_INVALID;
+  if (with_aux && (!aux || (!aux->depth && !aux->cell && !aux->face && !aux->steps)))
+    return SFRT_E_INVALID;
+  std::lock_guard<std::mutex> lk(v->mu);
+  // the world's own validation first, then the sizes that need the world's width: the order of
+  // sfrt_world_render_subset
+  if (v->blocks.empty()) return SFRT_E_EMPTY;
+  if (pitch_bytes < (int64_t)v->width * 4) return SFRT_E_INVALID;
+  sfrt::VoxAux a{};
+  if (with_aux &&
+      (!sfrt::aux_plane(aux->depth, aux->depth_pitch_bytes, v->width, a.depth, a.depth_pitch) ||
+       !sfrt::aux_plane(aux->cell, aux->cell_pitch_bytes, v->width, a.cell, a.cell_pitch) ||
+       !sfrt::aux_plane(aux->face, aux->face_pitch_bytes, v->width, a.face, a.face_pitch) ||
+       !sfrt::aux_plane(aux->steps, aux->steps_pitch_bytes, v->width, a.steps, a.steps_pitch)))
+    return SFRT_E_INVALID;
+  // 64-bit: a stride near INT_MAX is a valid one-pixel subset
+  const int sub_w = xstart < v->width ? (int)(((long long)v->width - xstart + xadd - 1) / xadd) : 0;
+  const int sub_h = ystart < v->height ? (int)(((long long)v->height - ystart + yadd - 1) / yadd) : 0;
+  if (sub_w == 0 || sub_h == 0) return SFRT_OK;
+  if (!v->sample_grid_ok(sub_w, sub_h)) return SFRT_E_INVALID;
+  sfrt::DeviceGuard g(v->device);
+  hipStream_t s = (hipStream_t)hip_stream;
+  sfrt::VoxFrame f;
+  int rc = v->prepare(f, s);
+  if (rc) return rc;
+  // the subset as update_image_body takes it (supersampled: in samples, a stride that addresses
+  // one pixel only not scaled)
+  const int ss = v->ss;
+  f.xstart = xstart << ss; f.xadd = (ss && sub_w == 1 ? 1 : xadd) << ss;
+  f.ystart = ystart << ss; f.yadd = (ss && sub_h == 1 ? 1 : yadd) << ss;
+  f.sub_w = sub_w << ss;
+  f.sub_row0 = 0;
+  f.sub_rows = sub_h << ss;
+  // Pixel (xstart + k xadd, ystart + l yadd) of the frame is output pixel (k, l) of the subset:
+  // base frame + ystart * pitch + xstart, row stride yadd * pitch, column stride xadd (elements).
+  // A subset of one column (row) never applies its stride, which is then passed as 1.
+  const long long pitch = pitch_bytes / 4;
+  const int col_stride = sub_w == 1 ? 1 : xadd;
+  const long long row_mul = sub_h == 1 ? 1 : yadd;
+  f.out = (uint32_t*)dev_frame + (long long)ystart * pitch + xstart;
+  f.out_pitch = row_mul * pitch;
+  if (with_aux) {
+    if (a.depth) a.depth += (long long)ystart * a.depth_pitch + xstart;
+    if (a.cell) a.cell += (long long)ystart * a.cell_pitch + xstart;
+    if (a.face) a.face += (long long)ystart * a.face_pitch + xstart;
+    if (a.steps) a.steps += (long long)ystart * a.steps_pitch + xstart;
+    a.depth_pitch *= row_mul; a.cell_pitch *= row_mul; a.face_pitch *= row_mul; a.steps_pitch *= row_mul;
+  }
+  if (sfrt::launch_voxel(f, s, v->launch_event(), with_aux ? &a : nullptr, col_stride)) return SFRT_E_HIP;
+  HIP_TRY(v->launched(s));
+  return SFRT_OK;
+}
+
+int sfrt_voxel_render_subset(sfrt_voxel* v, void* dev_frame, int64_t pitch_bytes, int ystart, int yadd,
+                             int xstart, int xadd, void* hip_stream) {
+  return render_subset_body(v, dev_frame, pitch_bytes, nullptr, false, ystart, yadd, xstart, xadd,
+                            hip_stream);
+}
+
+int sfrt_voxel_render_subset_aux(sfrt_voxel* v, void* dev_frame, int64_t pitch_bytes,
+                                 const sfrt_voxel_aux_planes* aux, int ystart, int yadd, int xstart,
+                                 int xadd, void* hip_stream) {
+  return render_subset_body(v, dev_frame, pitch_bytes, aux, true, ystart, yadd, xstart, xadd,
+                            hip_stream);
+}
+
 // ---- batched ray queries (include/sfrt.h) ----
 namespace {
 

@@ -1035,6 +1035,84 @@ int sfrt_world_render_band_aux(sfrt_world* w, void* dev_pixels, int64_t pitch_by
   return render_band_body(w, dev_pixels, pitch_bytes, aux, true, row0, rows, hip_stream);
 }
 
+// sfrt_world_render_subset and sfrt_world_render_subset_aux (with_aux false for the plain call):
+// update_image's subset walk and kernel table, stored in place in the caller's whole device frame
+// (the placing kernels, sfrt_trace.h launch_trace) on the caller's stream.  Like update_image's own
+// launch it is row-major and outside the tile-order chain: no sched_begin / sched_end, so the ray
+// cache, the tile records and the last fill (sfrt_world_row_costs) are left as they are.
+static int render_subset_body(sfrt_world* w, void* dev_frame, int64_t pitch_bytes,
+                              const sfrt_aux_planes* aux, bool with_aux, int ystart, int yadd,
+                              int xstart, int xadd, void* hip_stream) {
+  if (!w || !dev_frame || ystart < 0 || xstart < 0 || yadd <= 0 || xadd <= 0 || pitch_bytes % 4 != 0)
+    return SFRT_E_INVALID;
+  if (with_aux && (!aux || (!aux->depth && !aux->sphere && !aux->steps))) return SFRT_E_INVALID;
+  std::lock_guard<std::mutex> lk(w->mu);
+  int rc = w->validate();
+  if (rc) return rc;
+  if (pitch_bytes < (int64_t)w->width * 4) return SFRT_E_INVALID;
+  sfrt::AuxArgs a{};
+  if (with_aux &&
+      (!sfrt::aux_plane(aux->depth, aux->depth_pitch_bytes, w->width, a.depth, a.depth_pitch) ||
+       !sfrt::aux_plane(aux->sphere, aux->sphere_pitch_bytes, w->width, a.sphere, a.sphere_pitch) ||
+       !sfrt::aux_plane(aux->steps, aux->steps_pitch_bytes, w->width, a.steps, a.steps_pitch)))
+    return SFRT_E_INVALID;
+  // SphereWorld.cpp:94,97: i = xstart, xstart + xadd, ... < width (same for j); 64-bit: a
+  // stride near INT_MAX is a valid one-pixel subset
+  const int sub_w = xstart < w->width ? (int)(((long long)w->width - xstart + xadd - 1) / xadd) : 0;
+  const int sub_h = ystart < w->height ? (int)(((long long)w->height - ystart + yadd - 1) / yadd) : 0;
+  if (sub_w == 0 || sub_h == 0) return SFRT_OK;
+  sfrt::DeviceGuard g(w->device);
+  hipStream_t s = (hipStream_t)hip_stream;  // HIP convention: NULL = the null stream
+  sfrt::FrameRec f;
+  std::vector<sfrt::SphereRec> recs;
+  // the subset as update_image_body takes it (supersampled: in samples, a stride that addresses
+  // one pixel only not scaled)
+  const int ss = w->ss;
+  w->prepare(f, recs, ss);
+  f.xstart = xstart << ss; f.xadd = (ss && sub_w == 1 ? 1 : xadd) << ss;
+  f.ystart = ystart << ss; f.yadd = (ss && sub_h == 1 ? 1 : yadd) << ss;
+  f.sub_w = sub_w << ss;
+  f.sub_row0 = 0;
+  f.sub_rows = sub_h << ss;
+  f.tiles_x = (f.sub_w + sfrt::kTile - 1) / sfrt::kTile;
+  // Pixel (xstart + k xadd, ystart + l yadd) of the frame is output pixel (k, l) of the subset:
+  // base frame + ystart * pitch + xstart, row stride yadd * pitch, column stride xadd (elements).
+  // A subset of one column (row) never applies its stride, which is then passed as 1.
+  const long long pitch = pitch_bytes / 4;
+  const int col_stride = sub_w == 1 ? 1 : xadd;
+  const long long row_mul = sub_h == 1 ? 1 : yadd;
+  f.out = (uint32_t*)dev_frame + (long long)ystart * pitch + xstart;
+  f.out_pitch = row_mul * pitch;
+  if (with_aux) {
+    if (a.depth) a.depth += (long long)ystart * a.depth_pitch + xstart;
+    if (a.sphere) a.sphere += (long long)ystart * a.sphere_pitch + xstart;
+    if (a.steps) a.steps += (long long)ystart * a.steps_pitch + xstart;
+    a.depth_pitch *= row_mul; a.sphere_pitch *= row_mul; a.steps_pitch *= row_mul;
+  }
+  if ((rc = w->launchable(f))) return rc;
+  rc = w->stage_spheres(f, recs, s, false);
+  if (rc) return rc;
+  // after the last texture upload (queued on w->stream, where the other launches run)
+  HIP_TRY(w->tex_written.before_read(s));
+  if (sfrt::launch_trace(f, recs.data(), s, nullptr, w->ring_event(), nullptr, nullptr,
+                         with_aux ? &a : nullptr, col_stride))
+    return SFRT_E_HIP;
+  return w->launched_with();
+}
+
+int sfrt_world_render_subset(sfrt_world* w, void* dev_frame, int64_t pitch_bytes, int ystart,
+                             int yadd, int xstart, int xadd, void* hip_stream) {
+  return render_subset_body(w, dev_frame, pitch_bytes, nullptr, false, ystart, yadd, xstart, xadd,
+                            hip_stream);
+}
+
+int sfrt_world_render_subset_aux(sfrt_world* w, void* dev_frame, int64_t pitch_bytes,
+                                 const sfrt_aux_planes* aux, int ystart, int yadd, int xstart,
+                                 int xadd, void* hip_stream) {
+  return render_subset_body(w, dev_frame, pitch_bytes, aux, true, ystart, yadd, xstart, xadd,
+                            hip_stream);
+}
+
 // sfrt_world_cast_rays_device and, for the host call's staged copies, sfrt_world_cast_rays:
 // one launch of the ray-batch kernels on s with the world's mutex held.  The launch takes the
 // frame fill's immutable snapshot (records in the kernel arguments, or a ring slot with its
@@ -1313,7 +1391,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 10; }
+int sfrt_version(void) { return 11; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

@@ -756,13 +756,20 @@ __device__ __forceinline__ Rays<R> march_wave(const FrameRec& f, const SphereRec
 // one dword per non-null plane of `aux` (sfrt_trace.h AuxArgs): the hit distance shade_texel
 // computes for the brightness, drawSphere and the step count.  Supersampled, the leader lane
 // stores its own sample's values (the group's first sample), unfiltered.
-template <int R, bool LIST, bool DUMP, class P, int SS = 0, bool CACHED = false, bool AUX = false>
+// PLACE (sfrt_world_render_subset): the subset goes in place into a whole frame --
+// compact column a (output pixel a >> SS) is stored xstride elements apart, the host having put
+// the subset's first pixel into f.out and yadd frame rows into f.out_pitch (the planes' pitches
+// likewise) -- where every other launch stores it compactly.  All else is the same.
+template <int R, bool LIST, bool DUMP, class P, int SS = 0, bool CACHED = false, bool AUX = false,
+          bool PLACE = false>
 __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
                                                     const SphereRec* __restrict__ sph,
                                                     DumpArgs dmp,
                                                     const float* __restrict__ rc = nullptr,
                                                     const TileRec* tr = nullptr,
-                                                    AuxArgs aux = AuxArgs{}) {
+                                                    AuxArgs aux = AuxArgs{},
+                                                    [[maybe_unused]] int xstride = 1) {
+  static_assert(!PLACE || (!DUMP && !CACHED), "the placing kernels compute their directions and dump nothing");
   static_assert(SS == 0 || !DUMP, "trace_points dumps the 1x pixel");
   static_assert(!CACHED || !DUMP, "the DUMP kernels compute their directions");
   static_assert(!AUX || (!DUMP && !CACHED), "the AUX kernels compute their directions and dump nothing");
@@ -846,7 +853,12 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   // recomputed the 64-bit row offset, three quarter-rate multiplies per slot)
   // (SS > 0: the output pixel of sample (a, b) is (a >> SS, (b - sub_row0) >> SS))
   uint32_t* const row_out = f.out + (long long)((b_s - f.sub_row0) >> SS) * f.out_pitch;
-  auto px_out = [&](int r) { return row_out + (col(r) >> SS); };
+  // the output column's element offset in its row (PLACE: xstride apart; < 2^31, the host checks)
+  auto col_out = [&](int r) {
+    if constexpr (PLACE) return (col(r) >> SS) * xstride;
+    else return col(r) >> SS;
+  };
+  auto px_out = [&](int r) { return row_out + col_out(r); };
   // AUX: each plane's row likewise (null planes: wave-uniform, never stored)
   [[maybe_unused]] float* depth_row = nullptr;
   [[maybe_unused]] int32_t* sphere_row = nullptr;
@@ -878,7 +890,7 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
       sh[r] = shade_texel<P, AUX>(f, d[r], ray.px[r], ray.py[r], ray.pz[r], DUMP ? &dl[DUMP ? r : 0] : nullptr);
     // AUX: ray r's plane values beside its colour store (plain vector stores)
     [[maybe_unused]] auto aux_store = [&](int r) {
-      const int c = col(r) >> SS;
+      const int c = col_out(r);
       if (aux.depth) depth_row[c] = sh[r].depth;
       if (aux.sphere) sphere_row[c] = ray.draw[r];
       if (aux.steps) steps_row[c] = ray.iters[r];
@@ -954,7 +966,7 @@ __global__ __launch_bounds__(64, 8) void k_trace_window_r(InlineArgs args) {
 }
 
 // n > 64: the records in device memory (f.spheres, read with scalar loads: rec_at), the
-// culled list per wave.  57 VGPRs at R = 4 (8 waves/SIMD).
+// culled list per wave.  61 VGPRs at R = 4 (8 waves/SIMD).
 template <int R>
 __global__ __launch_bounds__(64) void k_trace_window_list(FrameRec f) {
   trace_tile_window_r<R, true, false, ActiveProbe>(f, f.spheres, DumpArgs{});
@@ -1025,6 +1037,21 @@ template <int R, int SS>
 __global__ __launch_bounds__(64) void k_trace_window_list_aux(FrameRec f, AuxArgs a) {
   trace_tile_window_r<R, true, false, NoProbe, SS, false, true>(f, f.spheres, DumpArgs{}, nullptr,
                                                                 nullptr, a);
+}
+
+// The placing instantiations (sfrt_world_render_subset[_aux]; never probed): one
+// family, AUX its flag, the planes and the column stride in arguments of their own.  The plain
+// ones keep k_trace_window_r's bound while they fit it; the plane-writing ones carry the AUX
+// kernels' step counters and, like them, take no occupancy bound.
+template <int R, int SS, bool AUX>
+__global__ __launch_bounds__(64, AUX ? 1 : 8) void k_trace_place_r(InlineArgs args, AuxArgs a, int xstride) {
+  trace_tile_window_r<R, false, false, NoProbe, SS, false, AUX, true>(args.f, args.s, DumpArgs{}, nullptr,
+                                                                      nullptr, a, xstride);
+}
+template <int R, int SS, bool AUX>
+__global__ __launch_bounds__(64) void k_trace_place_list(FrameRec f, AuxArgs a, int xstride) {
+  trace_tile_window_r<R, true, false, NoProbe, SS, false, AUX, true>(f, f.spheres, DumpArgs{}, nullptr,
+                                                                     nullptr, a, xstride);
 }
 
 // ---- Ray batches: SphereWorld::Raycast for caller-supplied rays (sfrt_world_cast_rays;
@@ -1268,7 +1295,7 @@ int launch_ray_fill(const FrameRec& f, float* ray_cache, TileRec* tile_recs, voi
 
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump, void* done_event, const float* ray_cache,
-                 const TileRec* tile_recs, const AuxArgs* aux) {
+                 const TileRec* tile_recs, const AuxArgs* aux, int place_xstride) {
   const long long tiles_y = (f.sub_rows + kTile - 1) / kTile;
   if (tiles_y <= 0 || f.sub_w <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
@@ -1293,6 +1320,11 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
   if (ray_cache && (!ordered || !g.tile_cost || dump)) return -1;
   // the AUX kernels compute their directions and dump nothing; one plane at least
   if (aux && (dump || ray_cache || (!aux->depth && !aux->sphere && !aux->steps))) return -1;
+  // the placing kernels: row-major, their directions computed, nothing dumped; the last output
+  // column's element offset fits the kernels' int
+  if (place_xstride < 0 || (place_xstride && (ordered || dump || ray_cache))) return -1;
+  if (place_xstride && (long long)((f.sub_w - 1) >> f.ss) * place_xstride > 0x7fffffffLL) return -1;
+  const AuxArgs no_planes{};
   // The list kernels run only for n > 64: their lookahead reads culled-list lane 63, whose
   // default sphere 63 must exist (the static_assert beside first_entry).
   const bool list = f.n > kInlineSpheres;
@@ -1311,7 +1343,12 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
     with_ss(f.ss, [&](auto ss) {
       constexpr int R = decltype(r)::value, SS = decltype(ss)::value;
       // mode                n <= 64                                                 n > 64
-      if (aux) {
+      if (place_xstride) {
+        if (aux) list ? lst(k_trace_place_list<R, SS, true>, *aux, place_xstride)
+                      : inl(k_trace_place_r<R, SS, true>, *aux, place_xstride);
+        else list ? lst(k_trace_place_list<R, SS, false>, no_planes, place_xstride)
+                  : inl(k_trace_place_r<R, SS, false>, no_planes, place_xstride);
+      } else if (aux) {
         list ? lst(k_trace_window_list_aux<R, SS>, *aux) : inl(k_trace_window_r_aux<R, SS>, *aux);
       } else if (ray_cache) {
         list ? lst(k_trace_window_list_rc<R, SS>, ray_cache, tile_recs)

@@ -111,8 +111,12 @@ struct VoxAux {
 long long voxel_tile_key(const VoxFrame& f, long long* tiles);
 // done_event (hipEvent_t, may be null): recorded by the launch's own completion (its stop event).
 // aux != nullptr (at least one plane set): the plane-writing kernels on the same grid.
+// place_xstride > 0 (sfrt_voxel_render_subset): the placing kernels -- the subset stored in place
+// in a whole frame, output column a at element a * place_xstride of its row, f.out the subset's
+// first pixel and f.out_pitch (and aux's pitches) the elements between two subset rows; row-major,
+// f linked into no tile-order chain, with or without aux.
 int launch_voxel(const VoxFrame& f, void* stream, void* done_event = nullptr,
-                 const VoxAux* aux = nullptr);
+                 const VoxAux* aux = nullptr, int place_xstride = 0);
 
 // A batch of caller-supplied rays (sfrt_voxel_cast_rays[_device]): device pointers,
 // ray q's direction at dirs[3q..3q+2] (r->dir verbatim), its r->yscale at yscales[q] (null: 1.0f

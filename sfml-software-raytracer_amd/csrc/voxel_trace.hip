@@ -496,9 +496,14 @@ __device__ __forceinline__ void store_planes(const VoxAux& aux, const VoxHit& hi
 // AUX (k_voxel_aux): the planes of `aux` beside the colour, one dword per non-null plane from the
 // lane that stores the pixel -- for SS > 0 the group's leader, whose sample is the output pixel's
 // first, (S * i, S * j).  The null tests are wave-uniform (kernel arguments).
-template <int SS, bool AUX>
+//
+// PLACE (k_voxel_place; sfrt_voxel_render_subset): the subset in place in a whole frame -- output
+// column a is stored xstride elements apart, the host having put the subset's first pixel into
+// f.out and yadd frame rows into f.out_pitch (the planes' pitches likewise).
+template <int SS, bool AUX, bool PLACE = false>
 __device__ __forceinline__ bool voxel_tile(const VoxFrame& f, const VoxAux& aux, int tiles_x,
-                                           int ntiles, int& tile, uint32_t& cls, uint32_t& work) {
+                                           int ntiles, int& tile, uint32_t& cls, uint32_t& work,
+                                           [[maybe_unused]] int xstride = 1) {
   const int lane = threadIdx.x & 63;
   int slot = (int)blockIdx.x;
   if (f.prev_cost) {
@@ -526,7 +531,20 @@ __device__ __forceinline__ bool voxel_tile(const VoxFrame& f, const VoxAux& aux,
   // raycast(), a, b and `in` were spilled to scratch (16 bytes per lane).
   const int lane2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   const int a2 = tx * 8 + (lane2 & 7), r2 = ty * 8 + (lane2 >> 3);
-  if constexpr (SS == 0) {
+  if constexpr (PLACE) {
+    // as the two branches below, the output column xstride elements apart (< 2^31: the host)
+    const int c2 = (a2 >> SS) * xstride;
+    uint32_t px = rgba;
+    bool store = a2 < f.sub_w && r2 < f.sub_rows;
+    if constexpr (SS > 0) {
+      px = group_box_rgba8<SS>(rgba);
+      store = store && group_leader<SS>(lane2);
+    }
+    if (store) {
+      f.out[(long long)(r2 >> SS) * f.out_pitch + c2] = px;
+      if constexpr (AUX) store_planes(aux, hit, r2 >> SS, c2);
+    }
+  } else if constexpr (SS == 0) {
     if (a2 < f.sub_w && r2 < f.sub_rows) {
       f.out[(long long)r2 * f.out_pitch + a2] = rgba;
       if constexpr (AUX) store_planes(aux, hit, r2, a2);
@@ -588,6 +606,18 @@ __global__ __launch_bounds__(64, SFRT_VOX_AUX_WAVES) void k_voxel_aux(VoxFrame f
     const uint32_t w = wave_max_u32(work);
     if ((threadIdx.x & 63) == 0) store_cost(f.tile_cost, tile, tile_bucket(w >> 2), cls, f.cost_diff);
   }
+}
+
+// The placing instantiations (sfrt_voxel_render_subset[_aux]), one family over
+// SS with AUX as its flag, the planes and the column stride in arguments of their own.  Row-major
+// always and outside every tile-order chain: no sorter, no cost record.  Each takes the bound of
+// its sibling above (plain: k_voxel_ordered's, planes: k_voxel_aux's).
+template <int SS, bool AUX>
+__global__ __launch_bounds__(64, AUX ? SFRT_VOX_AUX_WAVES : SFRT_VOX_WAVES) void k_voxel_place(
+    VoxFrame f, int tiles_x, int ntiles, VoxAux aux, int xstride) {
+  int tile;
+  uint32_t cls, work;
+  (void)voxel_tile<SS, AUX, true>(f, aux, tiles_x, ntiles, tile, cls, work, xstride);
 }
 
 // ---- Ray batches: World::Raycast / World::LRaycast for caller-supplied rays
@@ -755,9 +785,20 @@ void launch_voxel_aux(const VoxFrame& f, const VoxAux& aux, dim3 grid, long long
   hipExtLaunchKernelGGL((k_voxel_aux<COST, SS>), grid, dim3(64), 0, (hipStream_t)stream, nullptr,
                         (hipEvent_t)done_event, 0, f, (int)((f.sub_w + 7) / 8), (int)tiles, aux);
 }
+template <int SS>
+void launch_voxel_place(const VoxFrame& f, const VoxAux* aux, int xstride, dim3 grid, long long tiles,
+                        void* stream, void* done_event) {
+  if (aux)
+    hipExtLaunchKernelGGL((k_voxel_place<SS, true>), grid, dim3(64), 0, (hipStream_t)stream, nullptr,
+                          (hipEvent_t)done_event, 0, f, (int)((f.sub_w + 7) / 8), (int)tiles, *aux, xstride);
+  else
+    hipExtLaunchKernelGGL((k_voxel_place<SS, false>), grid, dim3(64), 0, (hipStream_t)stream, nullptr,
+                          (hipEvent_t)done_event, 0, f, (int)((f.sub_w + 7) / 8), (int)tiles, VoxAux{}, xstride);
+}
 }  // namespace
 
-int launch_voxel(const VoxFrame& f, void* stream, void* done_event, const VoxAux* aux) {
+int launch_voxel(const VoxFrame& f, void* stream, void* done_event, const VoxAux* aux,
+                 int place_xstride) {
   long long tiles = 0;
   if (voxel_tile_key(f, &tiles) == 0) return 0;
   // the kernel reads the grid through a buffer resource over f.cells (f.cell_bytes) and the tables
@@ -771,8 +812,17 @@ int launch_voxel(const VoxFrame& f, void* stream, void* done_event, const VoxAux
   if (f.ss < 0 || f.ss > 2) return -1;
   // whole S x S groups: the filter's cross-lane adds rely on it
   if (f.ss && ((f.sub_w | f.sub_row0 | f.sub_rows) & ((1 << f.ss) - 1))) return -1;
+  if (aux && !aux->depth && !aux->cell && !aux->face && !aux->steps) return -1;
+  if (place_xstride) {  // the placing kernels: row-major, outside every chain
+    if (place_xstride < 0 || f.tile_order || f.tile_cost || f.prev_cost) return -1;
+    // the last output column's element offset fits the kernels' int
+    if ((long long)((f.sub_w - 1) >> f.ss) * place_xstride > 0x7fffffffLL) return -1;
+    if (f.ss == 0) launch_voxel_place<0>(f, aux, place_xstride, grid, tiles, stream, done_event);
+    else if (f.ss == 1) launch_voxel_place<1>(f, aux, place_xstride, grid, tiles, stream, done_event);
+    else launch_voxel_place<2>(f, aux, place_xstride, grid, tiles, stream, done_event);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+  }
   if (aux) {  // the same grid, the plane-writing kernels
-    if (!aux->depth && !aux->cell && !aux->face && !aux->steps) return -1;
     const bool cost = f.tile_cost != nullptr;
     if (f.ss == 0) {
       if (cost) launch_voxel_aux<true, 0>(f, *aux, grid, tiles, stream, done_event);

@@ -68,6 +68,8 @@ ABI_SYMBOLS = (
     "sfrt_voxel_cast_shadow_rays", "sfrt_voxel_cast_shadow_rays_device",
     "sfrt_glsl_draw_aux", "sfrt_glsl_draw_image_aux",
     "sfrt_glsl_cast_rays", "sfrt_glsl_cast_rays_device",
+    "sfrt_world_render_subset", "sfrt_world_render_subset_aux",
+    "sfrt_voxel_render_subset", "sfrt_voxel_render_subset_aux",
 )
 
 SFRT_MULTI_AUTO, SFRT_MULTI_RCCL, SFRT_MULTI_PEER = 0, 1, 2
@@ -173,6 +175,12 @@ def lib() -> ctypes.CDLL:
         "sfrt_world_update_spheres": ([W], c_int),
         "sfrt_world_update_image": ([W, vp, c_int, c_int, c_int, c_int], c_int),
         "sfrt_world_render_band": ([W, vp, ctypes.c_int64, c_int, c_int, vp], c_int),
+        "sfrt_world_render_subset": ([W, vp, ctypes.c_int64, c_int, c_int, c_int, c_int, vp], c_int),
+        "sfrt_world_render_subset_aux": ([W, vp, ctypes.c_int64, P(AuxPlanes), c_int, c_int, c_int,
+                                          c_int, vp], c_int),
+        "sfrt_voxel_render_subset": ([vp, vp, ctypes.c_int64, c_int, c_int, c_int, c_int, vp], c_int),
+        "sfrt_voxel_render_subset_aux": ([vp, vp, ctypes.c_int64, P(VoxelAuxPlanes), c_int, c_int,
+                                          c_int, c_int, vp], c_int),
         "sfrt_world_render_band_aux": ([W, vp, ctypes.c_int64, P(AuxPlanes), c_int, c_int, vp],
                                        c_int),
         "sfrt_world_update_image_aux": ([W, vp, vp, vp, vp, c_int, c_int, c_int, c_int], c_int),
@@ -491,6 +499,32 @@ class World:
                                                 ctypes.c_void_p(stream or None)),
                "render_band_aux")
 
+    def render_subset(self, dev_ptr: int, pitch_bytes: int, ystart: int = 0, yadd: int = 1,
+                      xstart: int = 0, xadd: int = 1, stream: int = 0) -> None:
+        """update_image's pixel subset in place in the whole width x height device frame at
+        dev_ptr (sfrt_world_render_subset): only the addressed pixels are written; asynchronous
+        on `stream`."""
+        _check(lib().sfrt_world_render_subset(self._h, ctypes.c_void_p(dev_ptr), int(pitch_bytes),
+                                              int(ystart), int(yadd), int(xstart), int(xadd),
+                                              ctypes.c_void_p(stream or None)),
+               "render_subset")
+
+    def render_subset_aux(self, dev_ptr: int, pitch_bytes: int, ystart: int = 0, yadd: int = 1,
+                          xstart: int = 0, xadd: int = 1, stream: int = 0, depth=None, sphere=None,
+                          steps=None) -> None:
+        """render_subset plus the same elements of the whole-frame planes (render_band_aux's
+        pairs: device pointer, pitch in bytes)."""
+        planes = AuxPlanes()
+        for name, plane in (("depth", depth), ("sphere", sphere), ("steps", steps)):
+            if plane is not None:
+                setattr(planes, name, int(plane[0]))
+                setattr(planes, name + "_pitch_bytes", int(plane[1]))
+        _check(lib().sfrt_world_render_subset_aux(self._h, ctypes.c_void_p(dev_ptr), int(pitch_bytes),
+                                                  ctypes.byref(planes), int(ystart), int(yadd),
+                                                  int(xstart), int(xadd),
+                                                  ctypes.c_void_p(stream or None)),
+               "render_subset_aux")
+
     def update_image_aux(self, pixels: np.ndarray, depth=None, sphere=None, steps=None,
                          ystart=0, yadd=1, xstart=0, xadd=1) -> np.ndarray:
         """update_image plus host planes of width*height elements (sfrt_world_update_image_aux):
@@ -698,6 +732,31 @@ class VoxelWorld:
                                                 ctypes.byref(planes), int(row0), int(rows),
                                                 ctypes.c_void_p(stream or None)),
                "voxel_render_band_aux")
+
+    def render_subset(self, dev_ptr: int, pitch_bytes: int, ystart: int = 0, yadd: int = 1,
+                      xstart: int = 0, xadd: int = 1, stream: int = 0) -> None:
+        """update_image's pixel subset in place in the whole width x height device frame at
+        dev_ptr (sfrt_voxel_render_subset): only the addressed pixels are written."""
+        _check(lib().sfrt_voxel_render_subset(self._h, ctypes.c_void_p(dev_ptr), int(pitch_bytes),
+                                              int(ystart), int(yadd), int(xstart), int(xadd),
+                                              ctypes.c_void_p(stream or None)),
+               "voxel_render_subset")
+
+    def render_subset_aux(self, dev_ptr: int, pitch_bytes: int, ystart: int = 0, yadd: int = 1,
+                          xstart: int = 0, xadd: int = 1, stream: int = 0, depth=None, cell=None,
+                          face=None, steps=None) -> None:
+        """render_subset plus the same elements of the whole-frame planes (render_band_aux's
+        pairs: device pointer, pitch in bytes)."""
+        planes = VoxelAuxPlanes()
+        for name, plane in (("depth", depth), ("cell", cell), ("face", face), ("steps", steps)):
+            if plane is not None:
+                setattr(planes, name, int(plane[0]))
+                setattr(planes, name + "_pitch_bytes", int(plane[1]))
+        _check(lib().sfrt_voxel_render_subset_aux(self._h, ctypes.c_void_p(dev_ptr), int(pitch_bytes),
+                                                  ctypes.byref(planes), int(ystart), int(yadd),
+                                                  int(xstart), int(xadd),
+                                                  ctypes.c_void_p(stream or None)),
+               "voxel_render_subset_aux")
 
     def update_image_aux(self, pixels: np.ndarray, depth=None, cell=None, face=None, steps=None,
                          ystart=0, yadd=1, xstart=0, xadd=1) -> np.ndarray:
