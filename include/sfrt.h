@@ -198,6 +198,47 @@ SFRT_API int sfrt_world_render_subset_aux(sfrt_world* w, void* dev_frame, int64_
                                           const sfrt_aux_planes* aux, int ystart, int yadd,
                                           int xstart, int xadd, void* hip_stream);
 
+/* ---- a batch of camera views of the world in one launch ----
+ * The other eye of a stereo pair, the six faces of a probe's cube map, a split screen, a mini-map,
+ * many small agent or thumbnail views: each a whole width x height frame of this world from a
+ * camera of its own, into a target of its own, all in one kernel launch.
+ * Definition: with the world as it stands at the call, view k receives exactly the bytes that
+ *   sfrt_world_set_camera(w, &views[k].cam);
+ *   sfrt_world_update_spheres(w);                 -- with SFRT_VIEWS_SORT only
+ *   sfrt_world_render_band(w, views[k].dev_pixels, pitch_bytes, 0, height, s);
+ * would write on a copy of that world (the aux call: sfrt_world_render_band_aux with planes[k]),
+ * and the call writes no other byte.  Every view sorts from the world's current sphere order, not
+ * from view k-1's, and the per-sphere texture slots travel with their spheres; the sphere plane
+ * of a sorted view indexes that view's sorted order.  Whole frames only.
+ * The world itself is left as it was: its camera, its sphere list and order, the sphere
+ * textures, the tile-order chains, the ray cache and tile records (sfrt_world_ray_cache_stats)
+ * and the last fill (sfrt_world_row_costs).
+ * Asynchronous on `hip_stream` with sfrt_world_render_band's stream semantics; the march-limit
+ * and texel bits of every view go into the world's status word (sfrt_world_check).
+ * SFRT_OPT_SUPERSAMPLE, SFRT_OPT_CULL and SFRT_OPT_RAYS_PER_LANE are honoured (0 rays per lane:
+ * the row-major kernel table's choice, as sfrt_world_render_subset); the launch is row-major within
+ * a view and view-major across views, so SFRT_OPT_TILE_ORDER and SFRT_OPT_RAY_CACHE_MB have no
+ * influence.
+ * count == 0 returns SFRT_OK with nothing queued.  SFRT_E_INVALID, with nothing queued or written:
+ * a NULL world or `views`, count < 0 or > SFRT_MAX_VIEWS, unknown flag bits, pitch_bytes not a
+ * multiple of 4 or below 4*width, a NULL or not 4-byte-aligned dev_pixels or a camera
+ * sfrt_world_set_camera would refuse in any view, (aux) NULL `planes`, an entry with all three
+ * planes NULL or with a pitch sfrt_world_render_band_aux would refuse, or a grid the device cannot
+ * be given in one launch (more than 2^31 - 1 tiles over all views, or more than 2^26 - 1 tiles in
+ * one).  The world's own validation (SFRT_E_EMPTY, SFRT_E_NO_TEXTURE, SFRT_E_TOO_MANY) applies
+ * unchanged.  Targets (and planes) that overlap are the caller's responsibility. */
+#define SFRT_MAX_VIEWS 1024
+#define SFRT_VIEWS_SORT 1          /* flags bit 0: UpdateSpheres' sort per view */
+typedef struct {
+  sfrt_camera cam;                 /* this view's SphereWorld::cam */
+  void* dev_pixels;                /* its width x height RGBA8 target, rows pitch_bytes apart */
+} sfrt_view;
+SFRT_API int sfrt_world_render_views(sfrt_world* w, const sfrt_view* views, int count,
+                                     int64_t pitch_bytes, int flags, void* hip_stream);
+SFRT_API int sfrt_world_render_views_aux(sfrt_world* w, const sfrt_view* views,
+                                         const sfrt_aux_planes* planes /* count entries */,
+                                         int count, int64_t pitch_bytes, int flags, void* hip_stream);
+
 /* Estimated work per pixel row of the world's last frame fill that ran in the adaptive
  * tile order (sfrt_world_render_band, sfrt_world_submit_frame; SFRT_OPT_TILE_ORDER on):
  * *row0, *rows = the global rows it covered, costs[i] (i < *rows <= capacity) = the

@@ -207,6 +207,27 @@ class SphereWorld {
                                        hip_stream),
           "render_subset_aux");
   }
+  // A batch of whole frames of this world, one camera and one device target per view, in one
+  // launch (sfrt.h sfrt_world_render_views): view k is the frame that `cam = views[k].cam;
+  // [UpdateSpheres();] RenderBand(...)` would write, and this object's own cam and spheres are
+  // left as they are.  The Aux call writes planes[k] beside view k (one entry per view).
+  void RenderViews(const std::vector<sfrt_view>& views, int64_t pitch_bytes, bool sort,
+                   void* hip_stream) {
+    if (views.empty()) return;  // nothing to queue (an empty vector's data() may be null)
+    push_state();
+    check(sfrt_world_render_views(w_, views.data(), (int)views.size(), pitch_bytes,
+                                  sort ? SFRT_VIEWS_SORT : 0, hip_stream),
+          "render_views");
+  }
+  void RenderViewsAux(const std::vector<sfrt_view>& views, const std::vector<sfrt_aux_planes>& planes,
+                      int64_t pitch_bytes, bool sort, void* hip_stream) {
+    if (planes.size() != views.size()) throw Error(SFRT_E_INVALID, "render_views_aux");
+    if (views.empty()) return;
+    push_state();
+    check(sfrt_world_render_views_aux(w_, views.data(), planes.data(), (int)views.size(), pitch_bytes,
+                                      sort ? SFRT_VIEWS_SORT : 0, hip_stream),
+          "render_views_aux");
+  }
   // The reference's eight RenderThreads together (Source.cpp:17-28): each of the `cycles` steps
   // fills the columns == cycle (mod fullCycles) of every row, one launch, then steps cycle back by
   // one -- at fullCycles = 4 Source.cpp:23's (cycle + 3) % 4.  How many cycles a displayed frame

@@ -169,6 +169,24 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
 // trace_tile_key names) with the primary directions of f's rays, tile-major, and tile_recs
 // (tile_rec_bytes(tiles) bytes) with the tiles' records.
 int launch_ray_fill(const FrameRec& f, float* ray_cache, TileRec* tile_recs, void* stream);
+// A batch of camera views in one launch (sfrt_world_render_views[_aux]): view k's
+// record in a device table, the frame exactly as render_band's launch of a whole frame would
+// carry it in its arguments (f.spheres: the view's records in the same table, at least
+// kInlineSpheres of them readable; tile_order, tile_cost, prev_cost and next_order unused) and
+// its planes (read by the aux kernels only).
+struct ViewRec {
+  FrameRec f;
+  AuxArgs a;
+};
+// The tile grid of one view of the batch: pixels per lane by the row-major kernel table (f.rays
+// overrides it), the tiles of a row (the f.tiles_x of every record) and of a whole view.
+void trace_views_grid(const FrameRec& f, int* tiles_x, long long* tiles);
+// One launch for count views of one size: workgroup (x, y) is tile x, row-major, of view y, so the
+// views run in table order.  f: any view's record (its size, n, ss and rays choose the kernel);
+// dev_views: the table, staged earlier on the same stream; aux: the plane-writing kernels.
+// done_event (may be null): the launch's stop event, as launch_trace's.
+int launch_trace_views(const FrameRec& f, const ViewRec* dev_views, int count, bool aux,
+                       void* stream, void* done_event);
 // "release" for the shipped build; "diagnostic" (-DSFRT_EXP: wrong bytes by design) or
 // "ab" (EXTRA build flags, tools/ab_libs.py) otherwise.
 const char* trace_build_flavour();

@@ -55,6 +55,11 @@ inline V3 rot_y(V3 v, float amount) {
 inline V3 center(const sfrt_sphere& s) { return {s.x, s.y, s.z}; }
 
 bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+// A camera sfrt_world_set_camera takes.
+bool camera_ok(const sfrt_camera& c) {
+  return finite3(c.pos) && std::isfinite(c.rotation) && std::isfinite(c.hrotation) &&
+         std::isfinite(c.fov_h) && std::isfinite(c.fov_v);
+}
 bool sphere_ok(const sfrt_sphere& s) {
   return std::isfinite(s.x) && std::isfinite(s.y) && std::isfinite(s.z) && std::isfinite(s.radius) &&
          s.radius > 0.0f;
@@ -176,6 +181,12 @@ struct sfrt_world {
   sfrt::BatchStage ray_stage;  // staging of sfrt_world_cast_rays (the host call)
   sfrt::RetiredHost retired_host;  // the record ring's replaced pinned buffers (sfrt_host.h)
   std::vector<void*> retired_device;  // replaced record rings, freed with the world
+  // The tables of sfrt_world_render_views (view records and sphere records in one block): a ring
+  // of table slots under the record ring's rule (sfrt_host.h TableSlot) -- a slot is restaged only
+  // after the launch that read it, on whatever stream, is done (its relayed stop event).
+  static constexpr int kViewSlots = kRing;
+  sfrt::TableSlot view_slots[kViewSlots];
+  int next_view_slot = 0;
   // --- frame pipeline (display path): render k+1 while frame k is copied ---
   struct PipeSlot {
     sfrt::DeviceBuf d_buf;  // the frame, stream-ordered on the world's stream
@@ -224,6 +235,7 @@ struct sfrt_world {
       h_aux[q].release();
     }
     ray_stage.release();
+    for (sfrt::TableSlot& t : view_slots) t.release();
     retired_host.release();
     for (void* p : retired_device) (void)hipFree(p);
     if (stream) (void)hipStreamDestroy(stream);
@@ -252,6 +264,13 @@ struct sfrt_world {
   // ss_log2 > 0: the frame is the S*width x S*height sample frame (SFRT_OPT_SUPERSAMPLE),
   // i.e. :85-89 are evaluated with those sizes; the caller fills the subset in samples.
   void prepare(sfrt::FrameRec& f, std::vector<sfrt::SphereRec>& recs, int ss_log2 = 0) const {
+    prepare_frame(f, cam, spheres, ss_log2);
+    prepare_records(recs, spheres, sphere_tex);
+  }
+  // The frame's part, for any camera and sphere order (the views of sfrt_world_render_views take
+  // theirs), and the records' part, for any order and its texture slots.
+  void prepare_frame(sfrt::FrameRec& f, const sfrt_camera& cam, const std::vector<sfrt_sphere>& spheres,
+                     int ss_log2) const {
     std::memset(&f, 0, sizeof f);
     const int width = this->width << ss_log2, height = this->height << ss_log2;
     f.ss = ss_log2;
@@ -313,6 +332,9 @@ struct sfrt_world {
     if (!finite) f.cull = 0;
     f.tex = d_tex;
     f.status = d_status;
+  }
+  void prepare_records(std::vector<sfrt::SphereRec>& recs, const std::vector<sfrt_sphere>& spheres,
+                       const std::vector<int32_t>& sphere_tex) const {
     recs.resize(spheres.size());
     for (size_t i = 0; i < spheres.size(); i++) {
       const sfrt_sphere& s = spheres[i];
@@ -621,6 +643,7 @@ int sfrt_world_create(int hip_device, sfrt_world** out) {
   sfrt_world* w = new sfrt_world();
   w->device = hip_device;
   w->tex_written.relay = &w->relay;
+  for (sfrt::TableSlot& t : w->view_slots) t.relay = &w->relay;
   // Camera defaults (SphereWorld.h:10-21) and the constructor's conversion (:72-73).
   w->cam.fov_h = sfrt_deg_to_rad(75.0f);
   w->cam.fov_v = sfrt_deg_to_rad(47.0f);
@@ -659,9 +682,7 @@ int sfrt_world_get_size(const sfrt_world* w, int* width, int* height) {
 }
 
 int sfrt_world_set_camera(sfrt_world* w, const sfrt_camera* cam) {
-  if (!w || !cam || !finite3(cam->pos) || !std::isfinite(cam->rotation) ||
-      !std::isfinite(cam->hrotation) || !std::isfinite(cam->fov_h) || !std::isfinite(cam->fov_v))
-    return SFRT_E_INVALID;
+  if (!w || !cam || !camera_ok(*cam)) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
   w->cam = *cam;
   return SFRT_OK;
@@ -1113,6 +1134,121 @@ int sfrt_world_render_subset_aux(sfrt_world* w, void* dev_frame, int64_t pitch_b
                             hip_stream);
 }
 
+// sfrt_world_render_views and sfrt_world_render_views_aux (with_aux false for the plain call): view
+// k is the whole frame that set_camera(views[k].cam) [+ update_spheres] + render_band[_aux] would
+// write, all views in one launch of the view kernels (sfrt_trace.h launch_trace_views).  Each view's
+// record is prepare_frame's for its camera -- on a sorted copy of the spheres with SORT -- with the
+// frame geometry of render_band_body; the records and the sphere tables (one shared table, or one
+// per view with SORT, each at least kInlineSpheres records long) go to the device as one block of
+// a table slot.  Nothing of the world is written: not the camera, the spheres or their slots, and,
+// the launch being row-major and outside the tile-order chains as render_subset's, neither the ray
+// cache, the tile records nor the last fill.
+static int render_views_body(sfrt_world* w, const sfrt_view* views, const sfrt_aux_planes* planes,
+                             bool with_aux, int count, int64_t pitch_bytes, int flags,
+                             void* hip_stream) {
+  if (!w || !views || count < 0 || count > SFRT_MAX_VIEWS || (flags & ~SFRT_VIEWS_SORT) != 0 ||
+      pitch_bytes % 4 != 0 || (with_aux && !planes))
+    return SFRT_E_INVALID;
+  for (int k = 0; k < count; k++) {
+    if (!views[k].dev_pixels || !sfrt::aligned4({views[k].dev_pixels}) || !camera_ok(views[k].cam))
+      return SFRT_E_INVALID;
+    if (with_aux && !planes[k].depth && !planes[k].sphere && !planes[k].steps) return SFRT_E_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(w->mu);
+  if (count == 0) return SFRT_OK;
+  int rc = w->validate();
+  if (rc) return rc;
+  if (pitch_bytes < (int64_t)w->width * 4) return SFRT_E_INVALID;
+  std::vector<sfrt::AuxArgs> aux(with_aux ? (size_t)count : 0);
+  for (size_t k = 0; k < aux.size(); k++) {
+    const sfrt_aux_planes& p = planes[k];
+    sfrt::AuxArgs& a = aux[k];
+    if (!sfrt::aux_plane(p.depth, p.depth_pitch_bytes, w->width, a.depth, a.depth_pitch) ||
+        !sfrt::aux_plane(p.sphere, p.sphere_pitch_bytes, w->width, a.sphere, a.sphere_pitch) ||
+        !sfrt::aux_plane(p.steps, p.steps_pitch_bytes, w->width, a.steps, a.steps_pitch))
+      return SFRT_E_INVALID;
+  }
+  // The frame geometry of render_band_body for rows [0, height), the same for every view, and
+  // the grid it gives: refused before anything is queued if the runtime cannot take it
+  // (work-items per grid dimension are 32 bits, workgroups in all at most 2^31 - 1).
+  const int ss = w->ss;
+  const int n = (int)w->spheres.size();
+  sfrt::FrameRec geo;
+  std::memset(&geo, 0, sizeof geo);
+  geo.n = n;
+  geo.rays = w->rays;
+  geo.ss = ss;
+  geo.xstart = 0; geo.xadd = 1 << ss; geo.ystart = 0; geo.yadd = 1 << ss;
+  geo.sub_w = w->width << ss;
+  geo.sub_row0 = 0;
+  geo.sub_rows = w->height << ss;
+  long long tiles = 0;
+  sfrt::trace_views_grid(geo, &geo.tiles_x, &tiles);
+  if (tiles <= 0 || tiles * 64 > 0xffffffffLL || tiles * count > 0x7fffffffLL) return SFRT_E_INVALID;
+  sfrt::DeviceGuard g(w->device);
+  hipStream_t s = (hipStream_t)hip_stream;  // HIP convention: NULL = the null stream
+  const bool sort = (flags & SFRT_VIEWS_SORT) != 0;
+  std::vector<sfrt::SphereRec> recs;
+  w->prepare_records(recs, w->spheres, w->sphere_tex);
+  // The block: the view records, then the sphere tables (32-byte records, 32-byte aligned).
+  const size_t table_recs = (size_t)std::max(n, sfrt::kInlineSpheres);
+  const size_t table_bytes = table_recs * sizeof(sfrt::SphereRec);
+  const size_t tables_at = ((size_t)count * sizeof(sfrt::ViewRec) + 31) / 32 * 32;
+  const size_t bytes = tables_at + (sort ? (size_t)count : 1) * table_bytes;
+  sfrt::TableSlot& t = w->view_slots[w->next_view_slot];
+  w->next_view_slot = (w->next_view_slot + 1) % sfrt_world::kViewSlots;
+  HIP_TRY(t.reclaim());
+  HIP_TRY(t.grow(bytes, s));
+  uint8_t* const h = t.h.ptr<uint8_t>();
+  uint8_t* const d = t.d.ptr<uint8_t>();
+  std::memset(h + tables_at, 0, bytes - tables_at);  // the records past n: readable, never used
+  if (!sort) std::memcpy(h + tables_at, recs.data(), sizeof(sfrt::SphereRec) * (size_t)n);
+  std::vector<sfrt_sphere> sorted;
+  for (int k = 0; k < count; k++) {
+    const sfrt_camera& cam = views[k].cam;
+    const size_t table_at = tables_at + (sort ? (size_t)k * table_bytes : 0);
+    if (sort) {  // from the world's order, its records and their texture slots moved alike
+      sorted = w->spheres;
+      const std::vector<size_t> order = sort_spheres(sorted, {cam.pos[0], cam.pos[1], cam.pos[2]});
+      sfrt::SphereRec* const dst = (sfrt::SphereRec*)(h + table_at);
+      for (size_t i = 0; i < order.size(); i++) dst[i] = recs[order[i]];
+    }
+    sfrt::ViewRec v;
+    std::memset(&v, 0, sizeof v);
+    w->prepare_frame(v.f, cam, sort ? sorted : w->spheres, ss);
+    v.f.xstart = geo.xstart; v.f.xadd = geo.xadd; v.f.ystart = geo.ystart; v.f.yadd = geo.yadd;
+    v.f.sub_w = geo.sub_w;
+    v.f.sub_row0 = geo.sub_row0;
+    v.f.sub_rows = geo.sub_rows;
+    v.f.tiles_x = geo.tiles_x;
+    v.f.out = (uint32_t*)views[k].dev_pixels;
+    v.f.out_pitch = pitch_bytes / 4;
+    v.f.spheres = (const sfrt::SphereRec*)(d + table_at);
+    if (with_aux) v.a = aux[(size_t)k];
+    std::memcpy(h + (size_t)k * sizeof(sfrt::ViewRec), &v, sizeof v);
+    if (k == 0) geo = v.f;  // the launch's own copy: any view's record names the kernel
+  }
+  HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+  // after the last texture upload (queued on w->stream, where the other launches run)
+  if (w->tex_written.before_read(s) != hipSuccess ||
+      sfrt::launch_trace_views(geo, (const sfrt::ViewRec*)d, count, with_aux, s, t.launch_event())) {
+    (void)t.staged(s);  // the copy is queued: the slot stays busy until it has run
+    return SFRT_E_HIP;
+  }
+  HIP_TRY(t.launched_with(s));
+  return SFRT_OK;
+}
+
+int sfrt_world_render_views(sfrt_world* w, const sfrt_view* views, int count, int64_t pitch_bytes,
+                            int flags, void* hip_stream) {
+  return render_views_body(w, views, nullptr, false, count, pitch_bytes, flags, hip_stream);
+}
+
+int sfrt_world_render_views_aux(sfrt_world* w, const sfrt_view* views, const sfrt_aux_planes* planes,
+                                int count, int64_t pitch_bytes, int flags, void* hip_stream) {
+  return render_views_body(w, views, planes, true, count, pitch_bytes, flags, hip_stream);
+}
+
 // sfrt_world_cast_rays_device and, for the host call's staged copies, sfrt_world_cast_rays:
 // one launch of the ray-batch kernels on s with the world's mutex held.  The launch takes the
 // frame fill's immutable snapshot (records in the kernel arguments, or a ring slot with its
@@ -1391,7 +1527,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 11; }
+int sfrt_version(void) { return 12; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

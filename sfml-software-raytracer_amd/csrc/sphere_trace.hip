@@ -1054,6 +1054,39 @@ __global__ __launch_bounds__(64) void k_trace_place_list(FrameRec f, AuxArgs a, 
                                                                      nullptr, a, xstride);
 }
 
+// The view batches (sfrt_world_render_views[_aux]; never probed): workgroup (x, y)
+// is tile x of view y.  The view's record is read from the device table once, at entry, like a
+// sphere record (rec_at): the table is written only by the staging copy that precedes the launch
+// on its stream, the address is wave-uniform, so through the constant address space the fields
+// the body uses arrive by scalar loads, as the band kernels' arrive from their arguments.  The
+// body then runs on that copy as it runs on a band's arguments: row-major (the order fields are
+// constants here, so the sorter, the order lookup and the class store fold away), directions
+// computed, nothing dumped.  n <= 64 takes the non-list body -- the list body's lookahead needs
+// sphere 63 -- with the records in the table, where 64 are readable, in place of the arguments.
+__device__ __forceinline__ ViewRec view_rec_at(const ViewRec* p, uint32_t view) {
+  const __attribute__((address_space(4))) uint32_t* q =
+      (const __attribute__((address_space(4))) uint32_t*)(
+          (const __attribute__((address_space(4))) char*)p + (size_t)view * sizeof(ViewRec));
+  uint32_t w[sizeof(ViewRec) / 4];
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(ViewRec) / 4); i++) w[i] = q[i];
+  ViewRec r;
+  __builtin_memcpy(&r, w, sizeof r);
+  return r;
+}
+// The plain n <= 64 ones keep k_trace_window_r's bound; the others take none, as the kernels
+// they mirror.
+template <int R, int SS, bool LIST, bool AUX>
+__global__ __launch_bounds__(64, (LIST || AUX) ? 1 : 8) void k_trace_views(const ViewRec* views) {
+  ViewRec v = view_rec_at(views, blockIdx.y);
+  v.f.tile_order = nullptr;
+  v.f.tile_cost = nullptr;
+  v.f.prev_cost = nullptr;
+  v.f.next_order = nullptr;
+  trace_tile_window_r<R, LIST, false, NoProbe, SS, false, AUX>(v.f, v.f.spheres, DumpArgs{}, nullptr,
+                                                              nullptr, AUX ? v.a : AuxArgs{});
+}
+
 // ---- Ray batches: SphereWorld::Raycast for caller-supplied rays (sfrt_world_cast_rays;
 // DESIGN.md 18) ----
 //
@@ -1360,6 +1393,37 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
       } else {
         list ? lst(k_trace_window_list<R>) : inl(k_trace_window_r<R>);
       }
+    });
+  });
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+void trace_views_grid(const FrameRec& f, int* tiles_x, long long* tiles) {
+  const int rays = trace_rays(f, false);  // (64-bit: a width near INT_MAX must not wrap)
+  *tiles_x = (int)(((long long)f.sub_w + rays * kTile - 1) / (rays * kTile));
+  *tiles = (long long)*tiles_x * (((long long)f.sub_rows + kTile - 1) / kTile);
+}
+
+int launch_trace_views(const FrameRec& f, const ViewRec* dev_views, int count, bool aux,
+                       void* stream, void* done_event) {
+  int tiles_x = 0;
+  long long tiles = 0;
+  trace_views_grid(f, &tiles_x, &tiles);
+  // whole frames of whole sample groups, a grid the runtime takes (work-items per dimension in 32
+  // bits, views in the y dimension's 16), the table's tiles_x this kernel's
+  if (!dev_views || count <= 0 || count > 0xffff || f.n <= 0 || !f.spheres || f.ss < 0 || f.ss > 2) return -1;
+  if (tiles <= 0 || tiles * 64 > 0xffffffffLL || tiles * count > 0x7fffffffLL || f.tiles_x != tiles_x) return -1;
+  if (f.sub_row0 != 0 || (f.ss && (f.sub_w | f.sub_rows) & ((1 << f.ss) - 1))) return -1;
+  const dim3 gr((unsigned)tiles, (unsigned)count), b(64);
+  hipStream_t s = (hipStream_t)stream;
+  const hipEvent_t ev = (hipEvent_t)done_event;
+  const bool list = f.n > kInlineSpheres;  // as launch_trace
+  auto go = [&](auto k) { hipExtLaunchKernelGGL(k, gr, b, 0, s, nullptr, ev, 0, dev_views); };
+  with_rays(trace_rays(f, false), [&](auto r) {
+    with_ss(f.ss, [&](auto ss) {
+      constexpr int R = decltype(r)::value, SS = decltype(ss)::value;
+      if (aux) list ? go(k_trace_views<R, SS, true, true>) : go(k_trace_views<R, SS, false, true>);
+      else list ? go(k_trace_views<R, SS, true, false>) : go(k_trace_views<R, SS, false, false>);
     });
   });
   return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -70,7 +70,11 @@ ABI_SYMBOLS = (
     "sfrt_glsl_cast_rays", "sfrt_glsl_cast_rays_device",
     "sfrt_world_render_subset", "sfrt_world_render_subset_aux",
     "sfrt_voxel_render_subset", "sfrt_voxel_render_subset_aux",
+    "sfrt_world_render_views", "sfrt_world_render_views_aux",
 )
+
+SFRT_MAX_VIEWS = 1024
+SFRT_VIEWS_SORT = 1
 
 SFRT_MULTI_AUTO, SFRT_MULTI_RCCL, SFRT_MULTI_PEER = 0, 1, 2
 SFRT_TRANSFER_AUTO, SFRT_TRANSFER_RGBA, SFRT_TRANSFER_PACKED = 0, 1, 2
@@ -105,6 +109,11 @@ class AuxPlanes(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_void_p), ("depth_pitch_bytes", ctypes.c_int64),
                 ("sphere", ctypes.c_void_p), ("sphere_pitch_bytes", ctypes.c_int64),
                 ("steps", ctypes.c_void_p), ("steps_pitch_bytes", ctypes.c_int64)]
+
+
+class View(ctypes.Structure):
+    """sfrt_view: one view of sfrt_world_render_views, its camera and its device target."""
+    _fields_ = [("cam", Camera), ("dev_pixels", ctypes.c_void_p)]
 
 
 class VoxelAuxPlanes(ctypes.Structure):
@@ -178,6 +187,9 @@ def lib() -> ctypes.CDLL:
         "sfrt_world_render_subset": ([W, vp, ctypes.c_int64, c_int, c_int, c_int, c_int, vp], c_int),
         "sfrt_world_render_subset_aux": ([W, vp, ctypes.c_int64, P(AuxPlanes), c_int, c_int, c_int,
                                           c_int, vp], c_int),
+        "sfrt_world_render_views": ([W, P(View), c_int, ctypes.c_int64, c_int, vp], c_int),
+        "sfrt_world_render_views_aux": ([W, P(View), P(AuxPlanes), c_int, ctypes.c_int64, c_int, vp],
+                                        c_int),
         "sfrt_voxel_render_subset": ([vp, vp, ctypes.c_int64, c_int, c_int, c_int, c_int, vp], c_int),
         "sfrt_voxel_render_subset_aux": ([vp, vp, ctypes.c_int64, P(VoxelAuxPlanes), c_int, c_int,
                                           c_int, c_int, vp], c_int),
@@ -524,6 +536,49 @@ class World:
                                                   int(xstart), int(xadd),
                                                   ctypes.c_void_p(stream or None)),
                "render_subset_aux")
+
+    @staticmethod
+    def _view_array(views):
+        """A ctypes array of View from View objects or (Camera, device pointer) pairs."""
+        arr = (View * max(1, len(views)))()
+        for k, v in enumerate(views):
+            if not isinstance(v, View):
+                v = View(v[0], int(v[1]) or None)
+            arr[k] = v
+        return arr
+
+    def render_views(self, views, pitch_bytes: int, sort: bool = False, stream: int = 0) -> None:
+        """A batch of whole frames of this world in one launch (sfrt_world_render_views): view k
+        is the frame set_camera(views[k].cam) [+ update_spheres with sort] + render_band would
+        write at views[k].dev_pixels; the world itself is left as it was.  views: View objects
+        or (Camera, device pointer) pairs.  Asynchronous on `stream`."""
+        arr = self._view_array(views)
+        _check(lib().sfrt_world_render_views(self._h, arr, len(views), int(pitch_bytes),
+                                             SFRT_VIEWS_SORT if sort else 0,
+                                             ctypes.c_void_p(stream or None)), "render_views")
+
+    def render_views_aux(self, views, planes, pitch_bytes: int, sort: bool = False,
+                         stream: int = 0) -> None:
+        """render_views plus each view's planes (sfrt_world_render_views_aux): planes[k] is an
+        AuxPlanes, or a dict of render_band_aux's (device pointer, pitch in bytes) pairs under
+        "depth", "sphere" and "steps"."""
+        if len(planes) != len(views):
+            raise ValueError("one planes entry per view")
+        arr = self._view_array(views)
+        pl = (AuxPlanes * max(1, len(views)))()
+        for k, p in enumerate(planes):
+            if not isinstance(p, AuxPlanes):
+                q = AuxPlanes()
+                for name, plane in p.items():
+                    if plane is not None:
+                        setattr(q, name, int(plane[0]))
+                        setattr(q, name + "_pitch_bytes", int(plane[1]))
+                p = q
+            pl[k] = p
+        _check(lib().sfrt_world_render_views_aux(self._h, arr, pl, len(views), int(pitch_bytes),
+                                                 SFRT_VIEWS_SORT if sort else 0,
+                                                 ctypes.c_void_p(stream or None)),
+               "render_views_aux")
 
     def update_image_aux(self, pixels: np.ndarray, depth=None, sphere=None, steps=None,
                          ystart=0, yadd=1, xstart=0, xadd=1) -> np.ndarray:
