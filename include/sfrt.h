@@ -362,7 +362,17 @@ SFRT_API int sfrt_world_cast_rays(sfrt_world* w, const float* dirs, const float*
  * per tile (the tile's culling cone and grid position, which depend on the same things),
  * written by the same fill, read by the same launches and freed with the directions.  They
  * are not counted against the limit (0.3 % of the directions' size at 4K); 0 turns both off.
- * See sfrt_world_tile_record_bytes. */
+ * See sfrt_world_tile_record_bytes.
+ * It governs the cull cache as well.  What a tile's wave culls before it marches -- which
+ * spheres can pass for some ray of the tile, and between which along-ray distances -- depends
+ * on the tile's cone, the camera position, the sphere count and each sphere's centre and
+ * radius, not on the textures or the spheres' texture slots.  When a stream's second consecutive
+ * launch keeps all of those (a camera at rest in a scene at rest) and reads the ray cache, the
+ * result is written once (528 bytes per tile, 16 MiB for a 4K frame; 784 above 64 spheres) and
+ * later launches load it; any launch that changes one of them -- the library compares the values,
+ * sphere by sphere -- culls for itself as before, so a walking camera or a sphere that moves
+ * every frame never fills.  Same bytes either way.  These bytes count against the limit: a cull
+ * cache that would take the world past it is not created.  See sfrt_world_cull_cache_stats. */
 #define SFRT_OPT_CULL 1
 #define SFRT_OPT_RAYS_PER_LANE 2
 #define SFRT_OPT_TILE_ORDER 3
@@ -380,6 +390,12 @@ SFRT_API int sfrt_world_ray_cache_stats(const sfrt_world* w, int64_t* cached_fra
 /* *bytes = device memory the world's tile records hold now (32 bytes per tile of every filled
  * cache; 0 while SFRT_OPT_RAY_CACHE_MB is 0).  Not part of sfrt_world_ray_cache_stats' bytes. */
 SFRT_API int sfrt_world_tile_record_bytes(const sfrt_world* w, int64_t* bytes);
+/* The cull cache's counters since the world was created (SFRT_OPT_RAY_CACHE_MB): *fills =
+ * launches preceded by a fill of the cull cache, *hits = launches that loaded their culling from
+ * a cache filled earlier (the filling launch is not a hit), *bytes = device memory the world's
+ * cull caches hold now.  Not part of sfrt_world_ray_cache_stats' bytes. */
+SFRT_API int sfrt_world_cull_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits,
+                                         int64_t* bytes);
 
 /* ---- stateless helpers ---- */
 /* UpdateSpheres ordering of an array in place (SphereWorld.cpp:199-212). */

@@ -295,6 +295,15 @@ class SphereWorld {
     check(sfrt_world_tile_record_bytes(w_, &b), "tile_record_bytes");
     return b;
   }
+  // The cull cache's counters (sfrt.h sfrt_world_cull_cache_stats).
+  struct CullCacheStats {
+    int64_t fills, hits, bytes;
+  };
+  CullCacheStats GetCullCacheStats() const {
+    CullCacheStats s{};
+    check(sfrt_world_cull_cache_stats(w_, &s.fills, &s.hits, &s.bytes), "cull_cache_stats");
+    return s;
+  }
   sfrt_world* handle() { return w_; }
 
  private:

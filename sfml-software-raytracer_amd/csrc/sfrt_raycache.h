@@ -9,12 +9,15 @@
 // records (TileRec, below) are filled, read and dropped by the same decisions; their layout and
 // the chain's buffer bookkeeping (sfrt_hostmem.h CacheBuf) are tested in
 // tests/native/tilerec_check.cpp.
+// The cull cache (CullKey, CullCachePolicy, at the end) rides on the tile records: what each tile's
+// wave culls before it marches, under a key of its own (tests/native/cullcache_check.cpp).
 #pragma once
 
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
-#include "sfrt_hostmem.h"  // CacheBuf: a chain's two buffers, for every user of this header
+#include "sfrt_hostmem.h"  // CacheBuf: a chain's buffers, for every user of this header
 
 namespace sfrt {
 
@@ -102,6 +105,121 @@ struct RayCachePolicy {
     if (a == RayAction::kFill) {
       cached = key;
       valid = true;
+    }
+    prev = key;
+    have_prev = true;
+  }
+
+  void invalidate() {
+    valid = false;
+    have_prev = false;
+  }
+};
+
+// ---- The cull cache (DESIGN.md 5 "Cull cache") ----
+//
+// What a wave's cull (sphere_trace.hip cull_wave) leaves -- the mask m of the spheres that may
+// pass for some ray of the tile and, per lane, a sphere's march window -- depends on the tile's
+// cone (cached under RayKey), the camera position, the cull margin, first_l and the cull option
+// (whether the wave culls at all), n, and the fields cx, cy, cz, r, s_pass of the records.  While
+// all of those stay, every frame recomputes the same bits: a chain whose launches keep them
+// (CullKey) fills them once (k_cull_fill) and the _cc kernels load them.  Indexed by tile number
+// like TileRec, whatever the tile order.
+//
+// Per tile one 16-byte record, 16-byte aligned (one scalar 4-dword load): m and the tile's grid
+// position, so that a reading launch loads no TileRec at all.
+struct alignas(16) CullRec {
+  uint32_t m_lo, m_hi;  // cull_wave's m (the list kernels: culled-list entries)
+  uint32_t tile_x;
+  uint32_t tile_y;      // bits 0-30; bit 31 (kCullRecFull): a list wave whose cull overflowed
+                        // its 64 entries (culled == false) -- every step visits every sphere
+};
+static_assert(sizeof(CullRec) == 16 && alignof(CullRec) == 16, "one s_load_dwordx4 per tile");
+constexpr uint32_t kCullRecFull = 0x80000000u;
+
+// Per lane of a tile, [tile][lane]: the window of the lane's sphere (n <= 64) ...
+struct alignas(8) CullWin {
+  float lo, hi;
+};
+// ... or of the lane's culled-list entry and the entry's sphere (n > 64).
+struct CullWinList {
+  float lo, hi;
+  int32_t cidx;
+};
+static_assert(sizeof(CullWin) == 8 && sizeof(CullWinList) == 12, "one vector load per lane");
+
+inline long long cull_rec_bytes(long long tiles) { return tiles * (long long)sizeof(CullRec); }
+inline long long cull_win_bytes(long long tiles, bool list) {
+  return tiles * 64 * (long long)(list ? sizeof(CullWinList) : sizeof(CullWin));
+}
+
+constexpr int kCullKeyFields = 5;  // cx, cy, cz, r, s_pass
+
+// Everything the cached bits depend on beyond the tile records, as bit patterns like RayKey.
+// The record fields are a copy kept with the key and compared by value: the key relies on no
+// pointer and on no promise of the caller (at most 1024 records of 20 bytes per launch).
+struct CullKey {
+  RayKey ray{};
+  uint32_t cam[3] = {}, cull_margin = 0, first_l = 0;
+  int32_t cull = 0, n = 0;
+  std::vector<uint32_t> fields;  // kCullKeyFields per record, n records
+
+  // The fields the cull reads of records recs[0..count) (any struct with SphereRec's members).
+  template <class Rec>
+  void set_records(const Rec* recs, int count) {
+    n = count;
+    fields.resize((size_t)(count > 0 ? count : 0) * kCullKeyFields);
+    for (int k = 0; k < count; k++) {
+      const float v[kCullKeyFields] = {recs[k].cx, recs[k].cy, recs[k].cz, recs[k].r, recs[k].s_pass};
+      for (int q = 0; q < kCullKeyFields; q++) fields[(size_t)k * kCullKeyFields + q] = ray_key_bits(v[q]);
+    }
+  }
+
+  bool same(const CullKey& o) const {
+    if (!ray.same(o.ray) || cull != o.cull || n != o.n || cull_margin != o.cull_margin ||
+        first_l != o.first_l)
+      return false;
+    for (int q = 0; q < 3; q++)
+      if (cam[q] != o.cam[q]) return false;
+    return fields == o.fields;
+  }
+};
+
+// One chain's cull cache, decided after the ray cache's action for the same launch is known:
+// the cull cache lives on the tile records, so it is read or filled only by a launch that reads
+// the ray cache (kRead) or fills it (kFill: then the records are rewritten, and whatever the
+// cull cache held is not trusted), and it is dropped with them (invalidate).  As for the
+// directions, a fill needs the second consecutive launch of a key: a walking camera or a sphere
+// that moves every frame never fills and runs the tile-record kernels unchanged.
+struct CullCachePolicy {
+  CullKey cached;
+  bool valid = false;
+  CullKey prev;
+  bool have_prev = false;
+
+  // ray: the ray cache's decision for this launch.  bytes: what the cull cache of `key` needs;
+  // held: the chain's own cull buffers now; others: every other cached byte of the world, this
+  // launch's ray cache included; budget: SFRT_OPT_RAY_CACHE_MB in bytes.
+  RayAction decide(const CullKey& key, RayAction ray, long long bytes, long long held,
+                   long long others, long long budget) const {
+    if (budget <= 0 || bytes <= 0 || ray == RayAction::kTrace) return RayAction::kTrace;
+    if (ray == RayAction::kRead && valid && cached.same(key)) return RayAction::kRead;
+    if (!have_prev || !prev.same(key)) return RayAction::kTrace;
+    const long long after = bytes > held ? bytes : held;
+    return others + after <= budget ? RayAction::kFill : RayAction::kTrace;
+  }
+
+  // ray, a: the two decisions of the launch; queued = false: the launch or a fill failed.
+  void commit(const CullKey& key, RayAction ray, RayAction a, bool queued) {
+    if (!queued) {
+      invalidate();
+      return;
+    }
+    if (a == RayAction::kFill) {
+      cached = key;
+      valid = true;
+    } else if (ray == RayAction::kFill) {
+      valid = false;  // the tile records were rewritten under this cache
     }
     prev = key;
     have_prev = true;

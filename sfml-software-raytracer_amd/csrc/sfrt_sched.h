@@ -69,13 +69,28 @@ struct TileSched {
   RayCachePolicy ray_policy;
   CacheBuf ray_dirs;  // the directions (ray_cache_bytes)
   CacheBuf ray_recs;  // the tile records (tile_rec_bytes)
+  // The chain's cull cache (sfrt_raycache.h CullCachePolicy): each tile's culling mask and march
+  // windows, two more buffers under the same rules.  It lives on the tile records: whatever
+  // invalidates or frees the ray cache does the same to it (invalidate_caches).
+  CullCachePolicy cull_policy;
+  CacheBuf cull_recs;  // the per-tile records (cull_rec_bytes)
+  CacheBuf cull_wins;  // the per-lane windows (cull_win_bytes)
 
-  // Both buffers freed by the host (the device has drained, or the chain is going away).
+  long long cull_bytes() const { return cull_recs.bytes + cull_wins.bytes; }
+
+  void invalidate_caches() {
+    ray_policy.invalidate();
+    cull_policy.invalidate();
+  }
+
+  // All four buffers freed by the host (the device has drained, or the chain is going away).
   void release_ray_cache() {
     const auto free_now = [](void* p) { return hipFree(p) == hipSuccess; };
     ray_dirs.release(free_now);
     ray_recs.release(free_now);
-    ray_policy.invalidate();
+    cull_recs.release(free_now);
+    cull_wins.release(free_now);
+    invalidate_caches();
   }
 
   void release() {
@@ -151,7 +166,7 @@ struct TileSched {
     if (!p.tile_cost) return hipSuccess;
     if (!queued) {
       reset();
-      ray_policy.invalidate();
+      invalidate_caches();
       return hipSuccess;
     }
     committed = pending_key != 0;

@@ -92,6 +92,7 @@ struct InlineArgs {
 };
 
 struct TileRec;  // sfrt_raycache.h
+struct CullRec;  // sfrt_raycache.h
 
 struct PixelDump {
   float pos[3];
@@ -161,14 +162,25 @@ int launch_cast_rays(const FrameRec& f, const SphereRec* host_spheres, const Ray
 // for this very f by launch_ray_fill earlier on the same stream -- the launch then loads its
 // directions, its tiles' culling cones and their grid positions from them (an ordered,
 // non-dump launch only).
+// cull_recs, cull_wins (both null, or both set, and then with ray_cache): the chain's cull cache,
+// filled for this very f and these very records by launch_cull_fill earlier on the same stream --
+// the launch then loads each tile's culling mask, march windows and grid position from it and
+// reads no tile record.
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump = nullptr, void* done_event = nullptr,
                  const float* ray_cache = nullptr, const TileRec* tile_recs = nullptr,
-                 const AuxArgs* aux = nullptr, int place_xstride = 0);
+                 const AuxArgs* aux = nullptr, int place_xstride = 0,
+                 const CullRec* cull_recs = nullptr, const void* cull_wins = nullptr);
 // Fills ray_cache (ray_cache_bytes(tiles, rays) bytes, sfrt_raycache.h, of the grid
 // trace_tile_key names) with the primary directions of f's rays, tile-major, and tile_recs
 // (tile_rec_bytes(tiles) bytes) with the tiles' records.
 int launch_ray_fill(const FrameRec& f, float* ray_cache, TileRec* tile_recs, void* stream);
+// Fills cull_recs (cull_rec_bytes(tiles) bytes, sfrt_raycache.h) and cull_wins
+// (cull_win_bytes(tiles, f.n > kInlineSpheres) bytes) of the same grid with what each tile's wave
+// of launch_trace(f, host_spheres, ...) would cull, from the cones in tile_recs (filled for f
+// earlier on the same stream).  n > kInlineSpheres: the records are read from f.spheres.
+int launch_cull_fill(const FrameRec& f, const SphereRec* host_spheres, const TileRec* tile_recs,
+                     CullRec* cull_recs, void* cull_wins, void* stream);
 // A batch of camera views in one launch (sfrt_world_render_views[_aux]): view k's
 // record in a device table, the frame exactly as render_band's launch of a whole frame would
 // carry it in its arguments (f.spheres: the view's records in the same table, at least

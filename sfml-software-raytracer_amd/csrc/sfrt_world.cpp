@@ -159,6 +159,14 @@ struct sfrt_world {
   const float* ray_cache = nullptr;
   const sfrt::TileRec* tile_recs = nullptr;  // the tile records that go with ray_cache
   int64_t ray_cached_frames = 0, ray_fills = 0;
+  // The cull cache (sfrt_raycache.h CullCachePolicy) of that launch, decided after the ray
+  // cache: the key, the action, the two buffers launch_trace reads (null: the launch culls for
+  // itself).  Counters: sfrt_world_cull_cache_stats.
+  sfrt::CullKey cull_key;
+  sfrt::RayAction cull_action = sfrt::RayAction::kTrace;
+  const sfrt::CullRec* cull_recs = nullptr;
+  const void* cull_wins = nullptr;
+  int64_t cull_fills = 0, cull_hits = 0;
   // Device copies of the sphere records for launches that read them from memory
   // (> 64 spheres, trace_points): a ring of slots, each with pinned staging and
   // the event of the last launch that read it, so a slot is never overwritten
@@ -420,7 +428,9 @@ struct sfrt_world {
   // aux (sfrt_world_render_band_aux): the launch joins the chain like any band but takes no
   // part in the ray cache's policy -- it neither reads, fills nor invalidates the cache, and
   // sched_end commits nothing for it.
-  int sched_begin(sfrt::FrameRec& f, hipStream_t s, bool aux = false) {
+  // recs: the launch's records (the cull cache's key holds the fields the cull reads).
+  int sched_begin(sfrt::FrameRec& f, const std::vector<sfrt::SphereRec>& recs, hipStream_t s,
+                  bool aux = false) {
     long long tiles = 0;
     const long long key = tile_order_on ? sfrt::trace_tile_key(f, &tiles) : 0;
     sfrt::TileSchedPtrs p;
@@ -439,24 +449,56 @@ struct sfrt_world {
     ray_cache = nullptr;
     tile_recs = nullptr;
     ray_action = sfrt::RayAction::kTrace;
+    cull_recs = nullptr;
+    cull_wins = nullptr;
+    cull_action = sfrt::RayAction::kTrace;
     if (!aux && tile_order_on == 1 && p.tile_cost && sched.pending_key != 0) {
       ray_active = true;
       ray_key = make_ray_key(f, key);
       const long long bytes = sfrt::ray_cache_bytes(tiles, (int)((key >> 56) & 7));
+      const long long budget = (long long)ray_cache_mb << 20;
+      // (others: without this chain's own cull cache -- a fill of the directions rewrites the
+      // tile records under it, so it is dropped first and takes no room from them)
       ray_action = sched.ray_policy.decide(ray_key, bytes, sched.ray_dirs.bytes,
-                                           ray_bytes_held() - sched.ray_dirs.bytes,
-                                           (long long)ray_cache_mb << 20);
+                                           cache_bytes_held() - sched.ray_dirs.bytes - sched.cull_bytes(),
+                                           budget);
+      if (ray_action == sfrt::RayAction::kFill) release_cull_on(sched, s);
       if (ray_action == sfrt::RayAction::kFill &&
           !ray_fill(sched, f, bytes, sfrt::tile_rec_bytes(tiles), s)) {
-        sched.ray_policy.invalidate();  // the buffers may be gone or half written
+        sched.invalidate_caches();  // the buffers may be gone or half written
         ray_action = sfrt::RayAction::kTrace;
       }
       if (ray_action != sfrt::RayAction::kTrace) {
         ray_cache = (const float*)sched.ray_dirs.ptr;
         tile_recs = (const sfrt::TileRec*)sched.ray_recs.ptr;
       }
+      // The cull cache, on top of the tile records this launch reads (or has just filled).
+      make_cull_key(cull_key, ray_key, f, recs);
+      const bool list = f.n > sfrt::kInlineSpheres;
+      const long long rec_bytes = sfrt::cull_rec_bytes(tiles), win_bytes = sfrt::cull_win_bytes(tiles, list);
+      cull_action = sched.cull_policy.decide(cull_key, ray_action, rec_bytes + win_bytes, sched.cull_bytes(),
+                                             cache_bytes_held() - sched.cull_bytes(), budget);
+      if (cull_action == sfrt::RayAction::kFill &&
+          !cull_fill(sched, f, recs, rec_bytes, win_bytes, s)) {
+        sched.cull_policy.invalidate();  // the tile records are whole: the launch reads them
+        cull_action = sfrt::RayAction::kTrace;
+      }
+      if (cull_action != sfrt::RayAction::kTrace) {
+        cull_recs = (const sfrt::CullRec*)sched.cull_recs.ptr;
+        cull_wins = sched.cull_wins.ptr;
+      }
     }
     return SFRT_OK;
+  }
+
+  static void make_cull_key(sfrt::CullKey& k, const sfrt::RayKey& ray, const sfrt::FrameRec& f,
+                            const std::vector<sfrt::SphereRec>& recs) {
+    k.ray = ray;
+    for (int q = 0; q < 3; q++) k.cam[q] = sfrt::ray_key_bits(f.cam[q]);
+    k.cull_margin = sfrt::ray_key_bits(f.cull_margin);
+    k.first_l = sfrt::ray_key_bits(f.first_l);
+    k.cull = f.cull;  // the option, cleared by prepare_frame for non-finite inputs
+    k.set_records(recs.data(), f.n);
   }
 
   static sfrt::RayKey make_ray_key(const sfrt::FrameRec& f, long long tile_key) {
@@ -479,6 +521,13 @@ struct sfrt_world {
     for (const sfrt::TileSched& c : scheds.chain) held += c.ray_dirs.bytes;
     return held;
   }
+  long long cull_bytes_held() const {
+    long long held = 0;
+    for (const sfrt::TileSched& c : scheds.chain) held += c.cull_bytes();
+    return held;
+  }
+  // Everything SFRT_OPT_RAY_CACHE_MB limits: the directions and the cull caches.
+  long long cache_bytes_held() const { return ray_bytes_held() + cull_bytes_held(); }
   // The tile records' bytes: reported on their own, never counted against the budget.
   long long tile_rec_bytes_held() const {
     long long held = 0;
@@ -492,6 +541,12 @@ struct sfrt_world {
   // kernel.
   static bool ray_fill(sfrt::TileSched& sched, const sfrt::FrameRec& f, long long bytes,
                        long long rec_bytes, hipStream_t s) {
+    if (!reserve_on(sched.ray_dirs, bytes, s) || !reserve_on(sched.ray_recs, rec_bytes, s)) return false;
+    return sfrt::launch_ray_fill(f, (float*)sched.ray_dirs.ptr,
+                                 (sfrt::TileRec*)sched.ray_recs.ptr, s) == 0;
+  }
+  // A chain's buffer grown, if need be, in the order of s.
+  static bool reserve_on(sfrt::CacheBuf& buf, long long bytes, hipStream_t s) {
     const auto free_on_s = [s](void* p) {
       if (hipFreeAsync(p, s) == hipSuccess) return true;
       (void)hipGetLastError();
@@ -503,11 +558,27 @@ struct sfrt_world {
       (void)hipGetLastError();  // no memory for it: not an error of the frame
       return nullptr;
     };
-    if (!sched.ray_dirs.reserve(bytes, free_on_s, alloc_on_s) ||
-        !sched.ray_recs.reserve(rec_bytes, free_on_s, alloc_on_s))
-      return false;
-    return sfrt::launch_ray_fill(f, (float*)sched.ray_dirs.ptr,
-                                 (sfrt::TileRec*)sched.ray_recs.ptr, s) == 0;
+    return buf.reserve(bytes, free_on_s, alloc_on_s);
+  }
+  // The chain's cull buffers freed in the order of s (before the tile records under them are
+  // refilled: what they hold is dropped either way, CullCachePolicy::commit).
+  static void release_cull_on(sfrt::TileSched& sched, hipStream_t s) {
+    const auto free_on_s = [s](void* p) {
+      if (hipFreeAsync(p, s) != hipSuccess) (void)hipGetLastError();
+      return true;
+    };
+    sched.cull_recs.release(free_on_s);
+    sched.cull_wins.release(free_on_s);
+    sched.cull_policy.valid = false;
+  }
+  // The chain's cull cache likewise, filled for f and recs on s from the chain's tile records
+  // (valid, or filled earlier on s for this launch).  false: the launch culls for itself.
+  static bool cull_fill(sfrt::TileSched& sched, const sfrt::FrameRec& f,
+                        const std::vector<sfrt::SphereRec>& recs, long long rec_bytes,
+                        long long win_bytes, hipStream_t s) {
+    if (!reserve_on(sched.cull_recs, rec_bytes, s) || !reserve_on(sched.cull_wins, win_bytes, s)) return false;
+    return sfrt::launch_cull_fill(f, recs.data(), (const sfrt::TileRec*)sched.ray_recs.ptr,
+                                  (sfrt::CullRec*)sched.cull_recs.ptr, sched.cull_wins.ptr, s) == 0;
   }
 
   // SFRT_OPT_RAY_CACHE_MB lowered below what the chains hold: every cache goes.  The chains'
@@ -533,6 +604,9 @@ struct sfrt_world {
       sched.ray_policy.commit(ray_key, ray_action, true);
       if (ray_action == sfrt::RayAction::kFill) ray_fills++;
       if (ray_action != sfrt::RayAction::kTrace) ray_cached_frames++;
+      sched.cull_policy.commit(cull_key, ray_action, cull_action, true);
+      if (cull_action == sfrt::RayAction::kFill) cull_fills++;
+      if (cull_action == sfrt::RayAction::kRead) cull_hits++;
     }
     if (sched.committed) {
       chain_cam[cur_chain] = ChainCam{true, cam, f.sub_row0};
@@ -871,14 +945,14 @@ int sfrt_world_set_option(sfrt_world* w, int option, int value) {
   if (option == SFRT_OPT_RAY_CACHE_MB) {
     if (value < 0) return SFRT_E_INVALID;
     // (0 also frees tile records left without directions by a fill that found no memory)
-    if (((long long)value << 20) < w->ray_bytes_held() ||
+    if (((long long)value << 20) < w->cache_bytes_held() ||
         (value == 0 && w->tile_rec_bytes_held() > 0)) {
       sfrt::DeviceGuard g(w->device);
       const int rc = w->ray_release_all();
       if (rc) return rc;
     }
     if (value == 0)
-      for (sfrt::TileSched& c : w->scheds.chain) c.ray_policy.invalidate();
+      for (sfrt::TileSched& c : w->scheds.chain) c.invalidate_caches();
     w->ray_cache_mb = value;
     return SFRT_OK;
   }
@@ -892,6 +966,15 @@ int sfrt_world_ray_cache_stats(const sfrt_world* w, int64_t* cached_frames, int6
   *cached_frames = w->ray_cached_frames;
   *fills = w->ray_fills;
   *bytes = w->ray_bytes_held();
+  return SFRT_OK;
+}
+
+int sfrt_world_cull_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits, int64_t* bytes) {
+  if (!w || !fills || !hits || !bytes) return SFRT_E_INVALID;
+  std::lock_guard<std::mutex> lk(w->mu);
+  *fills = w->cull_fills;
+  *hits = w->cull_hits;
+  *bytes = w->cull_bytes_held();
   return SFRT_OK;
 }
 
@@ -1037,10 +1120,11 @@ static int render_band_body(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes
   if (rc) return rc;
   // after the last texture upload (queued on w->stream, where the other launches run)
   HIP_TRY(w->tex_written.before_read(s));
-  if ((rc = w->sched_begin(f, s, with_aux))) return rc;
+  if ((rc = w->sched_begin(f, recs, s, with_aux))) return rc;
   if ((rc = w->sched_end(f, s, sfrt::launch_trace(f, recs.data(), s, nullptr, w->ring_event(),
                                                   w->ray_cache, w->tile_recs,
-                                                  with_aux ? &a : nullptr) == 0)))
+                                                  with_aux ? &a : nullptr, 0, w->cull_recs,
+                                                  w->cull_wins) == 0)))
     return rc;
   if ((rc = w->launched_with())) return rc;
   return SFRT_OK;
@@ -1462,10 +1546,11 @@ int sfrt_world_submit_frame(sfrt_world* w, uint8_t* pixels, int64_t* ticket) {
   if ((rc = w->launchable(f))) return rc;
   rc = w->stage_spheres(f, recs, w->stream, false);
   if (rc) return rc;
-  if ((rc = w->sched_begin(f, w->stream))) return rc;  // adaptive tile order, as render_band
+  if ((rc = w->sched_begin(f, recs, w->stream))) return rc;  // adaptive tile order, as render_band
   if ((rc = w->sched_end(f, w->stream,
                          sfrt::launch_trace(f, recs.data(), w->stream, nullptr, w->ring_event(),
-                                            w->ray_cache, w->tile_recs) == 0)))
+                                            w->ray_cache, w->tile_recs, nullptr, 0, w->cull_recs,
+                                            w->cull_wins) == 0)))
     return rc;
   if ((rc = w->launched_with())) return rc;
   HIP_TRY(hipEventRecord(slot.rendered, w->stream));
@@ -1527,7 +1612,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 12; }
+int sfrt_version(void) { return 13; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

@@ -455,6 +455,28 @@ __device__ __forceinline__ TileRec tile_rec_at(const TileRec* p, int tile) {
   return r;
 }
 
+// The cull cache (sfrt_raycache.h CullRec, CullWin, CullWinList; DESIGN.md 5 "Cull cache"): what
+// cull_wave leaves a tile's wave, stored by k_cull_fill (plain vector stores, the record from
+// lane 0) and loaded by the _cc kernels -- the record like a tile record (one scalar 4-dword
+// load: the buffer is written only by the fill that precedes the launch on its stream), the
+// lane's windows with one vector load of 8 (n > 64: 12) bytes.
+template <bool LIST>
+using CullLane = std::conditional_t<LIST, CullWinList, CullWin>;
+__device__ __forceinline__ CullRec cull_rec_at(const CullRec* p, int tile) {
+  const __attribute__((address_space(4))) uint32_t* q =
+      (const __attribute__((address_space(4))) uint32_t*)(
+          (const __attribute__((address_space(4))) char*)p + (size_t)tile * sizeof(CullRec));
+  uint32_t w[sizeof(CullRec) / 4];
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(CullRec) / 4); i++) w[i] = q[i];
+  CullRec r;
+  __builtin_memcpy(&r, w, sizeof r);
+  return r;
+}
+__device__ __forceinline__ size_t cull_win_at(int tile, int lane) {
+  return (size_t)tile * 64u + (size_t)lane;
+}
+
 // L = +0 for a lane's R rays at the start of a march step, two registers per
 // v_mov_b64 (left to itself the compiler copies one zero register into three
 // others and then pairs them: five moves a step for R = 4, not two).
@@ -756,19 +778,26 @@ __device__ __forceinline__ Rays<R> march_wave(const FrameRec& f, const SphereRec
 // one dword per non-null plane of `aux` (sfrt_trace.h AuxArgs): the hit distance shade_texel
 // computes for the brightness, drawSphere and the step count.  Supersampled, the leader lane
 // stores its own sample's values (the group's first sample), unfiltered.
+// CULLED (implies CACHED): the tile's culling mask, the lane's march window (and list entry) and
+// the tile's grid position are loaded from the chain's cull cache cr / cw (filled by k_cull_fill
+// for this launch's CullKey: the bits cull_wave gives) -- neither the tile record nor the sphere
+// records are read before the march.
 // PLACE (sfrt_world_render_subset): the subset goes in place into a whole frame --
 // compact column a (output pixel a >> SS) is stored xstride elements apart, the host having put
 // the subset's first pixel into f.out and yadd frame rows into f.out_pitch (the planes' pitches
 // likewise) -- where every other launch stores it compactly.  All else is the same.
 template <int R, bool LIST, bool DUMP, class P, int SS = 0, bool CACHED = false, bool AUX = false,
-          bool PLACE = false>
+          bool PLACE = false, bool CULLED = false>
 __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
                                                     const SphereRec* __restrict__ sph,
                                                     DumpArgs dmp,
                                                     const float* __restrict__ rc = nullptr,
                                                     const TileRec* tr = nullptr,
                                                     AuxArgs aux = AuxArgs{},
-                                                    [[maybe_unused]] int xstride = 1) {
+                                                    [[maybe_unused]] int xstride = 1,
+                                                    [[maybe_unused]] const CullRec* cr = nullptr,
+                                                    [[maybe_unused]] const CullLane<LIST>* cw = nullptr) {
+  static_assert(!CULLED || CACHED, "the cull cache rides on the ray cache");
   static_assert(!PLACE || (!DUMP && !CACHED), "the placing kernels compute their directions and dump nothing");
   static_assert(SS == 0 || !DUMP, "trace_points dumps the 1x pixel");
   static_assert(!CACHED || !DUMP, "the DUMP kernels compute their directions");
@@ -790,7 +819,14 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   const int tile = slot_tile(f.tile_order, slot, ntiles, cls);
   int tile_x, tile_y;
   [[maybe_unused]] TileRec trec;
-  if constexpr (CACHED) {
+  [[maybe_unused]] CullRec crec;
+  [[maybe_unused]] CullLane<LIST> cwin;
+  if constexpr (CULLED) {
+    if (tile >= ntiles) return;  // as below
+    crec = cull_rec_at(cr, tile);  // issued ahead of the vector loads: the latencies overlap
+    tile_x = (int)crec.tile_x;
+    tile_y = (int)(crec.tile_y & ~kCullRecFull);
+  } else if constexpr (CACHED) {
     if (tile >= ntiles) return;  // the same test as below, before the record is read
     trec = tile_rec_at(tr, tile);  // issued ahead of ray_cache_load: the two latencies overlap
     tile_x = (int)trec.tile_x;
@@ -807,6 +843,7 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   [[maybe_unused]] const int j = CACHED ? 0 : subset_index<SS>(f.ystart, f.yadd, bc);
   const float l0 = f.first_l;
   Rays<R> ray;  // iters: DUMP and AUX only, the host's first trip included
+  if constexpr (CULLED) cwin = cw[cull_win_at(tile, lane)];  // beside the directions' loads
   if constexpr (CACHED) ray_cache_load<R>(rc, tile, lane, ray.dx, ray.dy, ray.dz);
 #pragma unroll
   for (int r = 0; r < R; r++) {
@@ -823,12 +860,33 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
     ray.mv[r] = l0 > 0.0f ? 1.0f : 0.0f;
     ray.tacc[r] = l0;  // along-ray distance marched (binary32 sum of the steps)
   }
+  // The windows are first used inside the march's window path, and left alone the compiler sinks
+  // their load down there; a use here keeps it above, ahead of the directions' loads, whose
+  // arrival (in order) the positions above have already waited for.  R >= 3 only (the wide
+  // tiles of large frames): 4K 64 spheres 122.7 -> 122.1 us with it; at R = 2 a wave with at
+  // most kSlots culled spheres never reads its windows, and loading them for every wave cost
+  // the 1080p 10-sphere frame 3 % (profiles/ab/r9c_ab3_window_load.txt).
+  if constexpr (CULLED && R >= 3) {
+    __asm__ volatile("" : : "v"(cwin.lo), "v"(cwin.hi));
+    if constexpr (LIST) __asm__ volatile("" : : "v"(cwin.cidx));
+  }
   const bool windowed = f.cull && l0 > 0.0f;
   bool culled = windowed;  // else every step visits every sphere
   uint64_t m = 0;          // culled spheres (LIST: culled-list entries)
   float lo = -__builtin_inff(), hi = __builtin_inff();
   int cidx = lane;         // sphere of culled-list entry `lane`
-  if (windowed) {
+  if constexpr (CULLED) {
+    // No branch on `windowed`: for a launch that does not cull, k_cull_fill stored the values
+    // set above (under a branch the compiler sinks the window load into it, its whole latency
+    // exposed right before the march, and copies the rays' registers at the join).
+    m = (uint64_t)crec.m_lo | ((uint64_t)crec.m_hi << 32);
+    lo = cwin.lo;
+    hi = cwin.hi;
+    if constexpr (LIST) {
+      cidx = cwin.cidx;
+      culled = windowed && (crec.tile_y & kCullRecFull) == 0;
+    }
+  } else if (windowed) {
     Cone cone;
     if constexpr (CACHED) {
       cone.ax = trec.ax; cone.ay = trec.ay; cone.az = trec.az;
@@ -1013,6 +1071,70 @@ __global__ __launch_bounds__(64) void k_trace_window_list_rc(FrameRec f,
                                                              const float* __restrict__ rc,
                                                              const TileRec* tr) {
   trace_tile_window_r<R, true, false, ActiveProbe, SS, true>(f, f.spheres, DumpArgs{}, rc, tr);
+}
+
+// The cull cache's kernels (sfrt_raycache.h CullCachePolicy), of their own once more.
+// k_cull_fill: one wave per tile of the same grid runs the trace kernels' own cull_wave on the
+// cone of the tile's record, from the launch's own frame and sphere records under the same
+// flags (the same bits), and stores what it leaves: the lane's window (and list entry), and from
+// lane 0 the mask with the tile's grid position.  A launch that does not cull (f.cull off, or a
+// camera inside no sphere: first_l = +0) stores the values such a launch starts from.  The
+// pixels per lane and the supersampling factor reach the cull through the tile record alone, so
+// the kernel is not instantiated for them.
+// The _cc kernels are the _rc ones with the cull loaded as well.
+template <bool LIST>
+__device__ __forceinline__ void cull_fill_wave(const FrameRec& f, const SphereRec* sph,
+                                               const TileRec* tr, CullRec* __restrict__ cr,
+                                               CullLane<LIST>* __restrict__ cw) {
+  const int lane = threadIdx.x & 63;
+  const int tile = (int)blockIdx.x;  // the grid is exactly the tiles
+  const TileRec trec = tile_rec_at(tr, tile);
+  const bool windowed = f.cull && f.first_l > 0.0f;
+  bool culled = windowed;
+  uint64_t m = 0;
+  float lo = -__builtin_inff(), hi = __builtin_inff();
+  int cidx = lane;
+  if (windowed) {
+    Cone cone;
+    cone.ax = trec.ax; cone.ay = trec.ay; cone.az = trec.az;
+    cone.sin_t = trec.sin_t; cone.cos_t = trec.cos_t;
+    cone.wide = trec.wide != 0;
+    cull_wave<LIST>(f, sph, cone, lane, culled, m, lo, hi, cidx);
+  }
+  CullLane<LIST> win;
+  win.lo = lo;
+  win.hi = hi;
+  if constexpr (LIST) win.cidx = cidx;
+  cw[cull_win_at(tile, lane)] = win;
+  if (lane == 0) {
+    CullRec c;
+    c.m_lo = (uint32_t)m;
+    c.m_hi = (uint32_t)(m >> 32);
+    c.tile_x = trec.tile_x;
+    c.tile_y = trec.tile_y | ((windowed && !culled) ? kCullRecFull : 0u);
+    cr[tile] = c;
+  }
+}
+template <bool LIST>
+__global__ __launch_bounds__(64) void k_cull_fill(std::conditional_t<LIST, FrameRec, InlineArgs> args,
+                                                  const TileRec* tr, CullRec* __restrict__ cr,
+                                                  CullLane<LIST>* __restrict__ cw) {
+  if constexpr (LIST) cull_fill_wave<true>(args, args.spheres, tr, cr, cw);
+  else cull_fill_wave<false>(args.f, args.s, tr, cr, cw);
+}
+template <int R, int SS>
+__global__ __launch_bounds__(64, 8) void k_trace_window_r_cc(InlineArgs args,
+                                                             const float* __restrict__ rc,
+                                                             const CullRec* cr, const CullWin* cw) {
+  trace_tile_window_r<R, false, false, ActiveProbe, SS, true, false, false, true>(
+      args.f, args.s, DumpArgs{}, rc, nullptr, AuxArgs{}, 1, cr, cw);
+}
+template <int R, int SS>
+__global__ __launch_bounds__(64) void k_trace_window_list_cc(FrameRec f,
+                                                             const float* __restrict__ rc,
+                                                             const CullRec* cr, const CullWinList* cw) {
+  trace_tile_window_r<R, true, false, ActiveProbe, SS, true, false, false, true>(
+      f, f.spheres, DumpArgs{}, rc, nullptr, AuxArgs{}, 1, cr, cw);
 }
 
 // The DUMP instantiations of both (sfrt_world_trace_points): the shipped march and
@@ -1326,9 +1448,31 @@ int launch_ray_fill(const FrameRec& f, float* ray_cache, TileRec* tile_recs, voi
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int launch_cull_fill(const FrameRec& f, const SphereRec* host_spheres, const TileRec* tile_recs,
+                     CullRec* cull_recs, void* cull_wins, void* stream) {
+  long long tiles = 0;
+  if (!tile_recs || !cull_recs || !cull_wins || f.n <= 0 || trace_tile_key(f, &tiles) == 0 ||
+      tiles > 0x7fffffffLL)
+    return -1;
+  const bool list = f.n > kInlineSpheres;  // as launch_trace
+  if (list ? !f.spheres : !host_spheres) return -1;
+  const dim3 gr((unsigned)tiles), b(64);
+  hipStream_t s = (hipStream_t)stream;
+  if (list) {
+    hipLaunchKernelGGL(k_cull_fill<true>, gr, b, 0, s, f, tile_recs, cull_recs, (CullWinList*)cull_wins);
+  } else {
+    InlineArgs args;
+    args.f = f;
+    for (int k = 0; k < f.n; k++) args.s[k] = host_spheres[k];
+    hipLaunchKernelGGL(k_cull_fill<false>, gr, b, 0, s, args, tile_recs, cull_recs, (CullWin*)cull_wins);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump, void* done_event, const float* ray_cache,
-                 const TileRec* tile_recs, const AuxArgs* aux, int place_xstride) {
+                 const TileRec* tile_recs, const AuxArgs* aux, int place_xstride,
+                 const CullRec* cull_recs, const void* cull_wins) {
   const long long tiles_y = (f.sub_rows + kTile - 1) / kTile;
   if (tiles_y <= 0 || f.sub_w <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
@@ -1351,6 +1495,8 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
   // the cache is laid out for the ordered kernel's grid (launch_ray_fill), never dumped
   if ((ray_cache != nullptr) != (tile_recs != nullptr)) return -1;
   if (ray_cache && (!ordered || !g.tile_cost || dump)) return -1;
+  // the cull cache rides on the ray cache
+  if ((cull_recs != nullptr) != (cull_wins != nullptr) || (cull_recs && !ray_cache)) return -1;
   // the AUX kernels compute their directions and dump nothing; one plane at least
   if (aux && (dump || ray_cache || (!aux->depth && !aux->sphere && !aux->steps))) return -1;
   // the placing kernels: row-major, their directions computed, nothing dumped; the last output
@@ -1383,6 +1529,9 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                   : inl(k_trace_place_r<R, SS, false>, no_planes, place_xstride);
       } else if (aux) {
         list ? lst(k_trace_window_list_aux<R, SS>, *aux) : inl(k_trace_window_r_aux<R, SS>, *aux);
+      } else if (cull_recs) {
+        list ? lst(k_trace_window_list_cc<R, SS>, ray_cache, cull_recs, (const CullWinList*)cull_wins)
+             : inl(k_trace_window_r_cc<R, SS>, ray_cache, cull_recs, (const CullWin*)cull_wins);
       } else if (ray_cache) {
         list ? lst(k_trace_window_list_rc<R, SS>, ray_cache, tile_recs)
              : inl(k_trace_window_r_rc<R, SS>, ray_cache, tile_recs);

@@ -71,6 +71,7 @@ ABI_SYMBOLS = (
     "sfrt_world_render_subset", "sfrt_world_render_subset_aux",
     "sfrt_voxel_render_subset", "sfrt_voxel_render_subset_aux",
     "sfrt_world_render_views", "sfrt_world_render_views_aux",
+    "sfrt_world_cull_cache_stats",
 )
 
 SFRT_MAX_VIEWS = 1024
@@ -209,6 +210,8 @@ def lib() -> ctypes.CDLL:
         "sfrt_world_ray_cache_stats": ([W, P(ctypes.c_int64), P(ctypes.c_int64),
                                         P(ctypes.c_int64)], c_int),
         "sfrt_world_tile_record_bytes": ([W, P(ctypes.c_int64)], c_int),
+        "sfrt_world_cull_cache_stats": ([W, P(ctypes.c_int64), P(ctypes.c_int64),
+                                         P(ctypes.c_int64)], c_int),
         "sfrt_world_submit_frame": ([W, vp, P(ctypes.c_int64)], c_int),
         "sfrt_world_wait_frame": ([W, ctypes.c_int64], c_int),
         "sfrt_host_alloc": ([P(vp), ctypes.c_int64], c_int),
@@ -468,6 +471,15 @@ class World:
         b = ctypes.c_int64()
         _check(lib().sfrt_world_tile_record_bytes(self._h, ctypes.byref(b)), "tile_record_bytes")
         return b.value
+
+    def cull_cache_stats(self) -> dict:
+        """The cull cache's counters (sfrt_world_cull_cache_stats): launches preceded by a fill,
+        launches that loaded their culling from a cache filled earlier, and the device bytes the
+        cull caches hold now."""
+        f, h, b = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().sfrt_world_cull_cache_stats(self._h, ctypes.byref(f), ctypes.byref(h),
+                                                 ctypes.byref(b)), "cull_cache_stats")
+        return {"fills": f.value, "hits": h.value, "bytes": b.value}
 
     def set_scene(self, scene, width: int, height: int) -> None:
         """Load a scenes.Scene (spheres verbatim, camera pose) at width x height."""

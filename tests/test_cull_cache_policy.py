@@ -1,0 +1,21 @@
+"""The cull cache's policy (csrc/sfrt_raycache.h CullKey, CullCachePolicy: when a chain fills,
+reads or leaves its cache of per-tile culling masks and march windows) as a stand-alone host
+program, tests/native/cullcache_check.cpp, built with the host sanitizers: fill on the second
+identical key and read on the third, a miss and a later refill on every input of the cull, a
+texture slot that keeps the cache, invalidation with the ray cache, the budget, a takeover and a
+failed launch, the chain's buffers through counting allocators.  No GPU, no HIP."""
+import os
+import subprocess
+
+from conftest import ROOT
+
+
+def test_cull_cache_policy_native(tmp_path):
+    exe = tmp_path / "cullcache_check"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "sfml-software-raytracer_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "native", "cullcache_check.cpp"), "-o", str(exe)],
+                   check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "cullcache_check ok" in r.stdout, r.stdout + r.stderr

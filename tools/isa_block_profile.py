@@ -6,7 +6,9 @@
 
 KERNEL is one of: sphere (k_trace_window_r<4>, the headline's uncached kernel), sphere_rc
 (k_trace_window_r_rc<4, 0>: the same launch served from the ray cache and the tile records, which
-is what the headline's steady state runs), voxel (k_voxel_ordered), glsl (k_glsl_ordered).
+is what a walking camera's steady state runs), sphere_cc (k_trace_window_r_cc<4, 0>: the same
+launch with the cull loaded from the cull cache as well, the headline's steady state), voxel
+(k_voxel_ordered), glsl (k_glsl_ordered).
 
 Method.  The release kernel's assembly (hipcc -S of the product source, release flags plus
 -gline-tables-only, which only adds .loc directives: the kernel's instruction text is checked
@@ -55,6 +57,9 @@ KERNELS = {
     "sphere_rc": {"src": "sphere_trace.hip", "obj": "sphere_trace.o",
                   "symbol": "_ZN4sfrt12_GLOBAL__N_119k_trace_window_r_rcILi4ELi0EEEvNS_10InlineArgsEPKf"
                             "PKNS_7TileRecE"},
+    "sphere_cc": {"src": "sphere_trace.hip", "obj": "sphere_trace.o",
+                  "symbol": "_ZN4sfrt12_GLOBAL__N_119k_trace_window_r_ccILi4ELi0EEEvNS_10InlineArgsEPKf"
+                            "PKNS_7CullRecEPKNS_7CullWinE"},
     # k_voxel_ordered<false>: the launch without tile costs (the voxel default)
     "voxel": {"src": "voxel_trace.hip", "obj": "voxel_trace.o",
               "symbol": "_ZN4sfrt12_GLOBAL__N_115k_voxel_orderedILb0EEEvNS_8VoxFrameEii"},
@@ -376,7 +381,7 @@ def run(kind, frames=3):
         w, h = 3840, 2160
         wd.set_scene(scenes.lcg64(), w, h)
         buf = torch.empty(h, w * 4, dtype=torch.uint8, device="cuda")
-        # (sphere_rc: the three warm-up frames are the uncached one, the fill and a first read)
+        # (sphere_rc, sphere_cc: the three warm-up frames are the uncached one, the fill and a first read)
         measure(str(w * h + 256), f"{w}x{h} lcg64 pose (0,0), adaptive order (+ the sorter)",
                 lambda: wd.render_band(buf.data_ptr(), w * 4, 0, h, 0))
         wd.check()
@@ -591,7 +596,7 @@ def regions_sphere(blocks, kind="sphere"):
     }.items()}
     helpers = [("sort_tiles", "sorter"), ("shade_texel", "shade"), ("shade_rgba", "shade"),
                ("primary_dir", "ray_setup"), ("ray_cache_load", "ray_setup"),
-               ("tile_cone", "cull"), ("tile_rec_at", "cull"), ("cull_window", "cull"),
+               ("tile_cone", "cull"), ("tile_rec_at", "cull"), ("cull_rec_at", "cull"), ("cull_window", "cull"),
                ("cull_wave", "cull"),
                ("dist2", "visit_test"), ("pass_body_r", "pass_body"), ("zero_steps", "step_control")]
 
@@ -632,7 +637,8 @@ def regions_sphere(blocks, kind="sphere"):
 
 
 REGIONS = {"voxel": regions_voxel, "glsl": regions_glsl, "sphere": regions_sphere,
-           "sphere_rc": lambda blocks: regions_sphere(blocks, "sphere_rc")}
+           "sphere_rc": lambda blocks: regions_sphere(blocks, "sphere_rc"),
+           "sphere_cc": lambda blocks: regions_sphere(blocks, "sphere_cc")}
 
 
 def report(kind, counts_path, pmc_path):

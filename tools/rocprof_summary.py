@@ -27,10 +27,10 @@ import re
 
 def pixels_per_thread(kernel_name: str) -> int:
     """Pixels one work-item writes: R for k_trace_window_r<R> / k_trace_window_list<R> and
-    their _ss<R, SS> (samples) and _rc<R, SS> (ray cache) kernels
+    their _ss<R, SS> (samples), _rc<R, SS> (ray cache) and _cc<R, SS> (cull cache) kernels
     (round 1: k_trace_window_r<SLOTS, R, ...>), else 1."""
     m = re.search(r"k_trace_window_(?:r|list)<\s*(\d+)\s*>", kernel_name) or \
-        re.search(r"k_trace_window_(?:r|list)_(?:ss|rc)<\s*(\d+)\s*,", kernel_name) or \
+        re.search(r"k_trace_window_(?:r|list)_(?:ss|rc|cc)<\s*(\d+)\s*,", kernel_name) or \
         re.search(r"k_trace_window_r<\s*\d+\s*,\s*(\d+)", kernel_name)
     return int(m.group(1)) if m else 1
 
