@@ -372,12 +372,33 @@ SFRT_API int sfrt_world_cast_rays(sfrt_world* w, const float* dirs, const float*
  * later launches load it; any launch that changes one of them -- the library compares the values,
  * sphere by sphere -- culls for itself as before, so a walking camera or a sphere that moves
  * every frame never fills.  Same bytes either way.  These bytes count against the limit: a cull
- * cache that would take the world past it is not created.  See sfrt_world_cull_cache_stats. */
+ * cache that would take the world past it is not created.  See sfrt_world_cull_cache_stats.
+ * SFRT_OPT_HIT_CACHE_MB (512 = default; 0 = off; negative values return SFRT_E_INVALID): the
+ * device memory, in megabytes of 10^6 bytes per world (not MiB: the default then holds two
+ * streams' 4K frames, 2 x 132.7 MB, and leaves an 8K frame's 530.8 MB out, which would fit 512
+ * MiB), that the world may spend on the hit cache -- a budget of its own, beside
+ * SFRT_OPT_RAY_CACHE_MB's and not counted against it.  Where a ray's march ends and
+ * on which sphere depends on exactly what the cull cache depends on -- the ray's direction, the
+ * camera position, the sphere count and each sphere's centre and radius -- and not on the
+ * textures or the spheres' texture slots.  While a stream's launches read the cull cache, the
+ * second consecutive launch of one such state also writes each ray's march result (16 bytes per
+ * ray: 132.7 MB for a 4K frame, per stream that renders such frames; supersampled, per sample),
+ * and later launches of that state do not march at all: they shade from the stored results with
+ * the current textures and texture slots, the same bytes as a marching launch and the same
+ * status (a texel outside its texture included).  Any launch that changes the state renders as
+ * without the hit cache, so a walking or turning camera or a moving sphere never fills.  The hit
+ * cache lives on the cull cache: SFRT_OPT_RAY_CACHE_MB 0 turns it off with the rest, and whatever
+ * refills the directions or the cull cache drops it.  A hit cache that would take the world past
+ * the limit is not created (at the default an 8K frame's 530.8 MB: raise the option to 600 to
+ * serve such frames from it) and the launch stays on the cull cache; lowering the limit below what is held waits
+ * for the device and frees every hit cache.  sfrt_world_row_costs keeps answering from the last
+ * launch that marched.  See sfrt_world_hit_cache_stats. */
 #define SFRT_OPT_CULL 1
 #define SFRT_OPT_RAYS_PER_LANE 2
 #define SFRT_OPT_TILE_ORDER 3
 #define SFRT_OPT_SUPERSAMPLE 4
 #define SFRT_OPT_RAY_CACHE_MB 5
+#define SFRT_OPT_HIT_CACHE_MB 6
 SFRT_API int sfrt_world_set_option(sfrt_world* w, int option, int value);
 /* The current value of any of the options above (SFRT_OPT_SUPERSAMPLE: the factor 1, 2 or 4). */
 SFRT_API int sfrt_world_get_option(const sfrt_world* w, int option, int* value);
@@ -396,6 +417,13 @@ SFRT_API int sfrt_world_tile_record_bytes(const sfrt_world* w, int64_t* bytes);
  * cull caches hold now.  Not part of sfrt_world_ray_cache_stats' bytes. */
 SFRT_API int sfrt_world_cull_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits,
                                          int64_t* bytes);
+/* The hit cache's counters since the world was created (SFRT_OPT_HIT_CACHE_MB): *fills = launches
+ * that stored their march results, *hits = launches that shaded from stored results and did not
+ * march (each also counts as a cached frame of sfrt_world_ray_cache_stats and a hit of
+ * sfrt_world_cull_cache_stats), *bytes = device memory the world's hit caches hold now.  Not part
+ * of the other caches' bytes. */
+SFRT_API int sfrt_world_hit_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits,
+                                        int64_t* bytes);
 
 /* ---- stateless helpers ---- */
 /* UpdateSpheres ordering of an array in place (SphereWorld.cpp:199-212). */

@@ -304,6 +304,16 @@ class SphereWorld {
     check(sfrt_world_cull_cache_stats(w_, &s.fills, &s.hits, &s.bytes), "cull_cache_stats");
     return s;
   }
+  // SFRT_OPT_HIT_CACHE_MB (sfrt.h): MB (10^6 bytes) this world may spend on cached march results, 0 = off.
+  void SetHitCacheMB(int mib) { SetOption(SFRT_OPT_HIT_CACHE_MB, mib); }
+  int HitCacheMB() const { return GetOption(SFRT_OPT_HIT_CACHE_MB); }
+  // The hit cache's counters (sfrt.h sfrt_world_hit_cache_stats).
+  using HitCacheStats = CullCacheStats;  // the same three counters
+  HitCacheStats GetHitCacheStats() const {
+    HitCacheStats s{};
+    check(sfrt_world_hit_cache_stats(w_, &s.fills, &s.hits, &s.bytes), "hit_cache_stats");
+    return s;
+  }
   sfrt_world* handle() { return w_; }
 
  private:

@@ -24,6 +24,7 @@
 
 #include "sfrt_device.h"
 #include "sfrt_math.h"
+#include "sfrt_trace.h"  // kDiagnosticBuild
 
 #ifndef SFRT_EXP
 #define SFRT_EXP 0
@@ -99,6 +100,5 @@ struct DiagProbe {
 };
 
 using ActiveProbe = std::conditional_t<(SFRT_EXP != 0), DiagProbe<SFRT_EXP>, NoProbe>;
-constexpr bool kDiagnosticBuild = SFRT_EXP != 0;
 
 }  // namespace sfrt

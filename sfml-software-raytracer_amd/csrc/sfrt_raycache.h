@@ -11,6 +11,8 @@
 // tests/native/tilerec_check.cpp.
 // The cull cache (CullKey, CullCachePolicy, at the end) rides on the tile records: what each tile's
 // wave culls before it marches, under a key of its own (tests/native/cullcache_check.cpp).
+// The hit cache (HitRec, HitCachePolicy, after it) rides on the cull cache under the same key: what
+// each ray's march leaves the shading (tests/native/hitcache_check.cpp).
 #pragma once
 
 #include <cstdint>
@@ -220,6 +222,93 @@ struct CullCachePolicy {
       valid = true;
     } else if (ray == RayAction::kFill) {
       valid = false;  // the tile records were rewritten under this cache
+    }
+    prev = key;
+    have_prev = true;
+  }
+
+  void invalidate() {
+    valid = false;
+    have_prev = false;
+  }
+};
+
+// ---- The hit cache (DESIGN.md 5 "Hit cache") ----
+//
+// The march (sphere_trace.hip march_wave) reads the rays' directions, the camera position, first_l
+// and first_draw (a function of the rest), n, and the fields cx, cy, cz, r, s_pass of the records:
+// exactly what CullKey holds.  What it leaves the rest of the launch is, per ray, the position and
+// drawSphere, and whether the ray still moved when the trip guard ended the march (status bit 0).
+// While the key stays, every frame repeats the same march: a chain whose launches keep it stores
+// those results once -- from the _hf instantiation of the very kernels that march, no extra pass --
+// and the reading kernels (k_shade_hits) shade from them, with the launch's own textures and
+// texture slots, which the key does not hold.
+//
+// Per ray one 16-byte record, 16-byte aligned, indexed by tile number like TileRec and CullRec,
+// [tile][r][lane]: a wave moves 1 KiB contiguous per ray slot with one 16-byte access per lane.
+// Clamped edge duplicates included; supersampled, per sample.
+struct alignas(16) HitRec {
+  uint32_t px, py, pz;  // the position after the march, binary32 bit patterns
+  uint32_t draw;        // drawSphere (< n <= 1024) in the low bits; bit 31 (kHitRecMoving): the
+                        // ray's last step was > 0 when march_wave returned, which only the trip
+                        // guard kMaxIterations allows
+};
+static_assert(sizeof(HitRec) == 16 && alignof(HitRec) == 16, "one 16-byte access per ray");
+constexpr uint32_t kHitRecMoving = 0x80000000u;
+
+#if defined(__HIP__)  // the kernels' translation unit: the same helpers on both sides
+#define SFRT_HIT_HD __host__ __device__ __forceinline__
+#else
+#define SFRT_HIT_HD inline
+#endif
+SFRT_HIT_HD uint32_t hit_pack_draw(int draw, bool moving) {
+  return (uint32_t)draw | (moving ? kHitRecMoving : 0u);
+}
+SFRT_HIT_HD int hit_draw(uint32_t w) { return (int)(w & ~kHitRecMoving); }
+SFRT_HIT_HD bool hit_moving(uint32_t w) { return (w & kHitRecMoving) != 0; }
+SFRT_HIT_HD size_t hit_rec_at(int tile, int rays, int r, int lane) {
+  return ((size_t)tile * (size_t)rays + (size_t)r) * 64u + (size_t)lane;
+}
+#undef SFRT_HIT_HD
+
+inline long long hit_cache_bytes(long long tiles, int rays) {
+  return tiles * rays * 64 * (long long)sizeof(HitRec);
+}
+
+// One chain's hit cache, decided after the cull cache's action for the same launch.  It is filled
+// by a launch that runs the cull-cached kernel anyway (cull action kRead or kFill) on the second
+// consecutive launch of a key, read by a launch that reads the cull cache under the cached key,
+// and never valid without a valid cull cache: whatever refills the directions or the cull cache
+// drops it.  kTrace: the launch runs what it would run without a hit cache.
+struct HitCachePolicy {
+  CullKey cached;
+  bool valid = false;
+  CullKey prev;
+  bool have_prev = false;
+
+  // cull: the cull cache's decision for this launch.  bytes: what the records of `key` need; held:
+  // the chain's own hit buffer now; others: the hit bytes of the world's other chains; budget:
+  // SFRT_OPT_HIT_CACHE_MB in bytes (a budget of its own).
+  RayAction decide(const CullKey& key, RayAction cull, long long bytes, long long held,
+                   long long others, long long budget) const {
+    if (budget <= 0 || bytes <= 0 || cull == RayAction::kTrace) return RayAction::kTrace;
+    if (cull == RayAction::kRead && valid && cached.same(key)) return RayAction::kRead;
+    if (!have_prev || !prev.same(key)) return RayAction::kTrace;
+    const long long after = bytes > held ? bytes : held;
+    return others + after <= budget ? RayAction::kFill : RayAction::kTrace;
+  }
+
+  // ray, cull, a: the three decisions of the launch; queued = false: the launch or a fill failed.
+  void commit(const CullKey& key, RayAction ray, RayAction cull, RayAction a, bool queued) {
+    if (!queued) {
+      invalidate();
+      return;
+    }
+    if (a == RayAction::kFill) {
+      cached = key;
+      valid = true;
+    } else if (ray == RayAction::kFill || cull == RayAction::kFill) {
+      valid = false;  // the caches under this one were rewritten
     }
     prev = key;
     have_prev = true;

@@ -76,20 +76,34 @@ struct TileSched {
   CacheBuf cull_recs;  // the per-tile records (cull_rec_bytes)
   CacheBuf cull_wins;  // the per-lane windows (cull_win_bytes)
 
+  // The chain's hit cache (sfrt_raycache.h HitCachePolicy): each ray's march result, one more
+  // buffer under the same rules, on a budget of its own.  It lives on the cull cache: whatever
+  // invalidates, refills or frees that does the same to it.
+  HitCachePolicy hit_policy;
+  CacheBuf hit_recs;  // the per-ray records (hit_cache_bytes)
+
   long long cull_bytes() const { return cull_recs.bytes + cull_wins.bytes; }
 
   void invalidate_caches() {
     ray_policy.invalidate();
     cull_policy.invalidate();
+    hit_policy.invalidate();
   }
 
-  // All four buffers freed by the host (the device has drained, or the chain is going away).
+  // The hit records alone freed by the host (the device has drained): SFRT_OPT_HIT_CACHE_MB lowered.
+  void release_hit_cache() {
+    hit_recs.release([](void* p) { return hipFree(p) == hipSuccess; });
+    hit_policy.invalidate();
+  }
+
+  // All five buffers freed by the host (the device has drained, or the chain is going away).
   void release_ray_cache() {
     const auto free_now = [](void* p) { return hipFree(p) == hipSuccess; };
     ray_dirs.release(free_now);
     ray_recs.release(free_now);
     cull_recs.release(free_now);
     cull_wins.release(free_now);
+    hit_recs.release(free_now);
     invalidate_caches();
   }
 
@@ -180,6 +194,16 @@ struct TileSched {
     last_stream = s;
     have_last = true;
     return hipSuccess;
+  }
+
+  // After a launch that reads the hit cache was queued on s: it was linked into nothing (no order,
+  // no classes, no sorter), so the chain does not advance -- the next marching launch continues it
+  // as if the reading launches had not happened -- and only the stream is remembered (begin() has
+  // waited for the device if another stream had the chain).  A failed one goes through end().
+  void end_reading(hipStream_t s) {
+    pending_key = 0;
+    last_stream = s;
+    have_last = true;
   }
 
   void reset() {

@@ -25,6 +25,12 @@ constexpr int kPairMinSpheres = 16;  // above this, n <= 64 frames use 16x8 tile
 #ifndef SFRT_SLOTS
 #define SFRT_SLOTS 2
 #endif
+// -DSFRT_EXP=<bits>: a diagnostic build (sfrt_probe.h; wrong bytes by design), said once for the
+// kernels and the host: such a build never reads the hit cache, it exists to time the march.
+#ifndef SFRT_EXP
+#define SFRT_EXP 0
+#endif
+constexpr bool kDiagnosticBuild = SFRT_EXP != 0;
 constexpr int kSlots = SFRT_SLOTS;  // culled spheres held in SGPRs per wave (2: best of 0-4, 6; profiles/ab/r2_ab32)
 
 // One sphere as the kernel reads it: 32 B, one s_load_dwordx8.
@@ -93,6 +99,7 @@ struct InlineArgs {
 
 struct TileRec;  // sfrt_raycache.h
 struct CullRec;  // sfrt_raycache.h
+struct HitRec;   // sfrt_raycache.h
 
 struct PixelDump {
   float pos[3];
@@ -166,11 +173,18 @@ int launch_cast_rays(const FrameRec& f, const SphereRec* host_spheres, const Ray
 // filled for this very f and these very records by launch_cull_fill earlier on the same stream --
 // the launch then loads each tile's culling mask, march windows and grid position from it and
 // reads no tile record.
+// hit_recs, hit_mode (null and 0, or set and 1 or 2; with cull_recs only): the chain's hit cache
+// (hit_cache_bytes(tiles, rays) bytes, sfrt_raycache.h).  1: the cull-cached launch also stores each
+// ray's march result there.  2: the reading launch -- no march; one wave per tile in tile-number
+// order shades from the records filled for this very key by a mode-1 launch earlier on the same
+// stream.  It takes no part in the tile order: f's tile_order, tile_cost, prev_cost and next_order
+// are ignored (the caller links nothing), and ray_cache and cull_wins are not read.
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump = nullptr, void* done_event = nullptr,
                  const float* ray_cache = nullptr, const TileRec* tile_recs = nullptr,
                  const AuxArgs* aux = nullptr, int place_xstride = 0,
-                 const CullRec* cull_recs = nullptr, const void* cull_wins = nullptr);
+                 const CullRec* cull_recs = nullptr, const void* cull_wins = nullptr,
+                 HitRec* hit_recs = nullptr, int hit_mode = 0);
 // Fills ray_cache (ray_cache_bytes(tiles, rays) bytes, sfrt_raycache.h, of the grid
 // trace_tile_key names) with the primary directions of f's rays, tile-major, and tile_recs
 // (tile_rec_bytes(tiles) bytes) with the tiles' records.

@@ -134,6 +134,7 @@ struct sfrt_world {
   int tile_order_on = 1;  // SFRT_OPT_TILE_ORDER
   int ss = 0;             // SFRT_OPT_SUPERSAMPLE: log2 of the factor S (0, 1, 2)
   int ray_cache_mb = 512;  // SFRT_OPT_RAY_CACHE_MB: MiB of ray caches over all chains (0: off)
+  int hit_cache_mb = 512;  // SFRT_OPT_HIT_CACHE_MB: MB (10^6 bytes) of hit caches over all chains (0: off)
   // --- device resources ---
   hipStream_t stream = nullptr;
   uint32_t* d_tex = nullptr;  // texture atlas: every loaded slot, back to back
@@ -167,6 +168,16 @@ struct sfrt_world {
   const sfrt::CullRec* cull_recs = nullptr;
   const void* cull_wins = nullptr;
   int64_t cull_fills = 0, cull_hits = 0;
+  // The hit cache (sfrt_raycache.h HitCachePolicy) of that launch, decided after the cull cache
+  // under the same key: kFill -- the launch runs the _hf kernel and stores its march results in
+  // hit_recs; kRead -- it shades from them and takes no part in the tile order (sched_end).
+  // Counters: sfrt_world_hit_cache_stats.
+  sfrt::RayAction hit_action = sfrt::RayAction::kTrace;
+  sfrt::HitRec* hit_recs = nullptr;
+  int64_t hit_fills = 0, hit_hits = 0;
+  int hit_mode() const {
+    return hit_action == sfrt::RayAction::kRead ? 2 : hit_action == sfrt::RayAction::kFill ? 1 : 0;
+  }
   // Device copies of the sphere records for launches that read them from memory
   // (> 64 spheres, trace_points): a ring of slots, each with pinned staging and
   // the event of the last launch that read it, so a slot is never overwritten
@@ -452,6 +463,8 @@ struct sfrt_world {
     cull_recs = nullptr;
     cull_wins = nullptr;
     cull_action = sfrt::RayAction::kTrace;
+    hit_recs = nullptr;
+    hit_action = sfrt::RayAction::kTrace;
     if (!aux && tile_order_on == 1 && p.tile_cost && sched.pending_key != 0) {
       ray_active = true;
       ray_key = make_ray_key(f, key);
@@ -481,11 +494,28 @@ struct sfrt_world {
       if (cull_action == sfrt::RayAction::kFill &&
           !cull_fill(sched, f, recs, rec_bytes, win_bytes, s)) {
         sched.cull_policy.invalidate();  // the tile records are whole: the launch reads them
+        sched.hit_policy.invalidate();
         cull_action = sfrt::RayAction::kTrace;
       }
       if (cull_action != sfrt::RayAction::kTrace) {
         cull_recs = (const sfrt::CullRec*)sched.cull_recs.ptr;
         cull_wins = sched.cull_wins.ptr;
+      }
+      // The hit cache, on top of the cull cache this launch reads (or has just filled), under the
+      // same key and a budget of its own.  The diagnostic builds exist to time the march: never.
+      const long long hit_bytes = sfrt::hit_cache_bytes(tiles, (int)((key >> 56) & 7));
+      hit_action = sched.hit_policy.decide(cull_key, cull_action, hit_bytes, sched.hit_recs.bytes,
+                                           hit_bytes_held() - sched.hit_recs.bytes,
+                                           sfrt::kDiagnosticBuild ? 0 : hit_budget_bytes());
+      if (hit_action == sfrt::RayAction::kFill && !reserve_on(sched.hit_recs, hit_bytes, s)) {
+        sched.hit_policy.invalidate();  // no memory for it: the launch stays on the cull-cache path
+        hit_action = sfrt::RayAction::kTrace;
+      }
+      if (hit_action != sfrt::RayAction::kTrace) hit_recs = (sfrt::HitRec*)sched.hit_recs.ptr;
+      // A reading launch marches nothing and takes no part in the tile order: nothing is linked.
+      if (hit_action == sfrt::RayAction::kRead) {
+        sfrt::TileSchedPtrs{}.link(f);
+        f.order_dilate = 0;
       }
     }
     return SFRT_OK;
@@ -524,6 +554,14 @@ struct sfrt_world {
   long long cull_bytes_held() const {
     long long held = 0;
     for (const sfrt::TileSched& c : scheds.chain) held += c.cull_bytes();
+    return held;
+  }
+  // SFRT_OPT_HIT_CACHE_MB in bytes: megabytes of 10^6 (sfrt.h says why), unlike the ray cache's MiB.
+  long long hit_budget_bytes() const { return (long long)hit_cache_mb * 1000000ll; }
+  // What SFRT_OPT_HIT_CACHE_MB limits, and nothing else does.
+  long long hit_bytes_held() const {
+    long long held = 0;
+    for (const sfrt::TileSched& c : scheds.chain) held += c.hit_recs.bytes;
     return held;
   }
   // Everything SFRT_OPT_RAY_CACHE_MB limits: the directions and the cull caches.
@@ -570,6 +608,8 @@ struct sfrt_world {
     sched.cull_recs.release(free_on_s);
     sched.cull_wins.release(free_on_s);
     sched.cull_policy.valid = false;
+    sched.hit_recs.release(free_on_s);  // the hit cache lives on the cull cache
+    sched.hit_policy.valid = false;
   }
   // The chain's cull cache likewise, filled for f and recs on s from the chain's tile records
   // (valid, or filled earlier on s for this launch).  false: the launch culls for itself.
@@ -588,12 +628,35 @@ struct sfrt_world {
     for (sfrt::TileSched& c : scheds.chain) c.release_ray_cache();
     return SFRT_OK;
   }
+  // SFRT_OPT_HIT_CACHE_MB lowered below what the chains hold: every hit cache goes, likewise.
+  int hit_release_all() {
+    HIP_TRY(hipDeviceSynchronize());
+    for (sfrt::TileSched& c : scheds.chain) c.release_hit_cache();
+    return SFRT_OK;
+  }
 
   // After launch_trace for f returned (queued = false: it failed).
   int sched_end(const sfrt::FrameRec& f, hipStream_t s, bool queued) {
     sfrt::TileSchedPtrs p;
     p.tile_cost = f.tile_cost;
     sfrt::TileSched& sched = scheds.chain[cur_chain];
+    if (queued && hit_action == sfrt::RayAction::kRead) {
+      // A launch that read the hit cache: the chain does not advance, and last_fill and the
+      // chain's camera stay the last marching launch's (their classes are this frame's too: the
+      // key is equal).  The three policies are committed as for a reading launch.
+      sched.end_reading(s);
+      sched.ray_policy.commit(ray_key, ray_action, true);
+      ray_cached_frames++;
+      sched.cull_policy.commit(cull_key, ray_action, cull_action, true);
+      cull_hits++;
+      sched.hit_policy.commit(cull_key, ray_action, cull_action, hit_action, true);
+      hit_hits++;
+      return SFRT_OK;
+    }
+    if (!queued && hit_action == sfrt::RayAction::kRead) {  // linked into nothing: end() would pass it by
+      sched.reset();
+      sched.invalidate_caches();
+    }
     HIP_TRY(sched.end(p, s, queued));
     if (!queued) {
       chain_cam[cur_chain].valid = false;
@@ -607,6 +670,8 @@ struct sfrt_world {
       sched.cull_policy.commit(cull_key, ray_action, cull_action, true);
       if (cull_action == sfrt::RayAction::kFill) cull_fills++;
       if (cull_action == sfrt::RayAction::kRead) cull_hits++;
+      sched.hit_policy.commit(cull_key, ray_action, cull_action, hit_action, true);
+      if (hit_action == sfrt::RayAction::kFill) hit_fills++;
     }
     if (sched.committed) {
       chain_cam[cur_chain] = ChainCam{true, cam, f.sub_row0};
@@ -956,6 +1021,18 @@ int sfrt_world_set_option(sfrt_world* w, int option, int value) {
     w->ray_cache_mb = value;
     return SFRT_OK;
   }
+  if (option == SFRT_OPT_HIT_CACHE_MB) {
+    if (value < 0) return SFRT_E_INVALID;
+    if ((long long)value * 1000000ll < w->hit_bytes_held()) {
+      sfrt::DeviceGuard g(w->device);
+      const int rc = w->hit_release_all();
+      if (rc) return rc;
+    }
+    if (value == 0)
+      for (sfrt::TileSched& c : w->scheds.chain) c.hit_policy.invalidate();
+    w->hit_cache_mb = value;
+    return SFRT_OK;
+  }
   return SFRT_E_INVALID;
 }
 
@@ -978,6 +1055,15 @@ int sfrt_world_cull_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hi
   return SFRT_OK;
 }
 
+int sfrt_world_hit_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits, int64_t* bytes) {
+  if (!w || !fills || !hits || !bytes) return SFRT_E_INVALID;
+  std::lock_guard<std::mutex> lk(w->mu);
+  *fills = w->hit_fills;
+  *hits = w->hit_hits;
+  *bytes = w->hit_bytes_held();
+  return SFRT_OK;
+}
+
 int sfrt_world_tile_record_bytes(const sfrt_world* w, int64_t* bytes) {
   if (!w || !bytes) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
@@ -994,6 +1080,7 @@ int sfrt_world_get_option(const sfrt_world* w, int option, int* value) {
     case SFRT_OPT_TILE_ORDER: *value = w->tile_order_on; return SFRT_OK;
     case SFRT_OPT_SUPERSAMPLE: *value = 1 << w->ss; return SFRT_OK;
     case SFRT_OPT_RAY_CACHE_MB: *value = w->ray_cache_mb; return SFRT_OK;
+    case SFRT_OPT_HIT_CACHE_MB: *value = w->hit_cache_mb; return SFRT_OK;
     default: return SFRT_E_INVALID;
   }
 }
@@ -1124,7 +1211,7 @@ static int render_band_body(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes
   if ((rc = w->sched_end(f, s, sfrt::launch_trace(f, recs.data(), s, nullptr, w->ring_event(),
                                                   w->ray_cache, w->tile_recs,
                                                   with_aux ? &a : nullptr, 0, w->cull_recs,
-                                                  w->cull_wins) == 0)))
+                                                  w->cull_wins, w->hit_recs, w->hit_mode()) == 0)))
     return rc;
   if ((rc = w->launched_with())) return rc;
   return SFRT_OK;
@@ -1550,7 +1637,7 @@ int sfrt_world_submit_frame(sfrt_world* w, uint8_t* pixels, int64_t* ticket) {
   if ((rc = w->sched_end(f, w->stream,
                          sfrt::launch_trace(f, recs.data(), w->stream, nullptr, w->ring_event(),
                                             w->ray_cache, w->tile_recs, nullptr, 0, w->cull_recs,
-                                            w->cull_wins) == 0)))
+                                            w->cull_wins, w->hit_recs, w->hit_mode()) == 0)))
     return rc;
   if ((rc = w->launched_with())) return rc;
   HIP_TRY(hipEventRecord(slot.rendered, w->stream));

@@ -477,6 +477,46 @@ __device__ __forceinline__ size_t cull_win_at(int tile, int lane) {
   return (size_t)tile * 64u + (size_t)lane;
 }
 
+// The hit cache (sfrt_raycache.h HitRec; DESIGN.md 5 "Hit cache"): what march_wave leaves a tile's
+// rays, [tile][r][lane], stored by the _hf kernels right after their march (plain vector stores,
+// one 16-byte store per ray slot: 1 KiB contiguous per wave) and loaded by the k_shade_hits
+// kernels, R loads back to back.  The buffer is written only by the _hf launch that precedes the
+// reading launches on its stream.
+template <int R>
+__device__ __forceinline__ void hit_store(HitRec* __restrict__ hr, int tile, int lane,
+                                          const float (&px)[R], const float (&py)[R],
+                                          const float (&pz)[R], const int (&draw)[R],
+                                          const float (&mv)[R]) {
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    uint4 v;
+    v.x = __float_as_uint(px[r]);
+    v.y = __float_as_uint(py[r]);
+    v.z = __float_as_uint(pz[r]);
+    v.w = hit_pack_draw(draw[r], mv[r] > 0.0f);
+    *(uint4*)(hr + hit_rec_at(tile, R, r, lane)) = v;
+  }
+}
+// Returns whether some ray of the lane still moved at the guard.
+template <int R>
+__device__ __forceinline__ bool hit_load(const HitRec* __restrict__ hr, int tile, int lane,
+                                         float (&px)[R], float (&py)[R], float (&pz)[R],
+                                         int (&draw)[R]) {
+  uint4 v[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) v[r] = *(const uint4*)(hr + hit_rec_at(tile, R, r, lane));
+  bool moving = false;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    px[r] = __uint_as_float(v[r].x);
+    py[r] = __uint_as_float(v[r].y);
+    pz[r] = __uint_as_float(v[r].z);
+    draw[r] = hit_draw(v[r].w);
+    moving = moving || hit_moving(v[r].w);
+  }
+  return moving;
+}
+
 // L = +0 for a lane's R rays at the start of a march step, two registers per
 // v_mov_b64 (left to itself the compiler copies one zero register into three
 // others and then pairs them: five moves a step for R = 4, not two).
@@ -782,12 +822,20 @@ __device__ __forceinline__ Rays<R> march_wave(const FrameRec& f, const SphereRec
 // the tile's grid position are loaded from the chain's cull cache cr / cw (filled by k_cull_fill
 // for this launch's CullKey: the bits cull_wave gives) -- neither the tile record nor the sphere
 // records are read before the march.
+// HIT (implies CULLED; DESIGN.md 5 "Hit cache"): 1, the _hf kernels -- the CULLED launch, which
+// also stores each ray's march result in the chain's hit cache hr (hit_store), the bits the very
+// same march under the very same flags leaves; 2, the k_shade_hits kernels -- one wave per tile in
+// tile-number order (the grid is exactly the tiles: no sorter workgroup, no order lookup, no cost
+// store), the tile's grid position from its CullRec, the rays' positions and drawSphere loaded
+// from hr in place of the ray setup, the cull and the march, then the same shading tail: it is
+// this function's, so there is one copy of it and the marching kernels' code cannot move when
+// the reading kernels change.  A ray that still moved at the guard raises status bit 0 again.
 // PLACE (sfrt_world_render_subset): the subset goes in place into a whole frame --
 // compact column a (output pixel a >> SS) is stored xstride elements apart, the host having put
 // the subset's first pixel into f.out and yadd frame rows into f.out_pitch (the planes' pitches
 // likewise) -- where every other launch stores it compactly.  All else is the same.
 template <int R, bool LIST, bool DUMP, class P, int SS = 0, bool CACHED = false, bool AUX = false,
-          bool PLACE = false, bool CULLED = false>
+          bool PLACE = false, bool CULLED = false, int HIT = 0>
 __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
                                                     const SphereRec* __restrict__ sph,
                                                     DumpArgs dmp,
@@ -796,8 +844,10 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
                                                     AuxArgs aux = AuxArgs{},
                                                     [[maybe_unused]] int xstride = 1,
                                                     [[maybe_unused]] const CullRec* cr = nullptr,
-                                                    [[maybe_unused]] const CullLane<LIST>* cw = nullptr) {
+                                                    [[maybe_unused]] const CullLane<LIST>* cw = nullptr,
+                                                    [[maybe_unused]] HitRec* hr = nullptr) {
   static_assert(!CULLED || CACHED, "the cull cache rides on the ray cache");
+  static_assert(HIT == 0 || (CULLED && !DUMP && !AUX && !PLACE), "the hit cache rides on the cull cache");
   static_assert(!PLACE || (!DUMP && !CACHED), "the placing kernels compute their directions and dump nothing");
   static_assert(SS == 0 || !DUMP, "trace_points dumps the 1x pixel");
   static_assert(!CACHED || !DUMP, "the DUMP kernels compute their directions");
@@ -808,15 +858,17 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   // Adaptive tile order (sfrt_trace.h FrameRec): workgroup 0 may be the sorter.
   const int ntiles = f.tiles_x * ((f.sub_rows + kTile - 1) / kTile);
   int slot = (int)blockIdx.x;
-  if (f.prev_cost) {
-    if (blockIdx.x == 0) {
-      sort_tiles(f.prev_cost, ntiles, f.next_order, f.order_dilate != 0);
-      return;
+  if constexpr (HIT != 2) {
+    if (f.prev_cost) {
+      if (blockIdx.x == 0) {
+        sort_tiles(f.prev_cost, ntiles, f.next_order, f.order_dilate != 0);
+        return;
+      }
+      slot -= 1;
     }
-    slot -= 1;
   }
-  uint32_t cls;  // the tile's class in the order (sfrt_device.h slot_tile)
-  const int tile = slot_tile(f.tile_order, slot, ntiles, cls);
+  [[maybe_unused]] uint32_t cls;  // the tile's class in the order (sfrt_device.h slot_tile)
+  const int tile = HIT == 2 ? slot : slot_tile(f.tile_order, slot, ntiles, cls);
   int tile_x, tile_y;
   [[maybe_unused]] TileRec trec;
   [[maybe_unused]] CullRec crec;
@@ -843,63 +895,75 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   [[maybe_unused]] const int j = CACHED ? 0 : subset_index<SS>(f.ystart, f.yadd, bc);
   const float l0 = f.first_l;
   Rays<R> ray;  // iters: DUMP and AUX only, the host's first trip included
-  if constexpr (CULLED) cwin = cw[cull_win_at(tile, lane)];  // beside the directions' loads
-  if constexpr (CACHED) ray_cache_load<R>(rc, tile, lane, ray.dx, ray.dy, ray.dz);
+  uint64_t m_end = 0;  // the wave's culling mask, for the probe's tile_end
+  if constexpr (HIT == 2) {
+    // every lane, clamped duplicates included: a duplicate is some stored pixel's ray again, so
+    // "some ray of the wave still moved" is what march_wave's own test saw
+    const bool moving = hit_load<R>(hr, tile, lane, ray.px, ray.py, ray.pz, ray.draw);
+    if (__builtin_amdgcn_ballot_w64(moving) != 0 && lane == 0) atomicOr(f.status, 1);
+  } else {
+    if constexpr (CULLED) cwin = cw[cull_win_at(tile, lane)];  // beside the directions' loads
+    if constexpr (CACHED) ray_cache_load<R>(rc, tile, lane, ray.dx, ray.dy, ray.dz);
 #pragma unroll
-  for (int r = 0; r < R; r++) {
-    if constexpr (!CACHED) {
-      const int a = tile_x * R * kTile + r * kTile + (lane & 7);
-      const int ac = a < f.sub_w ? a : f.sub_w - 1;
-      primary_dir(f, subset_index<SS>(f.xstart, f.xadd, ac), j, ray.dx[r], ray.dy[r], ray.dz[r]);
+    for (int r = 0; r < R; r++) {
+      if constexpr (!CACHED) {
+        const int a = tile_x * R * kTile + r * kTile + (lane & 7);
+        const int ac = a < f.sub_w ? a : f.sub_w - 1;
+        primary_dir(f, subset_index<SS>(f.xstart, f.xadd, ac), j, ray.dx[r], ray.dy[r], ray.dz[r]);
+      }
+      ray.px[r] = f.cam[0] + ray.dx[r] * l0;
+      ray.py[r] = f.cam[1] + ray.dy[r] * l0;
+      ray.pz[r] = f.cam[2] + ray.dz[r] * l0;
+      ray.draw[r] = f.first_draw;
+      ray.iters[r] = 1;
+      ray.mv[r] = l0 > 0.0f ? 1.0f : 0.0f;
+      ray.tacc[r] = l0;  // along-ray distance marched (binary32 sum of the steps)
     }
-    ray.px[r] = f.cam[0] + ray.dx[r] * l0;
-    ray.py[r] = f.cam[1] + ray.dy[r] * l0;
-    ray.pz[r] = f.cam[2] + ray.dz[r] * l0;
-    ray.draw[r] = f.first_draw;
-    ray.iters[r] = 1;
-    ray.mv[r] = l0 > 0.0f ? 1.0f : 0.0f;
-    ray.tacc[r] = l0;  // along-ray distance marched (binary32 sum of the steps)
-  }
-  // The windows are first used inside the march's window path, and left alone the compiler sinks
-  // their load down there; a use here keeps it above, ahead of the directions' loads, whose
-  // arrival (in order) the positions above have already waited for.  R >= 3 only (the wide
-  // tiles of large frames): 4K 64 spheres 122.7 -> 122.1 us with it; at R = 2 a wave with at
-  // most kSlots culled spheres never reads its windows, and loading them for every wave cost
-  // the 1080p 10-sphere frame 3 % (profiles/ab/r9c_ab3_window_load.txt).
-  if constexpr (CULLED && R >= 3) {
-    __asm__ volatile("" : : "v"(cwin.lo), "v"(cwin.hi));
-    if constexpr (LIST) __asm__ volatile("" : : "v"(cwin.cidx));
-  }
-  const bool windowed = f.cull && l0 > 0.0f;
-  bool culled = windowed;  // else every step visits every sphere
-  uint64_t m = 0;          // culled spheres (LIST: culled-list entries)
-  float lo = -__builtin_inff(), hi = __builtin_inff();
-  int cidx = lane;         // sphere of culled-list entry `lane`
-  if constexpr (CULLED) {
-    // No branch on `windowed`: for a launch that does not cull, k_cull_fill stored the values
-    // set above (under a branch the compiler sinks the window load into it, its whole latency
-    // exposed right before the march, and copies the rays' registers at the join).
-    m = (uint64_t)crec.m_lo | ((uint64_t)crec.m_hi << 32);
-    lo = cwin.lo;
-    hi = cwin.hi;
-    if constexpr (LIST) {
-      cidx = cwin.cidx;
-      culled = windowed && (crec.tile_y & kCullRecFull) == 0;
+    // The windows are first used inside the march's window path, and left alone the compiler sinks
+    // their load down there; a use here keeps it above, ahead of the directions' loads, whose
+    // arrival (in order) the positions above have already waited for.  R >= 3 only (the wide
+    // tiles of large frames): 4K 64 spheres 122.7 -> 122.1 us with it; at R = 2 a wave with at
+    // most kSlots culled spheres never reads its windows, and loading them for every wave cost
+    // the 1080p 10-sphere frame 3 % (profiles/ab/r9c_ab3_window_load.txt).
+    if constexpr (CULLED && R >= 3) {
+      __asm__ volatile("" : : "v"(cwin.lo), "v"(cwin.hi));
+      if constexpr (LIST) __asm__ volatile("" : : "v"(cwin.cidx));
     }
-  } else if (windowed) {
-    Cone cone;
-    if constexpr (CACHED) {
-      cone.ax = trec.ax; cone.ay = trec.ay; cone.az = trec.az;
-      cone.sin_t = trec.sin_t; cone.cos_t = trec.cos_t;
-      cone.wide = trec.wide != 0;
-    } else {
-      cone = tile_cone<R, SS>(f, tile_x, tile_y, lane, ray.dx, ray.dy, ray.dz);
+    const bool windowed = f.cull && l0 > 0.0f;
+    bool culled = windowed;  // else every step visits every sphere
+    uint64_t m = 0;          // culled spheres (LIST: culled-list entries)
+    float lo = -__builtin_inff(), hi = __builtin_inff();
+    int cidx = lane;         // sphere of culled-list entry `lane`
+    if constexpr (CULLED) {
+      // No branch on `windowed`: for a launch that does not cull, k_cull_fill stored the values
+      // set above (under a branch the compiler sinks the window load into it, its whole latency
+      // exposed right before the march, and copies the rays' registers at the join).
+      m = (uint64_t)crec.m_lo | ((uint64_t)crec.m_hi << 32);
+      lo = cwin.lo;
+      hi = cwin.hi;
+      if constexpr (LIST) {
+        cidx = cwin.cidx;
+        culled = windowed && (crec.tile_y & kCullRecFull) == 0;
+      }
+    } else if (windowed) {
+      Cone cone;
+      if constexpr (CACHED) {
+        cone.ax = trec.ax; cone.ay = trec.ay; cone.az = trec.az;
+        cone.sin_t = trec.sin_t; cone.cos_t = trec.cos_t;
+        cone.wide = trec.wide != 0;
+      } else {
+        cone = tile_cone<R, SS>(f, tile_x, tile_y, lane, ray.dx, ray.dy, ray.dz);
+      }
+      cull_wave<LIST>(f, sph, cone, lane, culled, m, lo, hi, cidx);
     }
-    cull_wave<LIST>(f, sph, cone, lane, culled, m, lo, hi, cidx);
+    ray = march_wave<R, LIST, DUMP || AUX>(f, sph, lane, probe, culled, m, lo, hi, cidx, ray);
+    if constexpr (HIT == 1) hit_store<R>(hr, tile, lane, ray.px, ray.py, ray.pz, ray.draw, ray.mv);
+    m_end = m;
   }
-  ray = march_wave<R, LIST, DUMP || AUX>(f, sph, lane, probe, culled, m, lo, hi, cidx, ray);
-  const int trips = ray.trips;
-  if (f.tile_cost && lane == 0) store_cost(f.tile_cost, tile, tile_bucket((uint32_t)trips), cls, f.cost_diff);
+  const int trips = HIT == 2 ? 0 : ray.trips;  // (2: no march; `ray` holds the loaded results only)
+  if constexpr (HIT != 2) {
+    if (f.tile_cost && lane == 0) store_cost(f.tile_cost, tile, tile_bucket((uint32_t)trips), cls, f.cost_diff);
+  }
   // Pixel (a, b) of ray r, recomputed here from a fresh lane id (mbcnt, so that the
   // compiler does not reuse the kernel entry's values): kept from there, the columns sat
   // in registers through the whole march, and at R = 4 one of them was spilled.
@@ -1013,7 +1077,7 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
       }
     }
   }
-  probe.tile_end(px_out(0), lane_s, valid(0), trips, slot, m);
+  probe.tile_end(px_out(0), lane_s, valid(0), trips, slot, m_end);
 }
 
 // n <= 64: the records travel in the kernel-argument segment.  8 waves/SIMD: <= 64
@@ -1135,6 +1199,37 @@ __global__ __launch_bounds__(64) void k_trace_window_list_cc(FrameRec f,
                                                              const CullRec* cr, const CullWinList* cw) {
   trace_tile_window_r<R, true, false, ActiveProbe, SS, true, false, false, true>(
       f, f.spheres, DumpArgs{}, rc, nullptr, AuxArgs{}, 1, cr, cw);
+}
+
+// The hit cache's kernels (sfrt_raycache.h HitCachePolicy).  The _hf kernels are the _cc ones that
+// also store their rays' march results (HIT = 1; they run once per key, so their occupancy is
+// left to the compiler); k_shade_hits[_list] shade a frame from those results (HIT = 2: no march,
+// see trace_tile_window_r), the records in the arguments or, n > 64, in the device ring.
+template <int R, int SS>
+__global__ __launch_bounds__(64) void k_trace_window_r_hf(InlineArgs args, const float* __restrict__ rc,
+                                                          const CullRec* cr, const CullWin* cw,
+                                                          HitRec* __restrict__ hr) {
+  trace_tile_window_r<R, false, false, ActiveProbe, SS, true, false, false, true, 1>(
+      args.f, args.s, DumpArgs{}, rc, nullptr, AuxArgs{}, 1, cr, cw, hr);
+}
+template <int R, int SS>
+__global__ __launch_bounds__(64) void k_trace_window_list_hf(FrameRec f, const float* __restrict__ rc,
+                                                             const CullRec* cr, const CullWinList* cw,
+                                                             HitRec* __restrict__ hr) {
+  trace_tile_window_r<R, true, false, ActiveProbe, SS, true, false, false, true, 1>(
+      f, f.spheres, DumpArgs{}, rc, nullptr, AuxArgs{}, 1, cr, cw, hr);
+}
+template <int R, int SS>
+__global__ __launch_bounds__(64, 8) void k_shade_hits(InlineArgs args, const CullRec* cr,
+                                                      const HitRec* __restrict__ hr) {
+  trace_tile_window_r<R, false, false, NoProbe, SS, true, false, false, true, 2>(
+      args.f, args.s, DumpArgs{}, nullptr, nullptr, AuxArgs{}, 1, cr, nullptr, const_cast<HitRec*>(hr));
+}
+template <int R, int SS>
+__global__ __launch_bounds__(64, 8) void k_shade_hits_list(FrameRec f, const CullRec* cr,
+                                                           const HitRec* __restrict__ hr) {
+  trace_tile_window_r<R, true, false, NoProbe, SS, true, false, false, true, 2>(
+      f, f.spheres, DumpArgs{}, nullptr, nullptr, AuxArgs{}, 1, cr, nullptr, const_cast<HitRec*>(hr));
 }
 
 // The DUMP instantiations of both (sfrt_world_trace_points): the shipped march and
@@ -1472,18 +1567,26 @@ int launch_cull_fill(const FrameRec& f, const SphereRec* host_spheres, const Til
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump, void* done_event, const float* ray_cache,
                  const TileRec* tile_recs, const AuxArgs* aux, int place_xstride,
-                 const CullRec* cull_recs, const void* cull_wins) {
+                 const CullRec* cull_recs, const void* cull_wins, HitRec* hit_recs, int hit_mode) {
   const long long tiles_y = (f.sub_rows + kTile - 1) / kTile;
   if (tiles_y <= 0 || f.sub_w <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const bool ordered = f.tile_cost != nullptr;  // linked into the tile-order chain
+  // the hit cache rides on the cull cache: 1 fills it from the marching launch, 2 shades from it
+  if (hit_mode < 0 || hit_mode > 2 || (hit_mode != 0) != (hit_recs != nullptr)) return -1;
+  if (hit_mode && (!cull_recs || dump || aux || place_xstride || kDiagnosticBuild)) return -1;
+  // (2: the caller linked nothing of the tile order into f, but the grid is the ordered one)
+  const bool ordered = hit_mode == 2 || f.tile_cost != nullptr;  // linked into the tile-order chain
   const int rays = trace_rays(f, ordered);
   FrameRec g = f;
   g.tiles_x = (f.sub_w + rays * kTile - 1) / (rays * kTile);
   const long long tiles = tiles_y * g.tiles_x;
   long long key_tiles = 0;
   if (!ordered || trace_tile_key(f, &key_tiles) == 0 || key_tiles != tiles) {
+    if (hit_mode) return -1;  // the caches are laid out for the key's grid
     g.tile_order = nullptr; g.tile_cost = nullptr; g.prev_cost = nullptr;
+  }
+  if (hit_mode == 2) {  // no sorter workgroup, no order, no classes
+    g.tile_order = nullptr; g.tile_cost = nullptr; g.prev_cost = nullptr; g.next_order = nullptr;
   }
   // one wave per workgroup (a finished wave's slot refills at once), plus the
   // tile-order sorter (sfrt_trace.h FrameRec)
@@ -1494,7 +1597,7 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
   if (f.ss && (f.sub_w | f.sub_row0 | f.sub_rows) & ((1 << f.ss) - 1)) return -1;  // whole groups
   // the cache is laid out for the ordered kernel's grid (launch_ray_fill), never dumped
   if ((ray_cache != nullptr) != (tile_recs != nullptr)) return -1;
-  if (ray_cache && (!ordered || !g.tile_cost || dump)) return -1;
+  if (ray_cache && (!ordered || (!g.tile_cost && hit_mode != 2) || dump)) return -1;
   // the cull cache rides on the ray cache
   if ((cull_recs != nullptr) != (cull_wins != nullptr) || (cull_recs && !ray_cache)) return -1;
   // the AUX kernels compute their directions and dump nothing; one plane at least
@@ -1529,6 +1632,12 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                   : inl(k_trace_place_r<R, SS, false>, no_planes, place_xstride);
       } else if (aux) {
         list ? lst(k_trace_window_list_aux<R, SS>, *aux) : inl(k_trace_window_r_aux<R, SS>, *aux);
+      } else if (hit_mode == 2) {
+        list ? lst(k_shade_hits_list<R, SS>, cull_recs, (const HitRec*)hit_recs)
+             : inl(k_shade_hits<R, SS>, cull_recs, (const HitRec*)hit_recs);
+      } else if (hit_mode == 1) {
+        list ? lst(k_trace_window_list_hf<R, SS>, ray_cache, cull_recs, (const CullWinList*)cull_wins, hit_recs)
+             : inl(k_trace_window_r_hf<R, SS>, ray_cache, cull_recs, (const CullWin*)cull_wins, hit_recs);
       } else if (cull_recs) {
         list ? lst(k_trace_window_list_cc<R, SS>, ray_cache, cull_recs, (const CullWinList*)cull_wins)
              : inl(k_trace_window_r_cc<R, SS>, ray_cache, cull_recs, (const CullWin*)cull_wins);

@@ -25,6 +25,7 @@ SFRT_OPT_RAYS_PER_LANE = 2
 SFRT_OPT_TILE_ORDER = 3
 SFRT_OPT_SUPERSAMPLE = 4  # 1 (default), 2 or 4: S x S samples per pixel, box-filtered in the kernel
 SFRT_OPT_RAY_CACHE_MB = 5  # MiB per world for cached primary ray directions (512 default, 0 off)
+SFRT_OPT_HIT_CACHE_MB = 6  # MB (10^6 B) per world for cached march results, a budget of its own (512, 0 off)
 ERRORS = {
     0: "SFRT_OK", -1: "SFRT_E_INVALID", -2: "SFRT_E_EMPTY", -3: "SFRT_E_NO_TEXTURE",
     -4: "SFRT_E_TOO_MANY", -5: "SFRT_E_HIP", -6: "SFRT_E_MARCH_LIMIT", -7: "SFRT_E_TEXEL",
@@ -71,7 +72,7 @@ ABI_SYMBOLS = (
     "sfrt_world_render_subset", "sfrt_world_render_subset_aux",
     "sfrt_voxel_render_subset", "sfrt_voxel_render_subset_aux",
     "sfrt_world_render_views", "sfrt_world_render_views_aux",
-    "sfrt_world_cull_cache_stats",
+    "sfrt_world_cull_cache_stats", "sfrt_world_hit_cache_stats",
 )
 
 SFRT_MAX_VIEWS = 1024
@@ -212,6 +213,8 @@ def lib() -> ctypes.CDLL:
         "sfrt_world_tile_record_bytes": ([W, P(ctypes.c_int64)], c_int),
         "sfrt_world_cull_cache_stats": ([W, P(ctypes.c_int64), P(ctypes.c_int64),
                                          P(ctypes.c_int64)], c_int),
+        "sfrt_world_hit_cache_stats": ([W, P(ctypes.c_int64), P(ctypes.c_int64),
+                                        P(ctypes.c_int64)], c_int),
         "sfrt_world_submit_frame": ([W, vp, P(ctypes.c_int64)], c_int),
         "sfrt_world_wait_frame": ([W, ctypes.c_int64], c_int),
         "sfrt_host_alloc": ([P(vp), ctypes.c_int64], c_int),
@@ -479,6 +482,15 @@ class World:
         f, h, b = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         _check(lib().sfrt_world_cull_cache_stats(self._h, ctypes.byref(f), ctypes.byref(h),
                                                  ctypes.byref(b)), "cull_cache_stats")
+        return {"fills": f.value, "hits": h.value, "bytes": b.value}
+
+    def hit_cache_stats(self) -> dict:
+        """The hit cache's counters (sfrt_world_hit_cache_stats): launches that stored their march
+        results, launches that shaded from stored results without marching, and the device bytes
+        the hit caches hold now."""
+        f, h, b = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().sfrt_world_hit_cache_stats(self._h, ctypes.byref(f), ctypes.byref(h),
+                                                ctypes.byref(b)), "hit_cache_stats")
         return {"fills": f.value, "hits": h.value, "bytes": b.value}
 
     def set_scene(self, scene, width: int, height: int) -> None:

@@ -1,0 +1,21 @@
+"""The hit cache's policy and record (csrc/sfrt_raycache.h HitRec, HitCachePolicy: when a chain
+stores, reads or leaves its cache of per-ray march results) as a stand-alone host program,
+tests/native/hitcache_check.cpp, built with the host sanitizers: first frames, a miss and a later
+refill on every field of the key, what the key does not hold, refusals by the budget of its own and
+by the allocator, failed launches, a takeover, the chain that does not advance under reading
+launches, and the packing of drawSphere with the guard bit.  No GPU, no HIP."""
+import os
+import subprocess
+
+from conftest import ROOT
+
+
+def test_hit_cache_policy_native(tmp_path):
+    exe = tmp_path / "hitcache_check"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "sfml-software-raytracer_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "native", "hitcache_check.cpp"), "-o", str(exe)],
+                   check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "hitcache_check ok" in r.stdout, r.stdout + r.stderr

@@ -7,7 +7,9 @@
 KERNEL is one of: sphere (k_trace_window_r<4>, the headline's uncached kernel), sphere_rc
 (k_trace_window_r_rc<4, 0>: the same launch served from the ray cache and the tile records, which
 is what a walking camera's steady state runs), sphere_cc (k_trace_window_r_cc<4, 0>: the same
-launch with the cull loaded from the cull cache as well, the headline's steady state), voxel
+launch with the cull loaded from the cull cache as well: the steady state of a camera at rest with
+SFRT_OPT_HIT_CACHE_MB 0), sphere_hits (k_shade_hits<4, 0>: the same launch shaded from the hit cache,
+the headline's steady state), voxel
 (k_voxel_ordered), glsl (k_glsl_ordered).
 
 Method.  The release kernel's assembly (hipcc -S of the product source, release flags plus
@@ -60,6 +62,9 @@ KERNELS = {
     "sphere_cc": {"src": "sphere_trace.hip", "obj": "sphere_trace.o",
                   "symbol": "_ZN4sfrt12_GLOBAL__N_119k_trace_window_r_ccILi4ELi0EEEvNS_10InlineArgsEPKf"
                             "PKNS_7CullRecEPKNS_7CullWinE"},
+    "sphere_hits": {"src": "sphere_trace.hip", "obj": "sphere_trace.o",
+                    "symbol": "_ZN4sfrt12_GLOBAL__N_112k_shade_hitsILi4ELi0EEEvNS_10InlineArgsEPKNS_7CullRecE"
+                              "PKNS_6HitRecE"},
     # k_voxel_ordered<false>: the launch without tile costs (the voxel default)
     "voxel": {"src": "voxel_trace.hip", "obj": "voxel_trace.o",
               "symbol": "_ZN4sfrt12_GLOBAL__N_115k_voxel_orderedILb0EEEvNS_8VoxFrameEii"},
@@ -382,8 +387,15 @@ def run(kind, frames=3):
         wd.set_scene(scenes.lcg64(), w, h)
         buf = torch.empty(h, w * 4, dtype=torch.uint8, device="cuda")
         # (sphere_rc, sphere_cc: the three warm-up frames are the uncached one, the fill and a first read)
-        measure(str(w * h + 256), f"{w}x{h} lcg64 pose (0,0), adaptive order (+ the sorter)",
-                lambda: wd.render_band(buf.data_ptr(), w * 4, 0, h, 0))
+        # (sphere_hits: the uncached one, the one that stores the march results and a first reading one)
+        if kind == "sphere_hits":  # the reading launch has no sorter workgroup
+            measure(str(w * h), f"{w}x{h} lcg64 pose (0,0), shaded from the hit cache",
+                    lambda: wd.render_band(buf.data_ptr(), w * 4, 0, h, 0))
+        else:
+            if kind == "sphere_cc":  # (the hit cache would serve the steady state, where the library has it)
+                wd.set_option(getattr(sfrt, "SFRT_OPT_HIT_CACHE_MB", 6), 0)
+            measure(str(w * h + 256), f"{w}x{h} lcg64 pose (0,0), adaptive order (+ the sorter)",
+                    lambda: wd.render_band(buf.data_ptr(), w * 4, 0, h, 0))
         wd.check()
         wd.close()
     print(json.dumps({"tool": "tools/isa_block_profile.py run", "kernel": info["kernel"],
@@ -592,11 +604,12 @@ def regions_sphere(blocks, kind="sphere"):
         "fn_first": "const int lane = threadIdx.x & 63;\n  P probe;",
         "windowed": "const bool windowed = f.cull && l0 > 0.0f;",
         "march_call": "ray = march_wave<R, LIST, DUMP || AUX>(",
-        "fn_last": "probe.tile_end(px_out(0), lane_s, valid(0), trips, slot, m);",
+        "fn_last": "probe.tile_end(px_out(0), lane_s, valid(0), trips, slot, m_end);",
     }.items()}
     helpers = [("sort_tiles", "sorter"), ("shade_texel", "shade"), ("shade_rgba", "shade"),
                ("primary_dir", "ray_setup"), ("ray_cache_load", "ray_setup"),
                ("tile_cone", "cull"), ("tile_rec_at", "cull"), ("cull_rec_at", "cull"), ("cull_window", "cull"),
+               ("hit_load", "hit_load"), ("hit_store", "hit_store"),
                ("cull_wave", "cull"),
                ("dist2", "visit_test"), ("pass_body_r", "pass_body"), ("zero_steps", "step_control")]
 
@@ -638,7 +651,8 @@ def regions_sphere(blocks, kind="sphere"):
 
 REGIONS = {"voxel": regions_voxel, "glsl": regions_glsl, "sphere": regions_sphere,
            "sphere_rc": lambda blocks: regions_sphere(blocks, "sphere_rc"),
-           "sphere_cc": lambda blocks: regions_sphere(blocks, "sphere_cc")}
+           "sphere_cc": lambda blocks: regions_sphere(blocks, "sphere_cc"),
+           "sphere_hits": lambda blocks: regions_sphere(blocks, "sphere_hits")}
 
 
 def report(kind, counts_path, pmc_path):

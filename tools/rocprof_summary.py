@@ -1,7 +1,7 @@
 """Summarise rocprofv3 CSV output of bench.py runs into profiles/.
 
     python tools/rocprof_summary.py --trace DIR --fetch DIR --write DIR --tag r1 [--sq DIR ...]
-                                    [--kernel k_trace|k_glsl|k_voxel] [--out profiles]
+                                    [--kernel k_trace|k_glsl|k_voxel|k_shade_hits] [--family k_trace] [--out profiles]
 
 Writes
   profiles/<tag>_kernel_stats_by_grid.csv  per (kernel, grid size): calls, avg/min/max ns
@@ -27,10 +27,12 @@ import re
 
 def pixels_per_thread(kernel_name: str) -> int:
     """Pixels one work-item writes: R for k_trace_window_r<R> / k_trace_window_list<R> and
-    their _ss<R, SS> (samples), _rc<R, SS> (ray cache) and _cc<R, SS> (cull cache) kernels
+    their _ss<R, SS> (samples), _rc<R, SS> (ray cache), _cc<R, SS> (cull cache) and _hf<R, SS> (hit
+    cache, storing) kernels, and for k_shade_hits[_list]<R, SS> (hit cache, reading)
     (round 1: k_trace_window_r<SLOTS, R, ...>), else 1."""
     m = re.search(r"k_trace_window_(?:r|list)<\s*(\d+)\s*>", kernel_name) or \
-        re.search(r"k_trace_window_(?:r|list)_(?:ss|rc|cc)<\s*(\d+)\s*,", kernel_name) or \
+        re.search(r"k_trace_window_(?:r|list)_(?:ss|rc|cc|hf)<\s*(\d+)\s*,", kernel_name) or \
+        re.search(r"k_shade_hits(?:_list)?<\s*(\d+)\s*,", kernel_name) or \
         re.search(r"k_trace_window_r<\s*\d+\s*,\s*(\d+)", kernel_name)
     return int(m.group(1)) if m else 1
 
@@ -39,7 +41,7 @@ def launch_key(kernel_name: str, grid: int) -> str:
     """Pixels per launch; the n > 64 culled-list kernel's launches get a "list:" prefix so
     that they never mix with the n <= 64 kernel's at the same frame size."""
     px = grid * pixels_per_thread(kernel_name)
-    return f"list:{px}" if "k_trace_window_list" in kernel_name else str(px)
+    return f"list:{px}" if ("k_trace_window_list" in kernel_name or "k_shade_hits_list" in kernel_name) else str(px)
 
 
 def rows(d, name):
@@ -56,6 +58,12 @@ def main():
                     help="--pmc passes with SQ_* counters (SQ_INSTS_VALU / SQ_WAVES, stall counters)")
     ap.add_argument("--tag", required=True)
     ap.add_argument("--kernel", default="k_trace", help="kernel-name substring (k_trace, k_glsl, k_voxel)")
+    ap.add_argument("--family", default="",
+                    help="the kernel family the traffic file is filed under (bench.py looks its workload up "
+                         "under k_trace, k_glsl or k_voxel); default: --kernel.  The sphere frame served from "
+                         "the hit cache: --kernel k_shade_hits --family k_trace, so that the first frame's "
+                         "marching launch, which has the same pixel count and no sorter workgroup either, "
+                         "stays out of the reading launch's averages")
     ap.add_argument("--out", default="profiles")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
@@ -92,7 +100,7 @@ def main():
         t["hbm_bytes_per_launch"] = 2.0 * t.get("FETCH_SIZE", 0.0) + t.get("WRITE_SIZE", 0.0)
         t["algorithmic_bytes_per_launch"] = 4.0 * int(g.split(":")[-1])
     with open(os.path.join(a.out, f"{a.tag}_traffic.json"), "w") as f:
-        json.dump({"note": __doc__.split("Writes")[0].strip(), "kernel": a.kernel,
+        json.dump({"note": __doc__.split("Writes")[0].strip(), "kernel": a.family or a.kernel,
                    "per_launch_pixels": traffic}, f, indent=1)
     print(json.dumps(traffic, indent=1))
 
