@@ -239,16 +239,26 @@ struct CullCachePolicy {
 // and first_draw (a function of the rest), n, and the fields cx, cy, cz, r, s_pass of the records:
 // exactly what CullKey holds.  What it leaves the rest of the launch is, per ray, the position and
 // drawSphere, and whether the ray still moved when the trip guard ended the march (status bit 0).
-// While the key stays, every frame repeats the same march: a chain whose launches keep it stores
-// those results once -- from the _hf instantiation of the very kernels that march, no extra pass --
-// and the reading kernels (k_shade_hits) shade from them, with the launch's own textures and
-// texture slots, which the key does not hold.
+// The shading tail (shade_texel) then takes the position, the camera position and the drawn
+// record's cx, cy, cz, r and atan_c -- atan2f of key fields -- through two atan2f, an asinf, two
+// roots and two divisions to three floats before anything of a texture enters: the fractions
+// fu = u - truncf(u), u = xcoord * 4 * r, and fw = w - truncf(w), w = ycoord * 2 * r, and the
+// brightness.  All of that is a function of the key too.  While the key stays, every frame repeats
+// the same march and the same tail up to there: a chain whose launches keep it stores those
+// results once -- from the _hf instantiation of the very kernels that march and shade, no extra
+// pass -- and the reading kernels (k_shade_hits) finish the tail from them with the launch's own
+// textures and texture slots, which the key does not hold: the drawn sphere's tex_off and tex_wh
+// of the moment, the fractions times that size, the index, the texel, the colour.  A fraction is
+// valid under every texture size; a texel index would have baked one in.
 //
 // Per ray one 16-byte record, 16-byte aligned, indexed by tile number like TileRec and CullRec,
 // [tile][r][lane]: a wave moves 1 KiB contiguous per ray slot with one 16-byte access per lane.
-// Clamped edge duplicates included; supersampled, per sample.
+// Clamped edge duplicates included; supersampled, per sample.  The three floats are stored raw,
+// neither canonicalised nor packed: the reading kernel feeds the very bits into the instructions
+// that follow them in the marching kernel, NaN included.
 struct alignas(16) HitRec {
-  uint32_t px, py, pz;  // the position after the march, binary32 bit patterns
+  uint32_t fu, fw;      // the texture coordinates' fractions, binary32 bit patterns
+  uint32_t brightness;  // 3 / max(|pos - cam|, 3), binary32 bit pattern
   uint32_t draw;        // drawSphere (< n <= 1024) in the low bits; bit 31 (kHitRecMoving): the
                         // ray's last step was > 0 when march_wave returned, which only the trip
                         // guard kMaxIterations allows

@@ -152,43 +152,67 @@ struct Shading {
   float brightness;
   bool outside;
   float depth;  // AUX only: |pos - cam| (:375's VLength, the operand of its std::max)
+  float fu, fw;  // the coordinates' fractions before the texture's size (the hit cache's record)
 };
 
 // ORIGIN (the ray batches, k_cast_rays): the brightness is taken from the ray's own origin
 // (ox, oy, oz) in place of f.cam, :375's cam.pos.
-template <class P, bool AUX = false, bool ORIGIN = false>
+// Everything above the line that reads d.tex_wh depends only on the position, f.cam, the drawn
+// record's cx, cy, cz, r and atan_c: on nothing CullKey does not hold.  It ends in three floats --
+// fu and fw, the fractions of the texture coordinates before they meet the texture's size, and
+// the brightness -- which the function returns beside the rest (dead, and removed, wherever they
+// are unused) and which the hit cache stores (sfrt_raycache.h HitRec).  FRAC (the k_shade_hits
+// kernels): (px, py, pz) are those three floats, loaded, and the function is its texture-
+// dependent part only -- the same bits into the same remaining instructions.
+template <class P, bool AUX = false, bool ORIGIN = false, bool FRAC = false>
 __device__ __forceinline__ Shading shade_texel(const FrameRec& f, const SphereRec& d, float px,
                                                float py, float pz, PixelDump* dump, float ox = 0.0f,
                                                float oy = 0.0f, float oz = 0.0f) {
-  float ang = d.atan_c - P::hit_atan2(pz, px);  // atan2f_wave == sfrt_math::atan2f (sfrt_device.h)
-  ang = ang > kPI ? ang - kPI2 : (ang < -kPI ? ang + kPI2 : ang);
-  const float xcoord = sfrt_math::div_pi2_plus_1(ang);  // == ang / PI2 + 1.0f
-  const float ex = px - d.cx, ey = py - d.cy, ez = pz - d.cz;
-  const float el = sqrt_cr((ex * ex + ey * ey) + ez * ez);
-  const float bx = px - (ORIGIN ? ox : f.cam[0]), by = py - (ORIGIN ? oy : f.cam[1]),
-              bz = pz - (ORIGIN ? oz : f.cam[2]);
-  const float bl = sqrt_cr((bx * bx + by * by) + bz * bz);
-  const float bd = bl < 3.0f ? 3.0f : bl;
-  // ey / el and 3 / bd through div_inrange (same bits) unless some lane's operands
-  // leave [2^-40, 2^40) (bd >= 3 needs only the upper bound)
-  float ny, brightness;
-  if ((ballot_bad_operand(ey) | ballot_bad_operand(el) | __builtin_amdgcn_ballot_w64(!(bd < 0x1.0p40f))) == 0) {
-    ny = div_inrange(ey, el);
-    brightness = div_inrange(3.0f, bd);
+  static_assert(!FRAC || (!AUX && !ORIGIN), "the fractions carry neither depth nor origin");
+  [[maybe_unused]] float xcoord = 0.0f, ycoord = 0.0f, bl = 0.0f;
+  float fu, fw, brightness;
+  if constexpr (FRAC) {
+    fu = px;
+    fw = py;
+    brightness = pz;
   } else {
-    ny = ey / keep_branch(el);
-    brightness = 3.0f / keep_branch(bd);
+    float ang = d.atan_c - P::hit_atan2(pz, px);  // atan2f_wave == sfrt_math::atan2f (sfrt_device.h)
+    ang = ang > kPI ? ang - kPI2 : (ang < -kPI ? ang + kPI2 : ang);
+    xcoord = sfrt_math::div_pi2_plus_1(ang);  // == ang / PI2 + 1.0f
+    const float ex = px - d.cx, ey = py - d.cy, ez = pz - d.cz;
+    const float el = sqrt_cr((ex * ex + ey * ey) + ez * ez);
+    const float bx = px - (ORIGIN ? ox : f.cam[0]), by = py - (ORIGIN ? oy : f.cam[1]),
+                bz = pz - (ORIGIN ? oz : f.cam[2]);
+    bl = sqrt_cr((bx * bx + by * by) + bz * bz);
+    const float bd = bl < 3.0f ? 3.0f : bl;
+    // ey / el and 3 / bd through div_inrange (same bits) unless some lane's operands
+    // leave [2^-40, 2^40) (bd >= 3 needs only the upper bound)
+    float ny;
+    if ((ballot_bad_operand(ey) | ballot_bad_operand(el) | __builtin_amdgcn_ballot_w64(!(bd < 0x1.0p40f))) == 0) {
+      ny = div_inrange(ey, el);
+      brightness = div_inrange(3.0f, bd);
+    } else {
+      ny = ey / keep_branch(el);
+      brightness = 3.0f / keep_branch(bd);
+    }
+    ycoord = sfrt_math::div_pi_plus_half(P::hit_asin(ny));  // == asinf / PI + 0.5f
   }
-  const float ycoord = sfrt_math::div_pi_plus_half(P::hit_asin(ny));  // == asinf / PI + 0.5f
   // fmodf(v, 1.0f) == v - truncf(v) exactly for every binary32 v (NaN/inf -> NaN).
   // texsize of textures[0] (or of the sphere's extension slot), (float)(unsigned) as :376
+  // (the statements in this order: the marching kernels' schedule follows it)
   const uint32_t tw = d.tex_wh & 0xffffu, th = d.tex_wh >> 16;
-  float u = xcoord * 4.0f * d.r;
-  u = (u - __builtin_truncf(u)) * (float)tw;
-  float w = ycoord * 2.0f * d.r;
-  w = (w - __builtin_truncf(w)) * (float)th;
+  if constexpr (!FRAC) {
+    const float u = xcoord * 4.0f * d.r;
+    fu = u - __builtin_truncf(u);
+  }
+  const float su = fu * (float)tw;
+  if constexpr (!FRAC) {
+    const float w = ycoord * 2.0f * d.r;
+    fw = w - __builtin_truncf(w);
+  }
+  const float sw = fw * (float)th;
   // float -> unsigned: v_cvt_u32_f32 (NaN -> 0), as x86's cvttss2si for [0, 2^31).
-  const uint32_t tx = __float2uint_rz(u), ty = __float2uint_rz(w);
+  const uint32_t tx = __float2uint_rz(su), ty = __float2uint_rz(sw);
   // ty < th <= 0xffff (a fraction in [0, 1) times th, or 0 from NaN; radii are > 0, so no
   // negative fraction reaches -1 / th): the 24-bit multiply is the exact product
   const uint32_t idx = tx + __umul24(ty, tw);
@@ -196,6 +220,8 @@ __device__ __forceinline__ Shading shade_texel(const FrameRec& f, const SphereRe
   sh.outside = !(idx < tw * th);
   sh.tex = d.tex_off + (sh.outside ? 0u : idx);
   sh.brightness = brightness;
+  sh.fu = fu;
+  sh.fw = fw;
   if constexpr (AUX) sh.depth = bl;
   else sh.depth = 0.0f;
   if (dump) {
@@ -477,30 +503,30 @@ __device__ __forceinline__ size_t cull_win_at(int tile, int lane) {
   return (size_t)tile * 64u + (size_t)lane;
 }
 
-// The hit cache (sfrt_raycache.h HitRec; DESIGN.md 5 "Hit cache"): what march_wave leaves a tile's
-// rays, [tile][r][lane], stored by the _hf kernels right after their march (plain vector stores,
-// one 16-byte store per ray slot: 1 KiB contiguous per wave) and loaded by the k_shade_hits
-// kernels, R loads back to back.  The buffer is written only by the _hf launch that precedes the
-// reading launches on its stream.
+// The hit cache (sfrt_raycache.h HitRec; DESIGN.md 5 "Hit cache"): what the march and the part of
+// the shading tail that no texture enters leave a tile's rays, [tile][r][lane]: the two texture
+// fractions and the brightness (shade_texel), drawSphere and the moving bit.  Stored by the _hf
+// kernels from their shading tail (plain vector stores, one 16-byte store per ray slot: 1 KiB
+// contiguous per wave) and loaded by the k_shade_hits kernels, R loads back to back.  The buffer
+// is written only by the _hf launch that precedes the reading launches on its stream.
+// hw: hit_pack_draw of the ray's drawSphere and of whether it still moved, taken after march_wave.
 template <int R>
 __device__ __forceinline__ void hit_store(HitRec* __restrict__ hr, int tile, int lane,
-                                          const float (&px)[R], const float (&py)[R],
-                                          const float (&pz)[R], const int (&draw)[R],
-                                          const float (&mv)[R]) {
+                                          const Shading (&sh)[R], const uint32_t (&hw)[R]) {
 #pragma unroll
   for (int r = 0; r < R; r++) {
     uint4 v;
-    v.x = __float_as_uint(px[r]);
-    v.y = __float_as_uint(py[r]);
-    v.z = __float_as_uint(pz[r]);
-    v.w = hit_pack_draw(draw[r], mv[r] > 0.0f);
+    v.x = __float_as_uint(sh[r].fu);
+    v.y = __float_as_uint(sh[r].fw);
+    v.z = __float_as_uint(sh[r].brightness);
+    v.w = hw[r];
     *(uint4*)(hr + hit_rec_at(tile, R, r, lane)) = v;
   }
 }
 // Returns whether some ray of the lane still moved at the guard.
 template <int R>
 __device__ __forceinline__ bool hit_load(const HitRec* __restrict__ hr, int tile, int lane,
-                                         float (&px)[R], float (&py)[R], float (&pz)[R],
+                                         float (&fu)[R], float (&fw)[R], float (&br)[R],
                                          int (&draw)[R]) {
   uint4 v[R];
 #pragma unroll
@@ -508,9 +534,9 @@ __device__ __forceinline__ bool hit_load(const HitRec* __restrict__ hr, int tile
   bool moving = false;
 #pragma unroll
   for (int r = 0; r < R; r++) {
-    px[r] = __uint_as_float(v[r].x);
-    py[r] = __uint_as_float(v[r].y);
-    pz[r] = __uint_as_float(v[r].z);
+    fu[r] = __uint_as_float(v[r].x);
+    fw[r] = __uint_as_float(v[r].y);
+    br[r] = __uint_as_float(v[r].z);
     draw[r] = hit_draw(v[r].w);
     moving = moving || hit_moving(v[r].w);
   }
@@ -823,13 +849,16 @@ __device__ __forceinline__ Rays<R> march_wave(const FrameRec& f, const SphereRec
 // for this launch's CullKey: the bits cull_wave gives) -- neither the tile record nor the sphere
 // records are read before the march.
 // HIT (implies CULLED; DESIGN.md 5 "Hit cache"): 1, the _hf kernels -- the CULLED launch, which
-// also stores each ray's march result in the chain's hit cache hr (hit_store), the bits the very
-// same march under the very same flags leaves; 2, the k_shade_hits kernels -- one wave per tile in
-// tile-number order (the grid is exactly the tiles: no sorter workgroup, no order lookup, no cost
-// store), the tile's grid position from its CullRec, the rays' positions and drawSphere loaded
-// from hr in place of the ray setup, the cull and the march, then the same shading tail: it is
-// this function's, so there is one copy of it and the marching kernels' code cannot move when
-// the reading kernels change.  A ray that still moved at the guard raises status bit 0 again.
+// also stores, from its shading tail, each ray's record in the chain's hit cache hr (hit_store):
+// the fractions and the brightness shade_texel has before the texture's size enters, drawSphere
+// and the moving bit, the bits the very same march and tail under the very same flags leave;
+// 2, the k_shade_hits kernels -- one wave per tile in tile-number order (the grid is exactly the
+// tiles: no sorter workgroup, no order lookup, no cost store), the tile's grid position from its
+// CullRec, the rays' records loaded from hr in place of the ray setup, the cull, the march and
+// the texture-independent part of the tail, of the drawn records only tex_off and tex_wh, then
+// the rest of the same tail (shade_texel's FRAC): it is this function's, so there is one copy of
+// it and the marching kernels' code cannot move when the reading kernels change.  A ray that
+// still moved at the guard raises status bit 0 again.
 // PLACE (sfrt_world_render_subset): the subset goes in place into a whole frame --
 // compact column a (output pixel a >> SS) is stored xstride elements apart, the host having put
 // the subset's first pixel into f.out and yadd frame rows into f.out_pitch (the planes' pitches
@@ -896,9 +925,11 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   const float l0 = f.first_l;
   Rays<R> ray;  // iters: DUMP and AUX only, the host's first trip included
   uint64_t m_end = 0;  // the wave's culling mask, for the probe's tile_end
+  [[maybe_unused]] uint32_t hit_w[HIT == 1 ? R : 1];
   if constexpr (HIT == 2) {
     // every lane, clamped duplicates included: a duplicate is some stored pixel's ray again, so
-    // "some ray of the wave still moved" is what march_wave's own test saw
+    // "some ray of the wave still moved" is what march_wave's own test saw.  ray.px, py, pz hold
+    // the records' fu, fw and brightness from here on (shade_texel's FRAC), not a position.
     const bool moving = hit_load<R>(hr, tile, lane, ray.px, ray.py, ray.pz, ray.draw);
     if (__builtin_amdgcn_ballot_w64(moving) != 0 && lane == 0) atomicOr(f.status, 1);
   } else {
@@ -957,7 +988,10 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
       cull_wave<LIST>(f, sph, cone, lane, culled, m, lo, hi, cidx);
     }
     ray = march_wave<R, LIST, DUMP || AUX>(f, sph, lane, probe, culled, m, lo, hi, cidx, ray);
-    if constexpr (HIT == 1) hit_store<R>(hr, tile, lane, ray.px, ray.py, ray.pz, ray.draw, ray.mv);
+    if constexpr (HIT == 1) {  // the record's fourth dword; the tail below stores it with its own three
+#pragma unroll
+      for (int r = 0; r < R; r++) hit_w[r] = hit_pack_draw(ray.draw[r], ray.mv[r] > 0.0f);
+    }
     m_end = m;
   }
   const int trips = HIT == 2 ? 0 : ray.trips;  // (2: no march; `ray` holds the loaded results only)
@@ -1009,7 +1043,9 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
     PixelDump dl[DUMP ? R : 1];
 #pragma unroll
     for (int r = 0; r < R; r++)
-      sh[r] = shade_texel<P, AUX>(f, d[r], ray.px[r], ray.py[r], ray.pz[r], DUMP ? &dl[DUMP ? r : 0] : nullptr);
+      sh[r] = shade_texel<P, AUX, false, HIT == 2>(f, d[r], ray.px[r], ray.py[r], ray.pz[r], DUMP ? &dl[DUMP ? r : 0] : nullptr);
+    // every lane, clamped duplicates included, as the reading kernels load them
+    if constexpr (HIT == 1) hit_store<R>(hr, tile, lane_s, sh, hit_w);
     // AUX: ray r's plane values beside its colour store (plain vector stores)
     [[maybe_unused]] auto aux_store = [&](int r) {
       const int c = col_out(r);

@@ -612,6 +612,10 @@ def regions_sphere(blocks, kind="sphere"):
                ("hit_load", "hit_load"), ("hit_store", "hit_store"),
                ("cull_wave", "cull"),
                ("dist2", "visit_test"), ("pass_body_r", "pass_body"), ("zero_steps", "step_control")]
+    if kind == "sphere_hits":
+        # the reading kernel's tail is shade_texel's texture-dependent part only (FRAC: the stored
+        # fractions times the texture's size, the index, the bound) and shade_rgba: told apart
+        helpers = [("shade_texel", "texel_index"), ("shade_rgba", "colour")] + helpers
 
     def march_region(line):
         """A line of march_wave (or of one of its lambdas)."""
