@@ -1,8 +1,8 @@
 // sfrt_hostmem.h -- the host layer's buffer bookkeeping and layouts, without a HIP call of their
 // own ("Host memory"): the one growable buffer every owner in sfrt_host.h and
-// sfrt_sched.h is built on, the staging layout of a ray batch, the scatter of a compact subset
+// sfrt_raycache.h is built on, the staging layout of a ray batch, the scatter of a compact subset
 // into the caller's frame.  Tested on the host: tests/native/hostmem_check.cpp (and, for
-// CacheBuf under the ray cache's policy, tests/native/tilerec_check.cpp).
+// CacheBuf under a chain's caches, tests/native/tilerec_check.cpp).
 #pragma once
 
 #include <cstddef>

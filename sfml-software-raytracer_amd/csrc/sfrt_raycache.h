@@ -1,22 +1,23 @@
-// sfrt_raycache.h -- policy of the primary-ray-direction cache ("Ray cache").
+// sfrt_raycache.h -- the sphere renderer's per-chain caches ("The chain's caches").
 //
 // The normalised direction of pixel (i, j) depends only on the view basis, the ray-angle
 // steps, the subset geometry and the tile grid -- not on the camera position, the spheres,
 // the textures or the march.  A tile-order chain (sfrt_sched.h) whose launches keep all of
-// those (RayKey) fills a tile-major buffer of directions once and reads it from then on
-// (sphere_trace.hip: k_ray_fill, the CACHED kernels).  This header decides when; it makes no
-// HIP call, so the policy is tested on the host (tests/native/raycache_check.cpp).  The tile
-// records (TileRec, below) are filled, read and dropped by the same decisions; their layout and
-// the chain's buffer bookkeeping (sfrt_hostmem.h CacheBuf) are tested in
-// tests/native/tilerec_check.cpp.
-// The cull cache (CullKey, CullCachePolicy, at the end) rides on the tile records: what each tile's
-// wave culls before it marches, under a key of its own (tests/native/cullcache_check.cpp).
-// The hit cache (HitRec, HitCachePolicy, after it) rides on the cull cache under the same key: what
-// each ray's march leaves the shading (tests/native/hitcache_check.cpp).
+// those (RayKey) fills a tile-major buffer of directions and the tile records (TileRec) once
+// and reads them from then on (sphere_trace.hip: k_ray_fill, the CACHED kernels).  On the tile
+// records rides the cull cache (CullKey: what each tile's wave culls before it marches), and on
+// that, under the same key, the hit cache (HitRec: what each ray's march leaves the shading).
+// One policy (CacheLayer) decides for each of the three; one object per chain (ChainCaches, at
+// the end) owns the layers, their five buffers and the order in which a launch decides, fills
+// and drops them.  This header makes no HIP call -- the device is a parameter of
+// ChainCaches::begin -- so all of it is tested on the host as it ships: tests/native/
+// raycache_check.cpp (the layer), tilerec_check.cpp, cullcache_check.cpp, hitcache_check.cpp
+// (the chain, through counting allocators).
 #pragma once
 
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "sfrt_hostmem.h"  // CacheBuf: a chain's buffers, for every user of this header
@@ -76,37 +77,39 @@ enum class RayAction {
   kRead    // the CACHED kernel
 };
 
-// One chain's cache state.  decide() before the launch, commit() once it is known to be queued
-// (or to have failed); nothing moves in between, as in TileSched.
-struct RayCachePolicy {
-  RayKey cached{};       // the key the buffer's contents were computed for
+// One cache of a chain: the state of the directions (Key = RayKey), of the cull cache or of the hit
+// cache (Key = CullKey).  decide() before the launch, commit() once it is known to be queued;
+// a launch or a fill that failed goes through invalidate() -- the buffer may hold anything.
+template <class Key>
+struct CacheLayer {
+  Key cached{};          // the key the buffer's contents were computed for
   bool valid = false;
-  RayKey prev{};         // the previous committed launch's key
+  Key prev{};            // the previous committed launch's key
   bool have_prev = false;
 
-  // bytes: the size the cache of `key` needs; held: the chain's own buffer size now (reused
-  // or replaced by a fill); others: bytes the world's other chains hold; budget: the world's
-  // limit in bytes (0: the cache is off).
-  // A fill needs the second consecutive launch of a key: a camera that turns every frame
-  // never fills.  A fill that would put the world past its budget is not made.
-  RayAction decide(const RayKey& key, long long bytes, long long held, long long others,
-                   long long budget) const {
-    if (budget <= 0 || bytes <= 0) return RayAction::kTrace;
-    if (valid && cached.same(key)) return RayAction::kRead;
+  // below: this launch's decision for the layer under this one (the directions, which have
+  // none: kRead) -- a layer is read only by a launch that reads the one below, and filled only
+  // by one that reads or fills it.  bytes: the size the cache of `key` needs; held: the chain's
+  // own buffers of this layer now (reused or replaced by a fill); others: every other byte under
+  // the same budget; budget: the limit in bytes (0: off).
+  // A fill needs the second consecutive launch of a key: a camera that turns every frame never
+  // fills.  A fill that would put the world past its budget is not made.
+  RayAction decide(const Key& key, RayAction below, long long bytes, long long held,
+                   long long others, long long budget) const {
+    if (budget <= 0 || bytes <= 0 || below == RayAction::kTrace) return RayAction::kTrace;
+    if (below == RayAction::kRead && valid && cached.same(key)) return RayAction::kRead;
     if (!have_prev || !prev.same(key)) return RayAction::kTrace;
     const long long after = bytes > held ? bytes : held;
     return others + after <= budget ? RayAction::kFill : RayAction::kTrace;
   }
 
-  // queued = false: the launch (or its fill) failed -- the buffer may hold anything.
-  void commit(const RayKey& key, RayAction a, bool queued) {
-    if (!queued) {
-      invalidate();
-      return;
-    }
+  // a: this layer's decision; below_filled: a layer under this one was rewritten by the launch.
+  void commit(const Key& key, RayAction a, bool below_filled) {
     if (a == RayAction::kFill) {
       cached = key;
       valid = true;
+    } else if (below_filled) {
+      valid = false;
     }
     prev = key;
     have_prev = true;
@@ -187,52 +190,6 @@ struct CullKey {
   }
 };
 
-// One chain's cull cache, decided after the ray cache's action for the same launch is known:
-// the cull cache lives on the tile records, so it is read or filled only by a launch that reads
-// the ray cache (kRead) or fills it (kFill: then the records are rewritten, and whatever the
-// cull cache held is not trusted), and it is dropped with them (invalidate).  As for the
-// directions, a fill needs the second consecutive launch of a key: a walking camera or a sphere
-// that moves every frame never fills and runs the tile-record kernels unchanged.
-struct CullCachePolicy {
-  CullKey cached;
-  bool valid = false;
-  CullKey prev;
-  bool have_prev = false;
-
-  // ray: the ray cache's decision for this launch.  bytes: what the cull cache of `key` needs;
-  // held: the chain's own cull buffers now; others: every other cached byte of the world, this
-  // launch's ray cache included; budget: SFRT_OPT_RAY_CACHE_MB in bytes.
-  RayAction decide(const CullKey& key, RayAction ray, long long bytes, long long held,
-                   long long others, long long budget) const {
-    if (budget <= 0 || bytes <= 0 || ray == RayAction::kTrace) return RayAction::kTrace;
-    if (ray == RayAction::kRead && valid && cached.same(key)) return RayAction::kRead;
-    if (!have_prev || !prev.same(key)) return RayAction::kTrace;
-    const long long after = bytes > held ? bytes : held;
-    return others + after <= budget ? RayAction::kFill : RayAction::kTrace;
-  }
-
-  // ray, a: the two decisions of the launch; queued = false: the launch or a fill failed.
-  void commit(const CullKey& key, RayAction ray, RayAction a, bool queued) {
-    if (!queued) {
-      invalidate();
-      return;
-    }
-    if (a == RayAction::kFill) {
-      cached = key;
-      valid = true;
-    } else if (ray == RayAction::kFill) {
-      valid = false;  // the tile records were rewritten under this cache
-    }
-    prev = key;
-    have_prev = true;
-  }
-
-  void invalidate() {
-    valid = false;
-    have_prev = false;
-  }
-};
-
 // ---- The hit cache (DESIGN.md 5 "Hit cache") ----
 //
 // The march (sphere_trace.hip march_wave) reads the rays' directions, the camera position, first_l
@@ -285,48 +242,141 @@ inline long long hit_cache_bytes(long long tiles, int rays) {
   return tiles * rays * 64 * (long long)sizeof(HitRec);
 }
 
-// One chain's hit cache, decided after the cull cache's action for the same launch.  It is filled
-// by a launch that runs the cull-cached kernel anyway (cull action kRead or kFill) on the second
-// consecutive launch of a key, read by a launch that reads the cull cache under the cached key,
-// and never valid without a valid cull cache: whatever refills the directions or the cull cache
-// drops it.  kTrace: the launch runs what it would run without a hit cache.
-struct HitCachePolicy {
-  CullKey cached;
-  bool valid = false;
-  CullKey prev;
-  bool have_prev = false;
+// ---- One chain's caches (DESIGN.md 5 "The chain's caches") ----
 
-  // cull: the cull cache's decision for this launch.  bytes: what the records of `key` need; held:
-  // the chain's own hit buffer now; others: the hit bytes of the world's other chains; budget:
-  // SFRT_OPT_HIT_CACHE_MB in bytes (a budget of its own).
-  RayAction decide(const CullKey& key, RayAction cull, long long bytes, long long held,
-                   long long others, long long budget) const {
-    if (budget <= 0 || bytes <= 0 || cull == RayAction::kTrace) return RayAction::kTrace;
-    if (cull == RayAction::kRead && valid && cached.same(key)) return RayAction::kRead;
-    if (!have_prev || !prev.same(key)) return RayAction::kTrace;
-    const long long after = bytes > held ? bytes : held;
-    return others + after <= budget ? RayAction::kFill : RayAction::kTrace;
+// What ChainCaches::begin decided for one launch and what that launch reads: launch_trace's cache
+// argument (sfrt_trace.h).  A pointer is set exactly when its layer's action is not kTrace.
+struct TraceCaches {
+  bool decided = false;  // begin() made it: end() has something to commit
+  RayAction ray = RayAction::kTrace, cull = RayAction::kTrace, hit = RayAction::kTrace;
+  const float* dirs = nullptr;
+  const TileRec* tile_recs = nullptr;
+  const CullRec* cull_recs = nullptr;
+  const void* cull_wins = nullptr;  // CullWin or CullWinList
+  HitRec* hit_recs = nullptr;       // written by a filling launch (hit == kFill), read by a reading one
+  bool reading() const { return hit == RayAction::kRead; }  // no march: outside the tile order
+};
+
+struct CacheSizes {  // of one launch's grid: ray_cache_bytes, tile_rec_bytes, cull_*_bytes, hit_cache_bytes
+  long long dirs = 0, tile_recs = 0, cull_recs = 0, cull_wins = 0, hit_recs = 0;
+};
+
+struct CacheCounters {  // sfrt_world_{ray,cull,hit}_cache_stats
+  int64_t ray_cached_frames = 0, ray_fills = 0, cull_fills = 0, cull_hits = 0, hit_fills = 0, hit_hits = 0;
+};
+
+// The three layers and the five buffers of one tile-order chain, and the one rule between them:
+// an upper cache is never valid without the one under it.  A refill below drops what is above; a
+// failed fill drops its own layer and everything above it; a failed launch drops all three.
+struct ChainCaches {
+  CacheLayer<RayKey> ray;
+  CacheLayer<CullKey> cull, hit;
+  CacheBuf dirs, tile_recs;  // ray_cache_bytes, tile_rec_bytes: one layer, two buffers
+  CacheBuf cull_recs, cull_wins;
+  CacheBuf hit_recs;
+  RayKey ray_key{};  // begin() -> end(): the launch being queued
+  CullKey cull_key;
+
+  long long cull_bytes() const { return cull_recs.bytes + cull_wins.bytes; }
+  // What SFRT_OPT_RAY_CACHE_MB limits (the tile records ride free: 0.3 to 1 % of the directions),
+  // what SFRT_OPT_HIT_CACHE_MB limits, and the tile records, reported on their own.
+  long long bytes_under_ray_budget() const { return dirs.bytes + cull_bytes(); }
+  long long hit_bytes() const { return hit_recs.bytes; }
+  long long tile_rec_bytes() const { return tile_recs.bytes; }
+
+  // Before a launch that takes part.  other_ray, other_hit: what the world's other chains hold
+  // under the two budgets.  dev: the device in the launch's stream order -- free(p) -> bool,
+  // alloc(n) -> pointer or null, fill_rays(dirs, tile_recs) -> bool and fill_cull(tile_recs,
+  // cull_recs, cull_wins) -> bool queue the fill kernels for this launch's frame.  A fill that
+  // fails is no error of the frame: the launch runs what it would run without that cache.
+  template <class Dev>
+  TraceCaches begin(const RayKey& rk, const CullKey& ck, const CacheSizes& n, long long other_ray,
+                    long long other_hit, long long ray_budget, long long hit_budget, Dev&& dev) {
+    const auto free_fn = [&dev](void* p) { return dev.free(p); };
+    const auto reserve = [&](CacheBuf& b, long long m) {
+      return b.reserve(m, free_fn, [&dev](long long q) { return dev.alloc(q); });
+    };
+    ray_key = rk;
+    cull_key = ck;
+    TraceCaches d;
+    d.decided = true;
+    d.ray = ray.decide(rk, RayAction::kRead, n.dirs, dirs.bytes, other_ray, ray_budget);
+    if (d.ray == RayAction::kFill) {
+      // The tile records are rewritten: what rides on them goes first and takes no room from the
+      // directions.  have_prev stays, so this very launch can go on to fill all three.
+      for (CacheBuf* b : {&cull_recs, &cull_wins, &hit_recs}) b->release(free_fn);
+      cull.valid = false;
+      hit.valid = false;
+      if (!reserve(dirs, n.dirs) || !reserve(tile_recs, n.tile_recs) ||
+          !dev.fill_rays((float*)dirs.ptr, (TileRec*)tile_recs.ptr)) {
+        invalidate();  // the buffers may be gone or half written
+        d.ray = RayAction::kTrace;
+      }
+    }
+    if (d.ray != RayAction::kTrace) {
+      d.dirs = (const float*)dirs.ptr;
+      d.tile_recs = (const TileRec*)tile_recs.ptr;
+    }
+    // The cull cache, on top of the tile records this launch reads (or has just filled).
+    d.cull = cull.decide(ck, d.ray, n.cull_recs + n.cull_wins, cull_bytes(), other_ray + dirs.bytes,
+                         ray_budget);
+    if (d.cull == RayAction::kFill &&
+        (!reserve(cull_recs, n.cull_recs) || !reserve(cull_wins, n.cull_wins) ||
+         !dev.fill_cull((const TileRec*)tile_recs.ptr, (CullRec*)cull_recs.ptr, cull_wins.ptr))) {
+      cull.invalidate();  // the tile records are whole: the launch reads them
+      hit.invalidate();
+      d.cull = RayAction::kTrace;
+    }
+    if (d.cull != RayAction::kTrace) {
+      d.cull_recs = (const CullRec*)cull_recs.ptr;
+      d.cull_wins = cull_wins.ptr;
+    }
+    // The hit cache, on top of the cull cache, under the same key and a budget of its own; the
+    // launch that marches anyway fills it, so there is only room to find.
+    d.hit = hit.decide(ck, d.cull, n.hit_recs, hit_recs.bytes, other_hit, hit_budget);
+    if (d.hit == RayAction::kFill && !reserve(hit_recs, n.hit_recs)) {
+      hit.invalidate();  // no memory for it: the launch stays on the cull-cache path
+      d.hit = RayAction::kTrace;
+    }
+    if (d.hit != RayAction::kTrace) d.hit_recs = (HitRec*)hit_recs.ptr;
+    return d;
   }
 
-  // ray, cull, a: the three decisions of the launch; queued = false: the launch or a fill failed.
-  void commit(const CullKey& key, RayAction ray, RayAction cull, RayAction a, bool queued) {
+  // After the launch begin() decided d for was queued (queued = false: it failed).
+  void end(const TraceCaches& d, bool queued, CacheCounters& n) {
     if (!queued) {
       invalidate();
       return;
     }
-    if (a == RayAction::kFill) {
-      cached = key;
-      valid = true;
-    } else if (ray == RayAction::kFill || cull == RayAction::kFill) {
-      valid = false;  // the caches under this one were rewritten
-    }
-    prev = key;
-    have_prev = true;
+    const bool ray_filled = d.ray == RayAction::kFill, cull_filled = d.cull == RayAction::kFill;
+    ray.commit(ray_key, d.ray, false);
+    cull.commit(cull_key, d.cull, ray_filled);
+    hit.commit(cull_key, d.hit, ray_filled || cull_filled);
+    n.ray_fills += ray_filled;
+    n.ray_cached_frames += d.ray != RayAction::kTrace;
+    n.cull_fills += cull_filled;
+    n.cull_hits += d.cull == RayAction::kRead;
+    n.hit_fills += d.hit == RayAction::kFill;
+    n.hit_hits += d.hit == RayAction::kRead;
   }
 
   void invalidate() {
-    valid = false;
-    have_prev = false;
+    ray.invalidate();
+    cull.invalidate();
+    hit.invalidate();
+  }
+  void invalidate_hit() { hit.invalidate(); }
+
+  // Freed by the host once the device has drained (an option lowered, the world going away).
+  template <class Free>
+  void release_hit(Free&& free_fn) {
+    hit_recs.release(free_fn);
+    hit.invalidate();
+  }
+  template <class Free>
+  void release_all(Free&& free_fn) {
+    for (CacheBuf* b : {&dirs, &tile_recs, &cull_recs, &cull_wins, &hit_recs}) b->release(free_fn);
+    invalidate();
   }
 };
 

@@ -16,9 +16,6 @@
 
 #include <cstdint>
 
-#include "sfrt_hostmem.h"
-#include "sfrt_raycache.h"
-
 namespace sfrt {
 
 // Entries of an n-tile order array: its slot layout (sfrt_device.h order_index) maps the n slots
@@ -62,53 +59,8 @@ struct TileSched {
   bool have_last = false;
   uint64_t used = 0;             // TileChains: when the chain last took a launch
   bool probed = false;           // a timing-probe launch rewrote cost[k % 2] since k last moved
-  // The chain's primary-ray-direction cache (sfrt_raycache.h; the sphere renderer only): a
-  // stream-ordered buffer like order[] and cost[], used by the chain's own launches alone.  A
-  // takeover by another stream keeps it (begin() has waited for the device by then).  The tile
-  // records (TileRec) live and die with the directions: one policy, one key, two buffers.
-  RayCachePolicy ray_policy;
-  CacheBuf ray_dirs;  // the directions (ray_cache_bytes)
-  CacheBuf ray_recs;  // the tile records (tile_rec_bytes)
-  // The chain's cull cache (sfrt_raycache.h CullCachePolicy): each tile's culling mask and march
-  // windows, two more buffers under the same rules.  It lives on the tile records: whatever
-  // invalidates or frees the ray cache does the same to it (invalidate_caches).
-  CullCachePolicy cull_policy;
-  CacheBuf cull_recs;  // the per-tile records (cull_rec_bytes)
-  CacheBuf cull_wins;  // the per-lane windows (cull_win_bytes)
-
-  // The chain's hit cache (sfrt_raycache.h HitCachePolicy): each ray's march result, one more
-  // buffer under the same rules, on a budget of its own.  It lives on the cull cache: whatever
-  // invalidates, refills or frees that does the same to it.
-  HitCachePolicy hit_policy;
-  CacheBuf hit_recs;  // the per-ray records (hit_cache_bytes)
-
-  long long cull_bytes() const { return cull_recs.bytes + cull_wins.bytes; }
-
-  void invalidate_caches() {
-    ray_policy.invalidate();
-    cull_policy.invalidate();
-    hit_policy.invalidate();
-  }
-
-  // The hit records alone freed by the host (the device has drained): SFRT_OPT_HIT_CACHE_MB lowered.
-  void release_hit_cache() {
-    hit_recs.release([](void* p) { return hipFree(p) == hipSuccess; });
-    hit_policy.invalidate();
-  }
-
-  // All five buffers freed by the host (the device has drained, or the chain is going away).
-  void release_ray_cache() {
-    const auto free_now = [](void* p) { return hipFree(p) == hipSuccess; };
-    ray_dirs.release(free_now);
-    ray_recs.release(free_now);
-    cull_recs.release(free_now);
-    cull_wins.release(free_now);
-    hit_recs.release(free_now);
-    invalidate_caches();
-  }
 
   void release() {
-    release_ray_cache();
     for (int q = 0; q < 2; q++) {
       (void)hipFree(order[q]);
       (void)hipFree(cost[q]);
@@ -180,7 +132,6 @@ struct TileSched {
     if (!p.tile_cost) return hipSuccess;
     if (!queued) {
       reset();
-      invalidate_caches();
       return hipSuccess;
     }
     committed = pending_key != 0;
@@ -196,10 +147,11 @@ struct TileSched {
     return hipSuccess;
   }
 
-  // After a launch that reads the hit cache was queued on s: it was linked into nothing (no order,
-  // no classes, no sorter), so the chain does not advance -- the next marching launch continues it
-  // as if the reading launches had not happened -- and only the stream is remembered (begin() has
-  // waited for the device if another stream had the chain).  A failed one goes through end().
+  // After a launch that marches nothing (the sphere renderer's, shading from its hit cache) was
+  // queued on s: it was linked into nothing (no order, no classes, no sorter), so the chain does
+  // not advance -- the next marching launch continues it as if the reading launches had not
+  // happened -- and only the stream is remembered (begin() has waited for the device if another
+  // stream had the chain).  A failed one goes through reset() and end().
   void end_reading(hipStream_t s) {
     pending_key = 0;
     last_stream = s;

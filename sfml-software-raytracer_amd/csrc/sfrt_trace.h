@@ -97,9 +97,9 @@ struct InlineArgs {
   SphereRec s[kInlineSpheres];
 };
 
-struct TileRec;  // sfrt_raycache.h
-struct CullRec;  // sfrt_raycache.h
-struct HitRec;   // sfrt_raycache.h
+struct TileRec;      // sfrt_raycache.h
+struct CullRec;      // sfrt_raycache.h
+struct TraceCaches;  // sfrt_raycache.h
 
 struct PixelDump {
   float pos[3];
@@ -165,26 +165,19 @@ int launch_cast_rays(const FrameRec& f, const SphereRec* host_spheres, const Ray
 // a row-major launch only (no tile order, no ray cache, no dump), with or without aux.
 // done_event (hipEvent_t, may be null): recorded by the list kernel's own completion (its stop
 // event; the inline kernel, which reads no device records, takes none).
-// ray_cache, tile_recs (both null, or both set): the chain's ray cache and tile records, filled
-// for this very f by launch_ray_fill earlier on the same stream -- the launch then loads its
-// directions, its tiles' culling cones and their grid positions from them (an ordered,
-// non-dump launch only).
-// cull_recs, cull_wins (both null, or both set, and then with ray_cache): the chain's cull cache,
-// filled for this very f and these very records by launch_cull_fill earlier on the same stream --
-// the launch then loads each tile's culling mask, march windows and grid position from it and
-// reads no tile record.
-// hit_recs, hit_mode (null and 0, or set and 1 or 2; with cull_recs only): the chain's hit cache
-// (hit_cache_bytes(tiles, rays) bytes, sfrt_raycache.h).  1: the cull-cached launch also stores each
-// ray's march result there.  2: the reading launch -- no march; one wave per tile in tile-number
-// order shades from the records filled for this very key by a mode-1 launch earlier on the same
-// stream.  It takes no part in the tile order: f's tile_order, tile_cost, prev_cost and next_order
-// are ignored (the caller links nothing), and ray_cache and cull_wins are not read.
+// caches (may be null: today's kernel): what the chain's caches decided for this launch
+// (sfrt_raycache.h ChainCaches::begin), every buffer filled for this very f and these very records
+// earlier on the same stream.  Each layer needs the one before it -- dirs with tile_recs (an
+// ordered, non-dump launch only): the directions, the tiles' culling cones and grid positions are
+// loaded; cull_recs with cull_wins: so are each tile's culling mask and march windows, and no
+// tile record is read; hit_recs with hit == kFill: the cull-cached launch also stores each ray's
+// march result; with hit == kRead: no march -- one wave per tile in tile-number order shades from
+// the records.  That launch takes no part in the tile order: f's tile_order, tile_cost, prev_cost
+// and next_order are ignored (the caller links nothing), and dirs and cull_wins are not read.
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump = nullptr, void* done_event = nullptr,
-                 const float* ray_cache = nullptr, const TileRec* tile_recs = nullptr,
-                 const AuxArgs* aux = nullptr, int place_xstride = 0,
-                 const CullRec* cull_recs = nullptr, const void* cull_wins = nullptr,
-                 HitRec* hit_recs = nullptr, int hit_mode = 0);
+                 const TraceCaches* caches = nullptr, const AuxArgs* aux = nullptr,
+                 int place_xstride = 0);
 // Fills ray_cache (ray_cache_bytes(tiles, rays) bytes, sfrt_raycache.h, of the grid
 // trace_tile_key names) with the primary directions of f's rays, tile-major, and tile_recs
 // (tile_rec_bytes(tiles) bytes) with the tiles' records.

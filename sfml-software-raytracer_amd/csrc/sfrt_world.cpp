@@ -24,6 +24,7 @@
 #include "sfrt.h"
 #include "sfrt_host.h"
 #include "sfrt_math.h"
+#include "sfrt_raycache.h"
 #include "sfrt_sched.h"
 #include "sfrt_trace.h"
 
@@ -152,32 +153,14 @@ struct sfrt_world {
   sfrt::TileChains scheds;  // adaptive tile order (sfrt_sched.h), one chain per stream
   sfrt::TileSched dump_sched;  // sfrt_world_trace_points' own chain (never the frames')
   int cur_chain = 0;        // the chain of the launch between sched_begin and sched_end
-  // The ray cache (sfrt_raycache.h) of that launch: what its chain's policy decided, and the
-  // buffer launch_trace reads (null: today's kernel).  Counters: sfrt_world_ray_cache_stats.
-  bool ray_active = false;  // the launch takes part in the policy (an ordered, committing one)
-  sfrt::RayKey ray_key{};
-  sfrt::RayAction ray_action = sfrt::RayAction::kTrace;
-  const float* ray_cache = nullptr;
-  const sfrt::TileRec* tile_recs = nullptr;  // the tile records that go with ray_cache
-  int64_t ray_cached_frames = 0, ray_fills = 0;
-  // The cull cache (sfrt_raycache.h CullCachePolicy) of that launch, decided after the ray
-  // cache: the key, the action, the two buffers launch_trace reads (null: the launch culls for
-  // itself).  Counters: sfrt_world_cull_cache_stats.
-  sfrt::CullKey cull_key;
-  sfrt::RayAction cull_action = sfrt::RayAction::kTrace;
-  const sfrt::CullRec* cull_recs = nullptr;
-  const void* cull_wins = nullptr;
-  int64_t cull_fills = 0, cull_hits = 0;
-  // The hit cache (sfrt_raycache.h HitCachePolicy) of that launch, decided after the cull cache
-  // under the same key: kFill -- the launch runs the _hf kernel and stores its march results in
-  // hit_recs; kRead -- it shades from them and takes no part in the tile order (sched_end).
-  // Counters: sfrt_world_hit_cache_stats.
-  sfrt::RayAction hit_action = sfrt::RayAction::kTrace;
-  sfrt::HitRec* hit_recs = nullptr;
-  int64_t hit_fills = 0, hit_hits = 0;
-  int hit_mode() const {
-    return hit_action == sfrt::RayAction::kRead ? 2 : hit_action == sfrt::RayAction::kFill ? 1 : 0;
-  }
+  // The chains' caches (sfrt_raycache.h ChainCaches: directions and tile records, cull cache, hit
+  // cache), one per chain like chain_cam[]; a stream that takes a chain over keeps them.  Of the
+  // launch between sched_begin and sched_end: what its chain decided, which launch_trace reads
+  // (decided == false: the launch takes no part).  Counters: the three sfrt_world_*_cache_stats.
+  sfrt::ChainCaches caches[sfrt::TileChains::kChains];
+  sfrt::CullKey cull_key;  // sched_begin's scratch: the records' vector keeps its capacity
+  sfrt::TraceCaches launch_caches;
+  sfrt::CacheCounters cache_stats;
   // Device copies of the sphere records for launches that read them from memory
   // (> 64 spheres, trace_points): a ring of slots, each with pinned staging and
   // the event of the last launch that read it, so a slot is never overwritten
@@ -232,6 +215,7 @@ struct sfrt_world {
       if (p.copied) (void)hipEventDestroy(p.copied);
     }
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
+    for (sfrt::ChainCaches& c : caches) c.release_all([](void* p) { return hipFree(p) == hipSuccess; });
     scheds.release();
     dump_sched.release();
     (void)hipFree(d_tex);
@@ -456,64 +440,22 @@ struct sfrt_world {
     // a moving camera: the recorded classes are a frame or two off
     f.order_dilate = p.prev_cost && chain_last.valid &&
                      std::memcmp(&chain_last.cam, &cam, sizeof cam) != 0;
-    ray_active = false;
-    ray_cache = nullptr;
-    tile_recs = nullptr;
-    ray_action = sfrt::RayAction::kTrace;
-    cull_recs = nullptr;
-    cull_wins = nullptr;
-    cull_action = sfrt::RayAction::kTrace;
-    hit_recs = nullptr;
-    hit_action = sfrt::RayAction::kTrace;
+    launch_caches = sfrt::TraceCaches{};
     if (!aux && tile_order_on == 1 && p.tile_cost && sched.pending_key != 0) {
-      ray_active = true;
-      ray_key = make_ray_key(f, key);
-      const long long bytes = sfrt::ray_cache_bytes(tiles, (int)((key >> 56) & 7));
-      const long long budget = (long long)ray_cache_mb << 20;
-      // (others: without this chain's own cull cache -- a fill of the directions rewrites the
-      // tile records under it, so it is dropped first and takes no room from them)
-      ray_action = sched.ray_policy.decide(ray_key, bytes, sched.ray_dirs.bytes,
-                                           cache_bytes_held() - sched.ray_dirs.bytes - sched.cull_bytes(),
-                                           budget);
-      if (ray_action == sfrt::RayAction::kFill) release_cull_on(sched, s);
-      if (ray_action == sfrt::RayAction::kFill &&
-          !ray_fill(sched, f, bytes, sfrt::tile_rec_bytes(tiles), s)) {
-        sched.invalidate_caches();  // the buffers may be gone or half written
-        ray_action = sfrt::RayAction::kTrace;
-      }
-      if (ray_action != sfrt::RayAction::kTrace) {
-        ray_cache = (const float*)sched.ray_dirs.ptr;
-        tile_recs = (const sfrt::TileRec*)sched.ray_recs.ptr;
-      }
-      // The cull cache, on top of the tile records this launch reads (or has just filled).
-      make_cull_key(cull_key, ray_key, f, recs);
-      const bool list = f.n > sfrt::kInlineSpheres;
-      const long long rec_bytes = sfrt::cull_rec_bytes(tiles), win_bytes = sfrt::cull_win_bytes(tiles, list);
-      cull_action = sched.cull_policy.decide(cull_key, ray_action, rec_bytes + win_bytes, sched.cull_bytes(),
-                                             cache_bytes_held() - sched.cull_bytes(), budget);
-      if (cull_action == sfrt::RayAction::kFill &&
-          !cull_fill(sched, f, recs, rec_bytes, win_bytes, s)) {
-        sched.cull_policy.invalidate();  // the tile records are whole: the launch reads them
-        sched.hit_policy.invalidate();
-        cull_action = sfrt::RayAction::kTrace;
-      }
-      if (cull_action != sfrt::RayAction::kTrace) {
-        cull_recs = (const sfrt::CullRec*)sched.cull_recs.ptr;
-        cull_wins = sched.cull_wins.ptr;
-      }
-      // The hit cache, on top of the cull cache this launch reads (or has just filled), under the
-      // same key and a budget of its own.  The diagnostic builds exist to time the march: never.
-      const long long hit_bytes = sfrt::hit_cache_bytes(tiles, (int)((key >> 56) & 7));
-      hit_action = sched.hit_policy.decide(cull_key, cull_action, hit_bytes, sched.hit_recs.bytes,
-                                           hit_bytes_held() - sched.hit_recs.bytes,
-                                           sfrt::kDiagnosticBuild ? 0 : hit_budget_bytes());
-      if (hit_action == sfrt::RayAction::kFill && !reserve_on(sched.hit_recs, hit_bytes, s)) {
-        sched.hit_policy.invalidate();  // no memory for it: the launch stays on the cull-cache path
-        hit_action = sfrt::RayAction::kTrace;
-      }
-      if (hit_action != sfrt::RayAction::kTrace) hit_recs = (sfrt::HitRec*)sched.hit_recs.ptr;
+      make_cull_key(cull_key, make_ray_key(f, key), f, recs);
+      const int rays = (int)((key >> 56) & 7);
+      const sfrt::CacheSizes sizes{sfrt::ray_cache_bytes(tiles, rays), sfrt::tile_rec_bytes(tiles),
+                                   sfrt::cull_rec_bytes(tiles),
+                                   sfrt::cull_win_bytes(tiles, f.n > sfrt::kInlineSpheres),
+                                   sfrt::hit_cache_bytes(tiles, rays)};
+      sfrt::ChainCaches& mine = caches[cur_chain];
+      // (the diagnostic builds exist to time the march: no hit cache)
+      launch_caches = mine.begin(cull_key.ray, cull_key, sizes,
+                                 cache_bytes_held() - mine.bytes_under_ray_budget(),
+                                 hit_bytes_held() - mine.hit_bytes(), (long long)ray_cache_mb << 20,
+                                 sfrt::kDiagnosticBuild ? 0 : hit_budget_bytes(), CacheDevice{s, f, recs});
       // A reading launch marches nothing and takes no part in the tile order: nothing is linked.
-      if (hit_action == sfrt::RayAction::kRead) {
+      if (launch_caches.reading()) {
         sfrt::TileSchedPtrs{}.link(f);
         f.order_dilate = 0;
       }
@@ -546,92 +488,57 @@ struct sfrt_world {
     return k;
   }
 
-  long long ray_bytes_held() const {
-    long long held = 0;
-    for (const sfrt::TileSched& c : scheds.chain) held += c.ray_dirs.bytes;
-    return held;
-  }
-  long long cull_bytes_held() const {
-    long long held = 0;
-    for (const sfrt::TileSched& c : scheds.chain) held += c.cull_bytes();
-    return held;
+  // A sum over the chains' caches.
+  template <class Bytes>
+  long long held(Bytes bytes) const {
+    long long sum = 0;
+    for (const sfrt::ChainCaches& c : caches) sum += bytes(c);
+    return sum;
   }
   // SFRT_OPT_HIT_CACHE_MB in bytes: megabytes of 10^6 (sfrt.h says why), unlike the ray cache's MiB.
   long long hit_budget_bytes() const { return (long long)hit_cache_mb * 1000000ll; }
-  // What SFRT_OPT_HIT_CACHE_MB limits, and nothing else does.
-  long long hit_bytes_held() const {
-    long long held = 0;
-    for (const sfrt::TileSched& c : scheds.chain) held += c.hit_recs.bytes;
-    return held;
+  // Everything SFRT_OPT_RAY_CACHE_MB limits (the directions and the cull caches); what
+  // SFRT_OPT_HIT_CACHE_MB limits, and nothing else does.
+  long long cache_bytes_held() const {
+    return held([](const sfrt::ChainCaches& c) { return c.bytes_under_ray_budget(); });
   }
-  // Everything SFRT_OPT_RAY_CACHE_MB limits: the directions and the cull caches.
-  long long cache_bytes_held() const { return ray_bytes_held() + cull_bytes_held(); }
-  // The tile records' bytes: reported on their own, never counted against the budget.
-  long long tile_rec_bytes_held() const {
-    long long held = 0;
-    for (const sfrt::TileSched& c : scheds.chain) held += c.ray_recs.bytes;
-    return held;
+  long long hit_bytes_held() const {
+    return held([](const sfrt::ChainCaches& c) { return c.hit_bytes(); });
   }
 
-  // The chain's cache -- directions and tile records --, each buffer grown if need be in the
-  // order of s, filled for f on s (where the chain's launches run: sched.begin has waited for
-  // the device if another stream ran the last one).  false: the frame renders with today's
-  // kernel.
-  static bool ray_fill(sfrt::TileSched& sched, const sfrt::FrameRec& f, long long bytes,
-                       long long rec_bytes, hipStream_t s) {
-    if (!reserve_on(sched.ray_dirs, bytes, s) || !reserve_on(sched.ray_recs, rec_bytes, s)) return false;
-    return sfrt::launch_ray_fill(f, (float*)sched.ray_dirs.ptr,
-                                 (sfrt::TileRec*)sched.ray_recs.ptr, s) == 0;
-  }
-  // A chain's buffer grown, if need be, in the order of s.
-  static bool reserve_on(sfrt::CacheBuf& buf, long long bytes, hipStream_t s) {
-    const auto free_on_s = [s](void* p) {
+  // The device as a chain's caches see it (ChainCaches::begin): buffers freed and allocated in
+  // the order of s, where the chain's launches run (sched.begin has waited for the device if
+  // another stream ran the last one), and the fill kernels for f and recs queued on s.
+  struct CacheDevice {
+    hipStream_t s;
+    const sfrt::FrameRec& f;
+    const std::vector<sfrt::SphereRec>& recs;
+    bool free(void* p) const {
       if (hipFreeAsync(p, s) == hipSuccess) return true;
       (void)hipGetLastError();
       return false;
-    };
-    const auto alloc_on_s = [s](long long n) -> void* {
+    }
+    void* alloc(long long n) const {
       void* p = nullptr;
       if (hipMallocAsync(&p, (size_t)n, s) == hipSuccess) return p;
       (void)hipGetLastError();  // no memory for it: not an error of the frame
       return nullptr;
-    };
-    return buf.reserve(bytes, free_on_s, alloc_on_s);
-  }
-  // The chain's cull buffers freed in the order of s (before the tile records under them are
-  // refilled: what they hold is dropped either way, CullCachePolicy::commit).
-  static void release_cull_on(sfrt::TileSched& sched, hipStream_t s) {
-    const auto free_on_s = [s](void* p) {
-      if (hipFreeAsync(p, s) != hipSuccess) (void)hipGetLastError();
-      return true;
-    };
-    sched.cull_recs.release(free_on_s);
-    sched.cull_wins.release(free_on_s);
-    sched.cull_policy.valid = false;
-    sched.hit_recs.release(free_on_s);  // the hit cache lives on the cull cache
-    sched.hit_policy.valid = false;
-  }
-  // The chain's cull cache likewise, filled for f and recs on s from the chain's tile records
-  // (valid, or filled earlier on s for this launch).  false: the launch culls for itself.
-  static bool cull_fill(sfrt::TileSched& sched, const sfrt::FrameRec& f,
-                        const std::vector<sfrt::SphereRec>& recs, long long rec_bytes,
-                        long long win_bytes, hipStream_t s) {
-    if (!reserve_on(sched.cull_recs, rec_bytes, s) || !reserve_on(sched.cull_wins, win_bytes, s)) return false;
-    return sfrt::launch_cull_fill(f, recs.data(), (const sfrt::TileRec*)sched.ray_recs.ptr,
-                                  (sfrt::CullRec*)sched.cull_recs.ptr, sched.cull_wins.ptr, s) == 0;
-  }
+    }
+    bool fill_rays(float* dirs, sfrt::TileRec* tile_recs) const {
+      return sfrt::launch_ray_fill(f, dirs, tile_recs, s) == 0;
+    }
+    bool fill_cull(const sfrt::TileRec* tile_recs, sfrt::CullRec* cull_recs, void* cull_wins) const {
+      return sfrt::launch_cull_fill(f, recs.data(), tile_recs, cull_recs, cull_wins, s) == 0;
+    }
+  };
 
-  // SFRT_OPT_RAY_CACHE_MB lowered below what the chains hold: every cache goes.  The chains'
-  // streams may be gone (sfrt_sched.h), so the host waits for the device.
-  int ray_release_all() {
+  // An option lowered below what the chains hold (hit_only: SFRT_OPT_HIT_CACHE_MB, the hit caches
+  // go; else SFRT_OPT_RAY_CACHE_MB, every cache goes).  The chains' streams may be gone
+  // (sfrt_sched.h), so the host waits for the device.
+  int release_caches(bool hit_only) {
     HIP_TRY(hipDeviceSynchronize());
-    for (sfrt::TileSched& c : scheds.chain) c.release_ray_cache();
-    return SFRT_OK;
-  }
-  // SFRT_OPT_HIT_CACHE_MB lowered below what the chains hold: every hit cache goes, likewise.
-  int hit_release_all() {
-    HIP_TRY(hipDeviceSynchronize());
-    for (sfrt::TileSched& c : scheds.chain) c.release_hit_cache();
+    const auto free_now = [](void* p) { return hipFree(p) == hipSuccess; };
+    for (sfrt::ChainCaches& c : caches) hit_only ? c.release_hit(free_now) : c.release_all(free_now);
     return SFRT_OK;
   }
 
@@ -640,39 +547,25 @@ struct sfrt_world {
     sfrt::TileSchedPtrs p;
     p.tile_cost = f.tile_cost;
     sfrt::TileSched& sched = scheds.chain[cur_chain];
-    if (queued && hit_action == sfrt::RayAction::kRead) {
+    sfrt::ChainCaches& mine = caches[cur_chain];
+    if (queued && launch_caches.reading()) {
       // A launch that read the hit cache: the chain does not advance, and last_fill and the
       // chain's camera stay the last marching launch's (their classes are this frame's too: the
-      // key is equal).  The three policies are committed as for a reading launch.
+      // key is equal).
       sched.end_reading(s);
-      sched.ray_policy.commit(ray_key, ray_action, true);
-      ray_cached_frames++;
-      sched.cull_policy.commit(cull_key, ray_action, cull_action, true);
-      cull_hits++;
-      sched.hit_policy.commit(cull_key, ray_action, cull_action, hit_action, true);
-      hit_hits++;
+      mine.end(launch_caches, true, cache_stats);
       return SFRT_OK;
     }
-    if (!queued && hit_action == sfrt::RayAction::kRead) {  // linked into nothing: end() would pass it by
-      sched.reset();
-      sched.invalidate_caches();
-    }
+    if (!queued && launch_caches.reading()) sched.reset();  // linked into nothing: end() would pass it by
     HIP_TRY(sched.end(p, s, queued));
     if (!queued) {
+      // the failed launch of a chain -- an aux band's too -- leaves no cache to trust
+      if (p.tile_cost || launch_caches.decided) mine.end(launch_caches, false, cache_stats);
       chain_cam[cur_chain].valid = false;
       if (last_fill.chain == cur_chain) last_fill.valid = false;
       return SFRT_E_HIP;
     }
-    if (ray_active) {
-      sched.ray_policy.commit(ray_key, ray_action, true);
-      if (ray_action == sfrt::RayAction::kFill) ray_fills++;
-      if (ray_action != sfrt::RayAction::kTrace) ray_cached_frames++;
-      sched.cull_policy.commit(cull_key, ray_action, cull_action, true);
-      if (cull_action == sfrt::RayAction::kFill) cull_fills++;
-      if (cull_action == sfrt::RayAction::kRead) cull_hits++;
-      sched.hit_policy.commit(cull_key, ray_action, cull_action, hit_action, true);
-      if (hit_action == sfrt::RayAction::kFill) hit_fills++;
-    }
+    if (launch_caches.decided) mine.end(launch_caches, true, cache_stats);
     if (sched.committed) {
       chain_cam[cur_chain] = ChainCam{true, cam, f.sub_row0};
       // that launch wrote its classes into cost[k % 2] before end() advanced k
@@ -1011,13 +904,13 @@ int sfrt_world_set_option(sfrt_world* w, int option, int value) {
     if (value < 0) return SFRT_E_INVALID;
     // (0 also frees tile records left without directions by a fill that found no memory)
     if (((long long)value << 20) < w->cache_bytes_held() ||
-        (value == 0 && w->tile_rec_bytes_held() > 0)) {
+        (value == 0 && w->held([](const sfrt::ChainCaches& c) { return c.tile_rec_bytes(); }) > 0)) {
       sfrt::DeviceGuard g(w->device);
-      const int rc = w->ray_release_all();
+      const int rc = w->release_caches(false);
       if (rc) return rc;
     }
     if (value == 0)
-      for (sfrt::TileSched& c : w->scheds.chain) c.invalidate_caches();
+      for (sfrt::ChainCaches& c : w->caches) c.invalidate();
     w->ray_cache_mb = value;
     return SFRT_OK;
   }
@@ -1025,11 +918,11 @@ int sfrt_world_set_option(sfrt_world* w, int option, int value) {
     if (value < 0) return SFRT_E_INVALID;
     if ((long long)value * 1000000ll < w->hit_bytes_held()) {
       sfrt::DeviceGuard g(w->device);
-      const int rc = w->hit_release_all();
+      const int rc = w->release_caches(true);
       if (rc) return rc;
     }
     if (value == 0)
-      for (sfrt::TileSched& c : w->scheds.chain) c.hit_policy.invalidate();
+      for (sfrt::ChainCaches& c : w->caches) c.invalidate_hit();
     w->hit_cache_mb = value;
     return SFRT_OK;
   }
@@ -1040,26 +933,26 @@ int sfrt_world_ray_cache_stats(const sfrt_world* w, int64_t* cached_frames, int6
                                int64_t* bytes) {
   if (!w || !cached_frames || !fills || !bytes) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
-  *cached_frames = w->ray_cached_frames;
-  *fills = w->ray_fills;
-  *bytes = w->ray_bytes_held();
+  *cached_frames = w->cache_stats.ray_cached_frames;
+  *fills = w->cache_stats.ray_fills;
+  *bytes = w->held([](const sfrt::ChainCaches& c) { return c.dirs.bytes; });
   return SFRT_OK;
 }
 
 int sfrt_world_cull_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits, int64_t* bytes) {
   if (!w || !fills || !hits || !bytes) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
-  *fills = w->cull_fills;
-  *hits = w->cull_hits;
-  *bytes = w->cull_bytes_held();
+  *fills = w->cache_stats.cull_fills;
+  *hits = w->cache_stats.cull_hits;
+  *bytes = w->held([](const sfrt::ChainCaches& c) { return c.cull_bytes(); });
   return SFRT_OK;
 }
 
 int sfrt_world_hit_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits, int64_t* bytes) {
   if (!w || !fills || !hits || !bytes) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
-  *fills = w->hit_fills;
-  *hits = w->hit_hits;
+  *fills = w->cache_stats.hit_fills;
+  *hits = w->cache_stats.hit_hits;
   *bytes = w->hit_bytes_held();
   return SFRT_OK;
 }
@@ -1067,7 +960,7 @@ int sfrt_world_hit_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hit
 int sfrt_world_tile_record_bytes(const sfrt_world* w, int64_t* bytes) {
   if (!w || !bytes) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
-  *bytes = w->tile_rec_bytes_held();
+  *bytes = w->held([](const sfrt::ChainCaches& c) { return c.tile_rec_bytes(); });
   return SFRT_OK;
 }
 
@@ -1135,7 +1028,7 @@ static int update_image_body(sfrt_world* w, uint8_t* pixels, void* const* planes
   if ((rc = w->launchable(f))) return rc;
   rc = w->stage_spheres(f, recs, w->stream, false);
   if (rc) return rc;
-  if (sfrt::launch_trace(f, recs.data(), w->stream, nullptr, w->ring_event(), nullptr, nullptr,
+  if (sfrt::launch_trace(f, recs.data(), w->stream, nullptr, w->ring_event(), nullptr,
                          planes ? &aux : nullptr))
     return SFRT_E_HIP;
   if ((rc = w->launched_with())) return rc;
@@ -1209,9 +1102,7 @@ static int render_band_body(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes
   HIP_TRY(w->tex_written.before_read(s));
   if ((rc = w->sched_begin(f, recs, s, with_aux))) return rc;
   if ((rc = w->sched_end(f, s, sfrt::launch_trace(f, recs.data(), s, nullptr, w->ring_event(),
-                                                  w->ray_cache, w->tile_recs,
-                                                  with_aux ? &a : nullptr, 0, w->cull_recs,
-                                                  w->cull_wins, w->hit_recs, w->hit_mode()) == 0)))
+                                                  &w->launch_caches, with_aux ? &a : nullptr) == 0)))
     return rc;
   if ((rc = w->launched_with())) return rc;
   return SFRT_OK;
@@ -1286,7 +1177,7 @@ static int render_subset_body(sfrt_world* w, void* dev_frame, int64_t pitch_byte
   if (rc) return rc;
   // after the last texture upload (queued on w->stream, where the other launches run)
   HIP_TRY(w->tex_written.before_read(s));
-  if (sfrt::launch_trace(f, recs.data(), s, nullptr, w->ring_event(), nullptr, nullptr,
+  if (sfrt::launch_trace(f, recs.data(), s, nullptr, w->ring_event(), nullptr,
                          with_aux ? &a : nullptr, col_stride))
     return SFRT_E_HIP;
   return w->launched_with();
@@ -1636,8 +1527,7 @@ int sfrt_world_submit_frame(sfrt_world* w, uint8_t* pixels, int64_t* ticket) {
   if ((rc = w->sched_begin(f, recs, w->stream))) return rc;  // adaptive tile order, as render_band
   if ((rc = w->sched_end(f, w->stream,
                          sfrt::launch_trace(f, recs.data(), w->stream, nullptr, w->ring_event(),
-                                            w->ray_cache, w->tile_recs, nullptr, 0, w->cull_recs,
-                                            w->cull_wins, w->hit_recs, w->hit_mode()) == 0)))
+                                            &w->launch_caches) == 0)))
     return rc;
   if ((rc = w->launched_with())) return rc;
   HIP_TRY(hipEventRecord(slot.rendered, w->stream));

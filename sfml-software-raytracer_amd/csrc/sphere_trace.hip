@@ -1173,7 +1173,7 @@ __global__ __launch_bounds__(64) void k_trace_window_list_rc(FrameRec f,
   trace_tile_window_r<R, true, false, ActiveProbe, SS, true>(f, f.spheres, DumpArgs{}, rc, tr);
 }
 
-// The cull cache's kernels (sfrt_raycache.h CullCachePolicy), of their own once more.
+// The cull cache's kernels (sfrt_raycache.h CullRec, ChainCaches), of their own once more.
 // k_cull_fill: one wave per tile of the same grid runs the trace kernels' own cull_wave on the
 // cone of the tile's record, from the launch's own frame and sphere records under the same
 // flags (the same bits), and stores what it leaves: the lane's window (and list entry), and from
@@ -1237,7 +1237,7 @@ __global__ __launch_bounds__(64) void k_trace_window_list_cc(FrameRec f,
       f, f.spheres, DumpArgs{}, rc, nullptr, AuxArgs{}, 1, cr, cw);
 }
 
-// The hit cache's kernels (sfrt_raycache.h HitCachePolicy).  The _hf kernels are the _cc ones that
+// The hit cache's kernels (sfrt_raycache.h HitRec, ChainCaches).  The _hf kernels are the _cc ones that
 // also store their rays' march results (HIT = 1; they run once per key, so their occupancy is
 // left to the compiler); k_shade_hits[_list] shade a frame from those results (HIT = 2: no march,
 // see trace_tile_window_r), the records in the arguments or, n > 64, in the device ring.
@@ -1601,12 +1601,18 @@ int launch_cull_fill(const FrameRec& f, const SphereRec* host_spheres, const Til
 }
 
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
-                 const DumpArgs* dump, void* done_event, const float* ray_cache,
-                 const TileRec* tile_recs, const AuxArgs* aux, int place_xstride,
-                 const CullRec* cull_recs, const void* cull_wins, HitRec* hit_recs, int hit_mode) {
+                 const DumpArgs* dump, void* done_event, const TraceCaches* caches,
+                 const AuxArgs* aux, int place_xstride) {
   const long long tiles_y = (f.sub_rows + kTile - 1) / kTile;
   if (tiles_y <= 0 || f.sub_w <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
+  const TraceCaches c = caches ? *caches : TraceCaches{};
+  const float* const ray_cache = c.dirs;
+  const TileRec* const tile_recs = c.tile_recs;
+  const CullRec* const cull_recs = c.cull_recs;
+  const void* const cull_wins = c.cull_wins;
+  HitRec* const hit_recs = c.hit_recs;
+  const int hit_mode = c.hit == RayAction::kRead ? 2 : c.hit == RayAction::kFill ? 1 : 0;
   // the hit cache rides on the cull cache: 1 fills it from the marching launch, 2 shades from it
   if (hit_mode < 0 || hit_mode > 2 || (hit_mode != 0) != (hit_recs != nullptr)) return -1;
   if (hit_mode && (!cull_recs || dump || aux || place_xstride || kDiagnosticBuild)) return -1;

@@ -1,206 +1,31 @@
-// hitcache_check.cpp -- the hit cache's policy and record (csrc/sfrt_raycache.h HitRec,
-// HitCachePolicy) on the host: no HIP.  A chain is modelled as the world drives it (sfrt_world.cpp
-// sched_begin / sched_end): the ray cache decides first, then the cull cache, then the hit cache
-// under the cull cache's key and a budget of its own; a fill reserves the chain's CacheBufs
-// through counting allocators.  Built and run by tests/test_hit_cache_policy.py (g++, with
-// -fsanitize=address,undefined).
+// hitcache_check.cpp -- the hit cache and its record (csrc/sfrt_raycache.h HitRec, the hit layer
+// of ChainCaches) on the host: no HIP.  Every launch goes through ChainCaches::begin / end
+// (chain_harness.h): the directions decide first, then the cull cache, then the hit cache under the
+// cull cache's key and a budget of its own.  Built and run by tests/test_hit_cache_policy.py (g++,
+// with -fsanitize=address,undefined).
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <utility>
-#include <vector>
 
-#include "sfrt_raycache.h"
+#include "chain_harness.h"
 
-using sfrt::CacheBuf;
-using sfrt::CullCachePolicy;
-using sfrt::CullKey;
-using sfrt::HitCachePolicy;
-using sfrt::RayAction;
-using sfrt::RayCachePolicy;
-using sfrt::RayKey;
-
-static int failures = 0;
-#define EXPECT(c)                                             \
-  do {                                                        \
-    if (!(c)) {                                               \
-      std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c); \
-      failures++;                                             \
-    }                                                         \
-  } while (0)
-
-// sfrt_trace.h SphereRec's members (this test needs only the names).
-struct Rec {
-  float cx, cy, cz, r, s_pass, atan_c;
-  uint32_t tex_off, tex_wh;
+// One chain on the frames' grid.
+struct HitChain : Chain {
+  using Chain::Chain;
+  TraceCaches launch(const Frame& f, bool queued = true) { return Chain::launch(f.key(), kTiles, kRays, queued); }
 };
-
-static RayKey base_ray_key() {
-  RayKey k{};
-  const float fwd[3] = {0.0f, 0.0f, 1.0f}, right[3] = {1.0f, 0.0f, 0.0f}, up[3] = {0.0f, -1.0f, 0.0f};
-  for (int q = 0; q < 3; q++) {
-    k.fwd[q] = sfrt::ray_key_bits(fwd[q]);
-    k.right[q] = sfrt::ray_key_bits(right[q]);
-    k.up[q] = sfrt::ray_key_bits(up[q]);
-  }
-  k.h_start = sfrt::ray_key_bits(-1.3f);
-  k.h_inc = sfrt::ray_key_bits(0.01f);
-  k.v_start = sfrt::ray_key_bits(-0.8f);
-  k.v_inc = sfrt::ray_key_bits(0.02f);
-  k.xstart = 0; k.xadd = 1; k.ystart = 0; k.yadd = 1;
-  k.sub_w = 72; k.sub_row0 = 0; k.sub_rows = 20;
-  k.tile_key = (1ll << 62) | (4ll << 56) | (3ll << 28) | 3;
-  return k;
-}
-
-static std::vector<Rec> base_records(int n) {
-  std::vector<Rec> r((size_t)n);
-  for (int k = 0; k < n; k++)
-    r[(size_t)k] = Rec{0.5f * (float)k, -0.25f * (float)k, 3.0f + (float)k, 1.0f + 0.125f * (float)k,
-                      0.75f + (float)k, 0.1f * (float)k, 0u, 128u | (128u << 16)};
-  return r;
-}
-
-// A launch's frame as far as the cull and the march read it.
-struct Frame {
-  RayKey ray = base_ray_key();
-  float cam[3] = {0.25f, -0.5f, 0.125f};
-  float cull_margin = 0.0123f, first_l = 0.75f;
-  int cull = 1;
-  std::vector<Rec> recs = base_records(10);
-
-  CullKey key() const {
-    CullKey k;
-    k.ray = ray;
-    for (int q = 0; q < 3; q++) k.cam[q] = sfrt::ray_key_bits(cam[q]);
-    k.cull_margin = sfrt::ray_key_bits(cull_margin);
-    k.first_l = sfrt::ray_key_bits(first_l);
-    k.cull = cull;
-    k.set_records(recs.data(), (int)recs.size());
-    return k;
-  }
-};
-
-constexpr long long kMiB = 1ll << 20;
-constexpr long long kTiles = 9;
-constexpr int kRays = 4;
-
-// What one launch did: the three decisions.
-struct Did {
-  RayAction ray, cull, hit;
-};
-
-// One chain and the world's budgets around it, with counting allocators.
-struct Chain {
-  RayCachePolicy ray;
-  CullCachePolicy cull;
-  HitCachePolicy hit;
-  CacheBuf ray_dirs, cull_recs, cull_wins, hit_recs;
-  long long budget = 512 * kMiB, hit_budget = 512 * kMiB, others = 0, hit_others = 0;
-  int allocs = 0, frees = 0, live = 0;
-  bool alloc_fails = false, hit_alloc_fails = false;
-  int cull_fills = 0, cull_hits = 0, hit_fills = 0, hit_hits = 0, cached_frames = 0;
-  int chain_k = 0;  // TileSched::k: launches that advanced the tile order
-
-  ~Chain() {
-    for (CacheBuf* b : {&ray_dirs, &cull_recs, &cull_wins, &hit_recs})
-      b->release([this](void* p) { return free_fn(p); });
-    if (live != 0) {
-      std::printf("FAIL: %d buffers leaked\n", live);
-      failures++;
-    }
-  }
-  bool free_fn(void* p) {
-    std::free(p);
-    frees++;
-    live--;
-    return true;
-  }
-  void* alloc_fn(long long n, bool fails) {
-    if (fails) return nullptr;
-    allocs++;
-    live++;
-    return std::malloc((size_t)n);
-  }
-  bool reserve(CacheBuf& b, long long n, bool fails = false) {
-    return b.reserve(n, [this](void* p) { return free_fn(p); },
-                     [this, fails](long long m) { return alloc_fn(m, fails || alloc_fails); });
-  }
-  long long cull_bytes() const { return cull_recs.bytes + cull_wins.bytes; }
-  void invalidate_caches() {  // TileSched::invalidate_caches
-    ray.invalidate();
-    cull.invalidate();
-    hit.invalidate();
-  }
-
-  // sched_begin and sched_end of one launch.
-  Did launch(const Frame& f, bool queued = true) {
-    const RayKey rk = f.ray;
-    const long long ray_bytes = sfrt::ray_cache_bytes(kTiles, kRays);
-    RayAction ra = ray.decide(rk, ray_bytes, ray_dirs.bytes, others, budget);
-    if (ra == RayAction::kFill) {  // release_cull_on: the cull cache and the hit cache on it go first
-      for (CacheBuf* b : {&cull_recs, &cull_wins, &hit_recs}) b->release([this](void* p) { return free_fn(p); });
-      cull.valid = false;
-      hit.valid = false;
-    }
-    if (ra == RayAction::kFill && !reserve(ray_dirs, ray_bytes)) {
-      invalidate_caches();
-      ra = RayAction::kTrace;
-    }
-    const CullKey ck = f.key();
-    const bool list = ck.n > 64;
-    const long long rb = sfrt::cull_rec_bytes(kTiles), wb = sfrt::cull_win_bytes(kTiles, list);
-    RayAction ca = cull.decide(ck, ra, rb + wb, cull_bytes(), others + ray_dirs.bytes, budget);
-    if (ca == RayAction::kFill && !(reserve(cull_recs, rb) && reserve(cull_wins, wb))) {
-      cull.invalidate();
-      hit.invalidate();
-      ca = RayAction::kTrace;
-    }
-    const long long hb = sfrt::hit_cache_bytes(kTiles, kRays);
-    RayAction ha = hit.decide(ck, ca, hb, hit_recs.bytes, hit_others, hit_budget);
-    if (ha == RayAction::kFill && !reserve(hit_recs, hb, hit_alloc_fails)) {
-      hit.invalidate();
-      ha = RayAction::kTrace;
-    }
-    if (!queued) {  // TileSched::end, or the reading launch's own branch: everything goes
-      invalidate_caches();
-      chain_k = 0;
-    } else {
-      ray.commit(rk, ra, true);
-      cull.commit(ck, ra, ca, true);
-      hit.commit(ck, ra, ca, ha, true);
-      if (ra != RayAction::kTrace) cached_frames++;
-      if (ca == RayAction::kFill) cull_fills++;
-      if (ca == RayAction::kRead) cull_hits++;
-      if (ha == RayAction::kFill) hit_fills++;
-      if (ha == RayAction::kRead) hit_hits++;
-      if (ha != RayAction::kRead) chain_k++;  // a reading launch does not advance the chain
-    }
-    // the invariant of item 5: never valid without a valid cull cache
-    EXPECT(!hit.valid || cull.valid);
-    EXPECT(!hit.valid || hit.cached.same(cull.cached));
-    return Did{ra, ca, ha};
-  }
-};
-
-static bool is(const Did& d, RayAction r, RayAction c, RayAction h) {
-  return d.ray == r && d.cull == c && d.hit == h;
-}
-
-constexpr RayAction T = RayAction::kTrace, F = RayAction::kFill, R = RayAction::kRead;
 
 static void first_frames() {
-  Chain c;
+  HitChain c;
   Frame f;
   EXPECT(is(c.launch(f), T, T, T));
-  EXPECT(c.hit_fills == 0 && c.hit_hits == 0 && c.hit_recs.bytes == 0);
+  EXPECT(c.stats.hit_fills == 0 && c.stats.hit_hits == 0 && c.caches.hit_recs.bytes == 0);
   // the second launch of the key: the directions, the cull and -- the _hf kernel being the _cc one --
   // the march results are all filled by it
   EXPECT(is(c.launch(f), F, F, F));
-  EXPECT(c.hit_fills == 1 && c.hit_hits == 0 && c.hit_recs.bytes == sfrt::hit_cache_bytes(kTiles, kRays));
+  EXPECT(c.stats.hit_fills == 1 && c.stats.hit_hits == 0 && c.caches.hit_recs.bytes == sfrt::hit_cache_bytes(kTiles, kRays));
   for (int q = 0; q < 3; q++) EXPECT(is(c.launch(f), R, R, R));
-  EXPECT(c.hit_fills == 1 && c.hit_hits == 3 && c.cull_hits == 3 && c.cached_frames == 4);
+  EXPECT(c.stats.hit_fills == 1 && c.stats.hit_hits == 3 && c.stats.cull_hits == 3 && c.stats.ray_cached_frames == 4);
   EXPECT(c.chain_k == 2);  // the two marching launches only
   EXPECT(sfrt::hit_cache_bytes(32400, 4) == 132710400ll);  // the 4K frame at four pixels per lane
 }
@@ -208,19 +33,19 @@ static void first_frames() {
 // A change of `change` misses, falls back, and the second launch of the new state refills.
 template <class Change>
 static void key_change(const char* what, bool view, Change change) {
-  Chain c;
+  HitChain c;
   Frame f;
   c.launch(f); c.launch(f); c.launch(f);
-  EXPECT(c.hit.valid);
+  EXPECT(c.caches.hit.valid);
   change(f);
-  const Did d1 = c.launch(f);
+  const TraceCaches d1 = c.launch(f);
   if (d1.hit != T) { std::printf("FAIL %s: first launch of a new key did not miss\n", what); failures++; }
   EXPECT(view ? d1.ray == T : d1.ray == R);
-  const Did d2 = c.launch(f);
+  const TraceCaches d2 = c.launch(f);
   if (d2.hit != F) { std::printf("FAIL %s: second launch of a new key did not refill\n", what); failures++; }
   EXPECT(view ? (d2.ray == F && d2.cull == F) : (d2.ray == R && d2.cull == F));
   EXPECT(is(c.launch(f), R, R, R));
-  EXPECT(c.hit_fills == 2);
+  EXPECT(c.stats.hit_fills == 2);
 }
 
 static void key_changes() {
@@ -242,7 +67,7 @@ static void key_changes() {
   key_change("rows", true, [](Frame& f) { f.ray.sub_rows = 12; });
   key_change("tile key", true, [](Frame& f) { f.ray.tile_key ^= 1ll << 56; });
   // what the key does not hold keeps hitting: texture slots, the centre's angle term
-  Chain c;
+  HitChain c;
   Frame f;
   c.launch(f); c.launch(f);
   f.recs[2].tex_off = 4096u;
@@ -259,19 +84,19 @@ static void key_changes() {
 
 static void refusals() {
   {  // a hit budget too small: the launch stays on the cull-cache path, whose stats are as without
-    Chain c;
+    HitChain c;
     c.hit_budget = sfrt::hit_cache_bytes(kTiles, kRays) - 1;
     Frame f;
     c.launch(f);
     EXPECT(is(c.launch(f), F, F, T));
     EXPECT(is(c.launch(f), R, R, T));
-    EXPECT(c.hit_fills == 0 && c.hit_hits == 0 && c.hit_recs.bytes == 0 && c.cull_fills == 1 && c.cull_hits == 1);
+    EXPECT(c.stats.hit_fills == 0 && c.stats.hit_hits == 0 && c.caches.hit_recs.bytes == 0 && c.stats.cull_fills == 1 && c.stats.cull_hits == 1);
     c.hit_budget = sfrt::hit_cache_bytes(kTiles, kRays);  // exactly enough: the next launch fills
     EXPECT(is(c.launch(f), R, R, F));
     EXPECT(is(c.launch(f), R, R, R));
   }
   {  // other chains' hit bytes count against the budget, the ray cache's bytes do not
-    Chain c;
+    HitChain c;
     c.hit_budget = 2 * sfrt::hit_cache_bytes(kTiles, kRays) - 1;
     c.hit_others = sfrt::hit_cache_bytes(kTiles, kRays);
     c.others = 100 * kMiB;
@@ -282,61 +107,61 @@ static void refusals() {
     EXPECT(is(c.launch(f), R, R, F));
   }
   {  // off: 0
-    Chain c;
+    HitChain c;
     c.hit_budget = 0;
     Frame f;
     c.launch(f); c.launch(f);
     EXPECT(is(c.launch(f), R, R, T));
-    EXPECT(c.allocs == 3);
+    EXPECT(c.dev.allocs == 4);
   }
   {  // the ray cache's budget at 0 turns everything off
-    Chain c;
+    HitChain c;
     c.budget = 0;
     Frame f;
     c.launch(f); c.launch(f);
     EXPECT(is(c.launch(f), T, T, T));
-    EXPECT(c.allocs == 0);
+    EXPECT(c.dev.allocs == 0);
   }
   {  // no memory for the records: not an error, the launch stays on the cull cache, a later one retries
-    Chain c;
-    c.hit_alloc_fails = true;
+    HitChain c;
+    c.dev.fail_alloc_of = sfrt::hit_cache_bytes(kTiles, kRays);
     Frame f;
     c.launch(f);
     EXPECT(is(c.launch(f), F, F, T));
-    EXPECT(!c.hit.valid && c.hit_recs.bytes == 0);
-    c.hit_alloc_fails = false;
+    EXPECT(!c.caches.hit.valid && c.caches.hit_recs.bytes == 0);
+    c.dev.fail_alloc_of = -1;
     EXPECT(is(c.launch(f), R, R, F));  // the launch itself was committed: its key is the previous one
     EXPECT(is(c.launch(f), R, R, R));
   }
 }
 
 static void failed_launches() {
-  Chain c;
+  HitChain c;
   Frame f;
   c.launch(f); c.launch(f); c.launch(f);
-  EXPECT(c.hit.valid);
+  EXPECT(c.caches.hit.valid);
   EXPECT(is(c.launch(f, false), R, R, R));  // a reading launch that failed: everything goes
-  EXPECT(!c.hit.valid && !c.cull.valid && !c.ray.valid && c.chain_k == 0);
+  EXPECT(!c.caches.hit.valid && !c.caches.cull.valid && !c.caches.ray.valid && c.chain_k == 0);
   EXPECT(is(c.launch(f), T, T, T));
   EXPECT(is(c.launch(f), F, F, F));
   EXPECT(is(c.launch(f), R, R, R));
   // a failed fill of the directions' buffer drops all three
-  Chain d;
+  HitChain d;
   d.launch(f);
-  d.alloc_fails = true;
+  d.dev.fail_alloc = true;
   EXPECT(is(d.launch(f), T, T, T));
-  EXPECT(!d.hit.valid && !d.cull.valid && !d.ray.valid);
+  EXPECT(!d.caches.hit.valid && !d.caches.cull.valid && !d.caches.ray.valid);
 }
 
 static void takeover() {
   // Another stream takes the chain over: TileSched::begin waits for the device and the chain goes on
-  // with every cache as it is -- the policies never see the stream.
-  Chain c;
+  // with every cache as it is -- the caches never see the stream.
+  HitChain c;
   Frame f;
   c.launch(f); c.launch(f);
-  const void* p = c.hit_recs.ptr;
+  const void* p = c.caches.hit_recs.ptr;
   EXPECT(is(c.launch(f), R, R, R));  // (the launch of the other stream)
-  EXPECT(c.hit_recs.ptr == p && c.hit.valid);
+  EXPECT(c.caches.hit_recs.ptr == p && c.caches.hit.valid);
   // marching resumes after reading launches as if they had not happened: the chain counted only
   // the marching launches
   const int k0 = c.chain_k;
@@ -346,6 +171,88 @@ static void takeover() {
   g.cam[2] += 0.25f;
   EXPECT(is(c.launch(g), R, T, T));
   EXPECT(c.chain_k == k0 + 1);
+}
+
+// Two chains of one world: each launch is told what the other chain holds, as sched_begin sums it.
+static TraceCaches launch_beside(HitChain& c, const HitChain& other, const Frame& f) {
+  c.others = other.caches.bytes_under_ray_budget();
+  c.hit_others = other.caches.hit_bytes();
+  return c.launch(f);
+}
+
+static void shared_budgets() {
+  const long long ray = sfrt::ray_cache_bytes(kTiles, kRays);
+  const long long cull = sfrt::cull_rec_bytes(kTiles) + sfrt::cull_win_bytes(kTiles, false);
+  const long long hit = sfrt::hit_cache_bytes(kTiles, kRays);
+  Frame f;
+  {  // one ray budget: the second chain's fill is refused while the first holds its bytes
+    HitChain a, b;
+    a.budget = b.budget = 2 * ray + cull - 1;
+    launch_beside(a, b, f);
+    EXPECT(is(launch_beside(a, b, f), F, F, F));
+    EXPECT(a.caches.bytes_under_ray_budget() == ray + cull && a.caches.hit_bytes() == hit);
+    EXPECT(a.caches.tile_rec_bytes() == sfrt::tile_rec_bytes(kTiles));  // held, and counted nowhere
+    launch_beside(b, a, f);
+    EXPECT(is(launch_beside(b, a, f), T, T, T));
+    EXPECT(b.dev.allocs == 0);
+    EXPECT(is(launch_beside(a, b, f), R, R, R));  // the first chain is none the worse
+    a.release();  // (an option lowered, say)
+    EXPECT(is(launch_beside(b, a, f), F, F, F));
+    EXPECT(is(launch_beside(b, a, f), R, R, R));
+  }
+  {  // room for the second chain's directions but not for its cull cache
+    HitChain a, b;
+    a.budget = b.budget = 2 * ray + 2 * cull - 1;
+    launch_beside(a, b, f); launch_beside(a, b, f);
+    launch_beside(b, a, f);
+    EXPECT(is(launch_beside(b, a, f), F, T, T));
+    EXPECT(b.caches.bytes_under_ray_budget() == ray);
+  }
+  {  // both budgets exactly twice one chain's figures: both chains fill everything -- the tile
+     // records the two hold are never counted
+    HitChain a, b;
+    a.budget = b.budget = 2 * (ray + cull);
+    a.hit_budget = b.hit_budget = 2 * hit;
+    launch_beside(a, b, f); launch_beside(a, b, f);
+    launch_beside(b, a, f);
+    EXPECT(is(launch_beside(b, a, f), F, F, F));
+    EXPECT(a.caches.tile_rec_bytes() + b.caches.tile_rec_bytes() == 2 * sfrt::tile_rec_bytes(kTiles));
+    EXPECT(is(launch_beside(a, b, f), R, R, R) && is(launch_beside(b, a, f), R, R, R));
+  }
+  {  // one hit budget, a byte short of two chains: the second stays on the cull cache until the
+     // first lets its records go
+    HitChain a, b;
+    a.hit_budget = b.hit_budget = 2 * hit - 1;
+    launch_beside(a, b, f); launch_beside(a, b, f);
+    launch_beside(b, a, f);
+    EXPECT(is(launch_beside(b, a, f), F, F, T));
+    EXPECT(is(launch_beside(b, a, f), R, R, T) && b.caches.hit_bytes() == 0);
+    a.caches.release_hit([&a](void* p) { return a.dev.free(p); });
+    EXPECT(a.caches.hit_bytes() == 0 && a.caches.bytes_under_ray_budget() == ray + cull);
+    EXPECT(is(launch_beside(b, a, f), R, R, F));
+    EXPECT(is(launch_beside(b, a, f), R, R, R));
+    // the first chain, its records released, starts over and finds the room taken
+    EXPECT(is(launch_beside(a, b, f), R, R, T) && is(launch_beside(a, b, f), R, R, T));
+  }
+}
+
+// A launch that takes no part (an aux band: sched_begin calls neither begin nor end for it) between
+// two reading launches leaves the state and the counters as they were.
+static void bystander() {
+  HitChain c;
+  Frame f;
+  c.launch(f); c.launch(f);
+  EXPECT(is(c.launch(f), R, R, R));
+  const sfrt::CacheCounters n0 = c.stats;
+  const sfrt::ChainCaches s0 = c.caches;
+  const int allocs0 = c.dev.allocs, k0 = c.chain_k;
+  // (the aux launch: nothing of the chain's caches is called)
+  EXPECT(std::memcmp(&n0, &c.stats, sizeof n0) == 0 && c.dev.allocs == allocs0 && c.chain_k == k0);
+  EXPECT(c.caches.ray.valid && c.caches.cull.valid && c.caches.hit.valid && c.caches.hit.have_prev);
+  EXPECT(c.caches.hit_recs.ptr == s0.hit_recs.ptr && c.caches.hit.cached.same(s0.hit.cached));
+  EXPECT(is(c.launch(f), R, R, R));
+  EXPECT(c.stats.hit_hits == n0.hit_hits + 1 && c.stats.hit_fills == 1 && c.stats.cull_hits == n0.cull_hits + 1 &&
+         c.stats.ray_cached_frames == n0.ray_cached_frames + 1);
 }
 
 static void records() {
@@ -373,6 +280,8 @@ int main() {
   refusals();
   failed_launches();
   takeover();
+  shared_budgets();
+  bystander();
   records();
   if (failures) {
     std::printf("hitcache_check: %d failures\n", failures);

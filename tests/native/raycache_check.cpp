@@ -1,4 +1,5 @@
-// raycache_check.cpp -- the ray cache's policy (csrc/sfrt_raycache.h) on the host: no HIP.
+// raycache_check.cpp -- the policy of one cache layer (csrc/sfrt_raycache.h CacheLayer), as the
+// directions' layer uses it, on the host: no HIP.
 // Built and run by tests/test_ray_cache_policy.py (g++, with -fsanitize=address,undefined).
 #include <cstdio>
 #include <cstdlib>
@@ -7,8 +8,8 @@
 #include "sfrt_raycache.h"
 
 using sfrt::RayAction;
-using sfrt::RayCachePolicy;
 using sfrt::RayKey;
+using RayLayer = sfrt::CacheLayer<RayKey>;
 
 static int failures = 0;
 #define EXPECT(c)                                             \
@@ -39,12 +40,14 @@ static RayKey base_key() {
 
 constexpr long long kMiB = 1ll << 20;
 
-// One launch as the world makes it: decide, then commit the decision.
-static RayAction launch(RayCachePolicy& p, const RayKey& k, long long bytes = 1000,
+// One launch as ChainCaches makes it for the layer with none below: decide, then commit the
+// decision -- or, the launch having failed, invalidate.
+static RayAction launch(RayLayer& p, const RayKey& k, long long bytes = 1000,
                         long long held = 0, long long others = 0, long long budget = 512 * kMiB,
                         bool queued = true) {
-  const RayAction a = p.decide(k, bytes, held, others, budget);
-  p.commit(k, a, queued);
+  const RayAction a = p.decide(k, RayAction::kRead, bytes, held, others, budget);
+  if (queued) p.commit(k, a, false);
+  else p.invalidate();
   return a;
 }
 
@@ -81,7 +84,7 @@ static std::vector<RayKey> single_field_changes(const RayKey& k) {
 int main() {
   const RayKey k = base_key();
   {  // fill only on the second consecutive equal key, read from then on
-    RayCachePolicy p;
+    RayLayer p;
     EXPECT(launch(p, k) == RayAction::kTrace);
     EXPECT(!p.valid);
     EXPECT(launch(p, k) == RayAction::kFill);
@@ -94,7 +97,7 @@ int main() {
     EXPECT(changed.size() == 23);
     for (const RayKey& c : changed) {
       EXPECT(!c.same(k) && !k.same(c));
-      RayCachePolicy p;
+      RayLayer p;
       launch(p, k);
       launch(p, k);
       EXPECT(launch(p, c) == RayAction::kTrace);  // no read of another key's directions
@@ -107,7 +110,7 @@ int main() {
     }
   }
   {  // a camera that turns every frame never fills
-    RayCachePolicy p;
+    RayLayer p;
     for (uint32_t t = 0; t < 100; t++) {
       RayKey c = k;
       c.fwd[0] = t;
@@ -121,28 +124,28 @@ int main() {
     for (int t = 0; t < 10; t++) EXPECT(launch(p, t % 2 ? c : k) == RayAction::kTrace);
   }
   {  // the budget: a fill past it is refused, and the frame renders as without the cache
-    RayCachePolicy p;
+    RayLayer p;
     launch(p, k);
     EXPECT(launch(p, k, 2 * kMiB, 0, 0, 1 * kMiB) == RayAction::kTrace);
     EXPECT(!p.valid);
     EXPECT(launch(p, k, 2 * kMiB, 0, 0, 2 * kMiB) == RayAction::kFill);  // exactly the budget fits
-    RayCachePolicy q;
+    RayLayer q;
     launch(q, k);
     EXPECT(launch(q, k, 2 * kMiB, 0, 3 * kMiB, 4 * kMiB) == RayAction::kTrace);  // other chains count
     EXPECT(launch(q, k, 2 * kMiB, 0, 2 * kMiB, 4 * kMiB) == RayAction::kFill);
     // a smaller cache into the chain's larger buffer keeps that buffer: its size counts
-    RayCachePolicy r;
+    RayLayer r;
     launch(r, k);
     EXPECT(launch(r, k, 1 * kMiB, 3 * kMiB, 2 * kMiB, 4 * kMiB) == RayAction::kTrace);
     EXPECT(launch(r, k, 1 * kMiB, 3 * kMiB, 1 * kMiB, 4 * kMiB) == RayAction::kFill);
     // off
-    RayCachePolicy o;
+    RayLayer o;
     for (int t = 0; t < 4; t++) EXPECT(launch(o, k, 1000, 0, 0, 0) == RayAction::kTrace);
     // a valid cache is not read once the option is 0
-    EXPECT(p.valid && p.decide(k, 2 * kMiB, 2 * kMiB, 0, 0) == RayAction::kTrace);
+    EXPECT(p.valid && p.decide(k, RayAction::kRead, 2 * kMiB, 2 * kMiB, 0, 0) == RayAction::kTrace);
   }
   {  // a failed launch invalidates: the next two launches are a first and a second one again
-    RayCachePolicy p;
+    RayLayer p;
     launch(p, k);
     launch(p, k);
     EXPECT(launch(p, k, 1000, 1000, 0, 512 * kMiB, false) == RayAction::kRead);
@@ -150,7 +153,7 @@ int main() {
     EXPECT(launch(p, k) == RayAction::kTrace);
     EXPECT(launch(p, k) == RayAction::kFill);
     // a failed filling launch leaves no valid cache either
-    RayCachePolicy q;
+    RayLayer q;
     launch(q, k);
     EXPECT(launch(q, k, 1000, 0, 0, 512 * kMiB, false) == RayAction::kFill);
     EXPECT(!q.valid);

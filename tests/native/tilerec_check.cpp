@@ -1,30 +1,15 @@
 // tilerec_check.cpp -- the tile records of the ray cache (csrc/sfrt_raycache.h) on the host: the
 // record's layout as the fill kernel and the trace kernels both see it through that one header,
-// and a chain's allocate / keep / invalidate bookkeeping of its two buffers (CacheBuf), driven
-// by RayCachePolicy's decisions the way sfrt_world.cpp's sched_begin / sched_end drive it -- with
-// counting allocators in place of the stream-ordered HIP calls.  No HIP.
+// and a chain's allocate / keep / invalidate bookkeeping of the directions' and the records'
+// buffers, through ChainCaches::begin / end (chain_harness.h) under a walking camera -- the cull
+// key changes with every launch, so only the ray layer ever acts.  No HIP.
 // Built and run by tests/test_tile_record_layout.py (g++, with -fsanitize=address,undefined).
 #include <cstddef>
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
-#include "sfrt_raycache.h"
+#include "chain_harness.h"
 
-using sfrt::CacheBuf;
-using sfrt::RayAction;
-using sfrt::RayCachePolicy;
-using sfrt::RayKey;
 using sfrt::TileRec;
-
-static int failures = 0;
-#define EXPECT(c)                                             \
-  do {                                                        \
-    if (!(c)) {                                               \
-      std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c); \
-      failures++;                                             \
-    }                                                         \
-  } while (0)
 
 // The layout the kernels rely on: eight dwords in this order, one aligned 32-byte load.
 static_assert(std::is_standard_layout<TileRec>::value && std::is_trivially_copyable<TileRec>::value,
@@ -39,72 +24,28 @@ static_assert(sizeof(((TileRec*)nullptr)->wide) == 4 && sizeof(((TileRec*)nullpt
                   sizeof(((TileRec*)nullptr)->sin_t) == 4,
               "binary32 and u32 fields");
 
-constexpr long long kMiB = 1ll << 20;
+using Heap = Device;
 
-// The host stand-in for the device heap: every live allocation is a real one (the address
-// sanitizer then sees a double free or a leak), counted.
-struct Heap {
-  int allocs = 0, frees = 0;
-  long long live = 0;
-  bool fail_alloc = false, fail_free = false;
-};
+// One chain whose camera walks: every launch's cull key is another one.
+struct WalkingChain : Chain {
+  uint32_t step = 0;
+  explicit WalkingChain(Heap* h) : Chain(*h) {}
 
-// One chain as sfrt_sched.h TileSched holds it, and one launch as sfrt_world.cpp makes it.
-struct Chain {
-  RayCachePolicy policy;
-  CacheBuf dirs, recs;
-  Heap* heap;
-
-  explicit Chain(Heap* h) : heap(h) {}
-  ~Chain() { release(); }
-
-  bool fill(long long bytes, long long rec_bytes) {
-    Heap* h = heap;
-    const auto free_fn = [h](void* p) {
-      if (h->fail_free) return false;
-      std::free(p);
-      h->frees++;
-      return true;
-    };
-    const auto alloc_fn = [h](long long n) -> void* {
-      if (h->fail_alloc) return nullptr;
-      h->allocs++;
-      return std::malloc((size_t)n);
-    };
-    return dirs.reserve(bytes, free_fn, alloc_fn) && recs.reserve(rec_bytes, free_fn, alloc_fn);
-  }
-  void release() {
-    Heap* h = heap;
-    const auto free_fn = [h](void* p) {
-      std::free(p);
-      h->frees++;
-      return true;
-    };
-    dirs.release(free_fn);
-    recs.release(free_fn);
-    policy.invalidate();
-  }
   // what the launch reads: both buffers, or neither
   struct Launch {
     RayAction action;
     const void* dirs;
     const void* recs;
   };
-  Launch launch(const RayKey& k, long long tiles, int rays, long long budget = 512 * kMiB,
-                bool queued = true, long long others = 0) {
-    const long long bytes = sfrt::ray_cache_bytes(tiles, rays);
-    RayAction a = policy.decide(k, bytes, dirs.bytes, others, budget);
-    if (a == RayAction::kFill && !fill(bytes, sfrt::tile_rec_bytes(tiles))) {
-      policy.invalidate();
-      a = RayAction::kTrace;
-    }
-    Launch l{a, nullptr, nullptr};
-    if (a != RayAction::kTrace) {
-      l.dirs = dirs.ptr;
-      l.recs = recs.ptr;
-    }
-    policy.commit(k, a, queued);
-    return l;
+  Launch launch(const RayKey& k, long long tiles, int rays, long long ray_budget = 512 * kMiB,
+                bool queued = true) {
+    budget = ray_budget;
+    CullKey ck;
+    ck.ray = k;
+    ck.cam[0] = step++;
+    const TraceCaches d = Chain::launch(ck, tiles, rays, queued);
+    EXPECT(d.cull == T && d.hit == T && caches.cull_bytes() == 0 && caches.hit_bytes() == 0);
+    return Launch{d.ray, d.dirs, d.tile_recs};
   }
 };
 
@@ -140,17 +81,17 @@ int main() {
   }
   Heap heap;
   {  // allocate with the fill, keep while the key is read, keep on a position change
-    Chain c(&heap);
+    WalkingChain c(&heap);
     const RayKey k = key_of(4, 7, 4);
-    Chain::Launch l = c.launch(k, 28, 4);
+    WalkingChain::Launch l = c.launch(k, 28, 4);
     EXPECT(l.action == RayAction::kTrace && !l.dirs && !l.recs);
-    EXPECT(c.dirs.bytes == 0 && c.recs.bytes == 0 && heap.allocs == 0);
+    EXPECT(c.caches.dirs.bytes == 0 && c.caches.tile_recs.bytes == 0 && heap.allocs == 0);
     l = c.launch(k, 28, 4);
     EXPECT(l.action == RayAction::kFill && l.dirs && l.recs);
-    EXPECT(c.dirs.bytes == sfrt::ray_cache_bytes(28, 4) && c.recs.bytes == 28 * 32);
+    EXPECT(c.caches.dirs.bytes == sfrt::ray_cache_bytes(28, 4) && c.caches.tile_recs.bytes == 28 * 32);
     EXPECT(heap.allocs == 2 && heap.frees == 0);
-    const void* d0 = c.dirs.ptr;
-    const void* r0 = c.recs.ptr;
+    const void* d0 = c.caches.dirs.ptr;
+    const void* r0 = c.caches.tile_recs.ptr;
     for (int t = 0; t < 3; t++) {  // the key holds no camera position: walking reads
       l = c.launch(k, 28, 4);
       EXPECT(l.action == RayAction::kRead && l.dirs == d0 && l.recs == r0);
@@ -168,38 +109,38 @@ int main() {
     const RayKey small = key_of(2, 3, 4);
     c.launch(small, 6, 4);
     l = c.launch(small, 6, 4);
-    EXPECT(l.action == RayAction::kFill && l.recs == r0 && c.recs.bytes == 28 * 32);
+    EXPECT(l.action == RayAction::kFill && l.recs == r0 && c.caches.tile_recs.bytes == 28 * 32);
     EXPECT(heap.allocs == 2 && heap.frees == 0);
     // a larger grid: both are replaced, old ones freed first
     const RayKey large = key_of(13, 30, 4);
     c.launch(large, 390, 4);
     l = c.launch(large, 390, 4);
     EXPECT(l.action == RayAction::kFill && l.dirs && l.recs);
-    EXPECT(c.dirs.bytes == sfrt::ray_cache_bytes(390, 4) && c.recs.bytes == 390 * 32);
+    EXPECT(c.caches.dirs.bytes == sfrt::ray_cache_bytes(390, 4) && c.caches.tile_recs.bytes == 390 * 32);
     EXPECT(heap.allocs == 4 && heap.frees == 2);
     // more tiles at fewer pixels per lane: fewer direction bytes, more record bytes -- only the
     // records grow
     const RayKey narrow = key_of(50, 30, 1);
-    EXPECT(sfrt::ray_cache_bytes(1500, 1) < c.dirs.bytes && sfrt::tile_rec_bytes(1500) > c.recs.bytes);
-    const void* d1 = c.dirs.ptr;
+    EXPECT(sfrt::ray_cache_bytes(1500, 1) < c.caches.dirs.bytes && sfrt::tile_rec_bytes(1500) > c.caches.tile_recs.bytes);
+    const void* d1 = c.caches.dirs.ptr;
     c.launch(narrow, 1500, 1);
     l = c.launch(narrow, 1500, 1);
-    EXPECT(l.action == RayAction::kFill && l.dirs == d1 && c.recs.bytes == 1500 * 32);
+    EXPECT(l.action == RayAction::kFill && l.dirs == d1 && c.caches.tile_recs.bytes == 1500 * 32);
     EXPECT(heap.allocs == 5 && heap.frees == 3);
     // a failed launch invalidates both: nothing is read until the second equal launch refills
     l = c.launch(narrow, 1500, 1, 512 * kMiB, false);
     EXPECT(l.action == RayAction::kRead);
-    EXPECT(!c.policy.valid);
+    EXPECT(!c.caches.ray.valid);
     l = c.launch(narrow, 1500, 1);
     EXPECT(l.action == RayAction::kTrace && !l.recs);
     l = c.launch(narrow, 1500, 1);
-    EXPECT(l.action == RayAction::kFill && l.recs == c.recs.ptr);
+    EXPECT(l.action == RayAction::kFill && l.recs == c.caches.tile_recs.ptr);
     EXPECT(heap.allocs == 5 && heap.frees == 3);  // into the buffers it still holds
     // the option at 0: no read, no fill; the records do not count against a budget that the
     // directions exactly fill
     EXPECT(c.launch(narrow, 1500, 1, 0).action == RayAction::kTrace);
     c.release();
-    EXPECT(c.dirs.bytes == 0 && c.recs.bytes == 0 && !c.dirs.ptr && !c.recs.ptr);
+    EXPECT(c.caches.dirs.bytes == 0 && c.caches.tile_recs.bytes == 0 && !c.caches.dirs.ptr && !c.caches.tile_recs.ptr);
     EXPECT(heap.allocs == 5 && heap.frees == 5);
     c.launch(k, 28, 4, sfrt::ray_cache_bytes(28, 4));
     EXPECT(c.launch(k, 28, 4, sfrt::ray_cache_bytes(28, 4)).action == RayAction::kFill);
@@ -208,35 +149,35 @@ int main() {
   EXPECT(heap.allocs == 7 && heap.frees == 7);
   {  // no memory for the records: the launch renders uncached and reads neither buffer
     Heap h;
-    Chain c(&h);
+    WalkingChain c(&h);
     const RayKey k = key_of(4, 7, 4);
     c.launch(k, 28, 4);
     h.fail_alloc = true;
-    Chain::Launch l = c.launch(k, 28, 4);
-    EXPECT(l.action == RayAction::kTrace && !l.dirs && !l.recs && !c.policy.valid);
-    EXPECT(c.dirs.bytes == 0 && c.recs.bytes == 0);
+    WalkingChain::Launch l = c.launch(k, 28, 4);
+    EXPECT(l.action == RayAction::kTrace && !l.dirs && !l.recs && !c.caches.ray.valid);
+    EXPECT(c.caches.dirs.bytes == 0 && c.caches.tile_recs.bytes == 0);
     h.fail_alloc = false;
     // the launch itself was queued and committed its key: the next equal one tries again
     l = c.launch(k, 28, 4);
-    EXPECT(l.action == RayAction::kFill && l.dirs && l.recs && c.recs.bytes == 28 * 32);
+    EXPECT(l.action == RayAction::kFill && l.dirs && l.recs && c.caches.tile_recs.bytes == 28 * 32);
     // a free that fails keeps the old buffer and its size, and fills nothing
     const RayKey large = key_of(13, 30, 4);
     c.launch(large, 390, 4);
     h.fail_free = true;
     l = c.launch(large, 390, 4);
-    EXPECT(l.action == RayAction::kTrace && c.dirs.bytes == sfrt::ray_cache_bytes(28, 4) && c.dirs.ptr);
+    EXPECT(l.action == RayAction::kTrace && c.caches.dirs.bytes == sfrt::ray_cache_bytes(28, 4) && c.caches.dirs.ptr);
     h.fail_free = false;
   }
   {  // two chains: each its own records
     Heap h;
-    Chain a(&h), b(&h);
+    WalkingChain a(&h), b(&h);
     const RayKey k = key_of(4, 7, 4);
     for (int t = 0; t < 3; t++) {
       a.launch(k, 28, 4);
       b.launch(k, 28, 4);
     }
-    EXPECT(a.recs.ptr && b.recs.ptr && a.recs.ptr != b.recs.ptr && a.dirs.ptr != b.dirs.ptr);
-    EXPECT(a.recs.bytes + b.recs.bytes == 2 * 28 * 32);
+    EXPECT(a.caches.tile_recs.ptr && b.caches.tile_recs.ptr && a.caches.tile_recs.ptr != b.caches.tile_recs.ptr && a.caches.dirs.ptr != b.caches.dirs.ptr);
+    EXPECT(a.caches.tile_recs.bytes + b.caches.tile_recs.bytes == 2 * 28 * 32);
   }
   if (failures) return 1;
   std::printf("tilerec_check ok\n");

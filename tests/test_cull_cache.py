@@ -1,4 +1,4 @@
-"""The cull cache (csrc/sfrt_raycache.h CullCachePolicy; DESIGN.md 5 "Cull cache"): beside the ray
+"""The cull cache (csrc/sfrt_raycache.h CullKey, ChainCaches; DESIGN.md 5 "Cull cache"): beside the ray
 directions and the tile records, a chain caches what each tile's wave culls -- the mask of the
 spheres that may pass and every sphere's march window -- while the view, the camera position,
 the sphere count and every sphere's centre and radius stay.
@@ -55,7 +55,9 @@ def cluster_spheres():
 
 SCENES = {"n10": lambda: random_spheres(10), "n64": lambda: random_spheres(64),
           "n65": lambda: random_spheres(65), "n200": lambda: random_spheres(200),
-          "cluster": cluster_spheres}
+          "cluster": cluster_spheres,
+          # two of the named scenes (scenes.py), as they come: tests/test_hit_cache.py
+          "default10": lambda: scenes.default10().spheres, "lcg256": lambda: scenes.lcg256().spheres}
 
 
 @functools.lru_cache(maxsize=None)

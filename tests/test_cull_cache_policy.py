@@ -1,4 +1,4 @@
-"""The cull cache's policy (csrc/sfrt_raycache.h CullKey, CullCachePolicy: when a chain fills,
+"""The cull cache's policy (csrc/sfrt_raycache.h CullKey, ChainCaches: when a chain fills,
 reads or leaves its cache of per-tile culling masks and march windows) as a stand-alone host
 program, tests/native/cullcache_check.cpp, built with the host sanitizers: fill on the second
 identical key and read on the third, a miss and a later refill on every input of the cull, a

@@ -1,4 +1,4 @@
-"""The hit cache (csrc/sfrt_raycache.h HitCachePolicy; DESIGN.md 5 "Hit cache"): on top of the cull
+"""The hit cache (csrc/sfrt_raycache.h HitRec, ChainCaches; DESIGN.md 5 "Hit cache"): on top of the cull
 cache and under its key, a chain stores where each ray's march ended and on which sphere, and
 while the key stays its launches do not march: they shade from the stored results with the
 textures and texture slots of the moment.
@@ -123,12 +123,45 @@ class HitRig(Rig):
         return fills + 1, hits + count - 2
 
 
-@pytest.mark.parametrize("geom", ["72x20-r4", "40x9-r1", "40x9-r2", "40x9-r3"])
-@pytest.mark.parametrize("scene", ["n10", "n64", "n65", "n200", "cluster"])
+FIVE_FRAMES = [(scene, geom) for geom in ("72x20-r4", "40x9-r1", "40x9-r2", "40x9-r3")
+               for scene in ("n10", "n64", "n65", "n200", "cluster")]
+# ... and two named scenes with an aux band (sfrt_world_render_band_aux) after the third frame: a
+# launch that takes no part in the caches, between two reading launches
+AUX_BETWEEN = [("default10", "72x20-r4"), ("lcg256", "72x20-r4")]
+
+
+def _aux_band(r):
+    """One render_band_aux call of r's state on r's stream: its colour bytes, nothing else kept."""
+    import torch
+    pitch = 4 * r.width + 16
+    buf = poisoned((r.rows, pitch), POISON)
+    depth = torch.empty((r.rows, r.width), dtype=torch.float32, device="cuda")
+    r.w.render_band_aux(buf.data_ptr(), pitch, r.row0, r.rows, r.stream.cuda_stream,
+                        depth=(depth.data_ptr(), 4 * r.width))
+    r.w.check(r.stream.cuda_stream)
+    return r.bytes_of(buf)
+
+
+@pytest.mark.parametrize("scene,geom", FIVE_FRAMES + AUX_BETWEEN,
+                         ids=[f"{scene}-{geom}" for scene, geom in FIVE_FRAMES + AUX_BETWEEN])
 def test_five_identical_frames(built, scene, geom):
     with HitRig(scene, geom) as r:
         assert r.w.get_option(r.sfrt.SFRT_OPT_HIT_CACHE_MB) == 512
         assert r.hstats() == (0, 0, 0)
+        if (scene, geom) in AUX_BETWEEN:
+            first = r.check_frame("frame 1")
+            for k, want in ((2, (1, 0, r.hit_bytes())), (3, (1, 1, r.hit_bytes()))):
+                r.check_frame(f"frame {k}")
+                assert r.hstats() == want, k
+            before = r.hstats(), r.stats(), r.w.ray_cache_stats()
+            assert before[:2] == ((1, 1, r.hit_bytes()), (1, 1)) and before[2]["cached_frames"] == 2
+            aux = _aux_band(r)
+            assert (r.hstats(), r.stats(), r.w.ray_cache_stats()) == before  # no trace of it
+            last = r.check_frame("the frame after the aux band")
+            assert r.hstats() == (1, 2, r.hit_bytes())
+            assert r.stats() == (1, 2) and r.w.ray_cache_stats()["cached_frames"] == 3
+            assert np.array_equal(aux, first) and np.array_equal(last, first)
+            return
         r.frames("five frames", count=5)
         assert r.hstats() == (1, 3, r.hit_bytes())
         # each reading launch counts as a cached frame and a cull-cache hit, as without the hit cache

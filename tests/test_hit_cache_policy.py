@@ -1,4 +1,4 @@
-"""The hit cache's policy and record (csrc/sfrt_raycache.h HitRec, HitCachePolicy: when a chain
+"""The hit cache's policy and record (csrc/sfrt_raycache.h HitRec, ChainCaches: when a chain
 stores, reads or leaves its cache of per-ray march results) as a stand-alone host program,
 tests/native/hitcache_check.cpp, built with the host sanitizers: first frames, a miss and a later
 refill on every field of the key, what the key does not hold, refusals by the budget of its own and

@@ -3,7 +3,7 @@ host program, tests/native/tilerec_check.cpp, built with the host sanitizers: th
 alignment and field offsets as the fill kernel and the trace kernels share them through that
 header, and a chain's bookkeeping of its two buffers -- allocated with the fill, kept while the
 key is read and across a position change, refilled in place after a basis change, regrown for a
-larger grid, never read after a failed launch -- driven by RayCachePolicy's decisions.
+larger grid, never read after a failed launch -- driven through ChainCaches::begin and end.
 No GPU, no HIP."""
 import os
 import subprocess

@@ -7,8 +7,9 @@
 
 `run` makes each host entry point's first call and one growing call (frames 320x240 -> 640x360 for
 the sphere world, 160x90 -> 320x180 for the voxel and GLSL renderers, ray batches of 64 -> 4,096
-rays: each more than 1.5 times larger, past the pinned buffers' geometric capacity) and writes the
-entry points' labels in call order.  Before each it calls sfrt_world_create(-1) twice -- two
+rays: each more than 1.5 times larger, past the pinned buffers' geometric capacity), then the
+sphere world's render_band sequence through every state of a chain's caches (sfrt_raycache.h), and
+writes the entry points' labels in call order.  Before each it calls sfrt_world_create(-1) twice -- two
 hipGetDeviceCount calls in a row, which no entry point makes -- so `compare` can cut the trace
 into entry points.  `compare` prints both builds' call names per entry point and exits 1 if any
 entry point's list differs.
@@ -30,7 +31,14 @@ def run(labels_path):
     import scenes
     import sfrt
     import voxel_scenes as vs
+    import torch
     labels, frames = [], []
+    # (before the first marker: the band sequence's device buffers, so that no allocator call of
+    # torch's falls between two entry points)
+    band_w, band_h = 72, 20
+    band = torch.empty((band_h, band_w * 4), dtype=torch.uint8, device="cuda")
+    band_depth = torch.empty((band_h, band_w), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
 
     def entry(label, fn):
         out = ctypes.c_void_p()
@@ -60,6 +68,29 @@ def run(labels_path):
     for tag, n in (("first", 64), ("grown", 4096)):
         entry(f"world_cast_rays origins {tag}", lambda: world.cast_rays(dirs[:n], org[:n]))
         entry(f"world_cast_rays camera {tag}", lambda: world.cast_rays(dirs[:n]))
+    # One pose at 72x20 (a clamped last tile column and row) on the null stream: an uncached, a
+    # filling and three reading launches; an aux band, which takes no part; a moved camera twice
+    # (a miss, then a refill over the directions); the first pose again; each budget lowered to 0.
+    world.set_scene(sc, band_w, band_h)
+    pos = tuple(sc.cam_pos)
+
+    def draw():
+        world.render_band(band.data_ptr(), band_w * 4, 0, band_h)
+
+    for k, what in enumerate(("trace", "fill", "read", "read", "read")):
+        entry(f"world_render_band {k + 1} {what}", draw)
+    entry("world_render_band_aux between reads", lambda: world.render_band_aux(
+        band.data_ptr(), band_w * 4, 0, band_h, depth=(band_depth.data_ptr(), band_w * 4)))
+    world.set_camera((pos[0] + 0.25, pos[1], pos[2]), sc.rotation, sc.hrotation)
+    entry("world_render_band moved 1", draw)
+    entry("world_render_band moved 2", draw)
+    world.set_camera(pos, sc.rotation, sc.hrotation)
+    entry("world_render_band moved back", draw)
+    entry("world_set_option hit cache 0", lambda: world.set_option(sfrt.SFRT_OPT_HIT_CACHE_MB, 0))
+    entry("world_render_band hit cache 0", draw)
+    entry("world_set_option ray cache 0", lambda: world.set_option(sfrt.SFRT_OPT_RAY_CACHE_MB, 0))
+    entry("world_render_band ray cache 0", draw)
+    entry("world_check after bands", world.check)
     entry("host_free", lambda: [f.free() for f in frames])
     entry("world_destroy", world.close)
 
@@ -109,6 +140,8 @@ def entries(trace_csv, labels_path):
         else:
             k += 1
     labels = open(labels_path).read().split("\n")[:-1]
+    # (torch's own initialisation, before the first entry point, counts the devices twice in a row)
+    cuts = cuts[max(0, len(cuts) - len(labels)):]
     if len(cuts) != len(labels):
         raise SystemExit(f"{trace_csv}: {len(cuts)} markers for {len(labels)} labels")
     out = []
