@@ -230,7 +230,7 @@ SFRT_API int sfrt_world_render_subset_aux(sfrt_world* w, void* dev_frame, int64_
 #define SFRT_MAX_VIEWS 1024
 #define SFRT_VIEWS_SORT 1          /* flags bit 0: UpdateSpheres' sort per view */
 typedef struct {
-  sfrt_camera cam;                 /* this view's SphereWorld::cam */
+  sfrt_camera cam;                 /* this view's SphereWorld::cam (voxel: World::cam) */
   void* dev_pixels;                /* its width x height RGBA8 target, rows pitch_bytes apart */
 } sfrt_view;
 SFRT_API int sfrt_world_render_views(sfrt_world* w, const sfrt_view* views, int count,
@@ -688,6 +688,66 @@ SFRT_API int sfrt_voxel_render_subset(sfrt_voxel* v, void* dev_frame, int64_t pi
 SFRT_API int sfrt_voxel_render_subset_aux(sfrt_voxel* v, void* dev_frame, int64_t pitch_bytes,
                                           const sfrt_voxel_aux_planes* aux, int ystart, int yadd,
                                           int xstart, int xadd, void* hip_stream);
+
+/* ---- a batch of camera views of the voxel world in one launch ----
+ * sfrt_world_render_views for the voxel world: each view a whole width x height frame from a
+ * camera of its own into a device target of its own (sfrt_view, SFRT_MAX_VIEWS: the sphere
+ * batch's), all views in one kernel launch.
+ * Definition: with the world as it stands at the call, view k receives exactly the bytes that
+ *   sfrt_voxel_set_camera(v, &views[k].cam);
+ *   sfrt_voxel_set_dynamics(v, L, n);             -- with SFRT_VOXEL_VIEWS_DYNAMICS only: L = a copy
+ *                                                    of the world's list after
+ *                                                    sfrt_voxel_sort_dynamics(L, n, views[k].cam.pos)
+ *   sfrt_voxel_render_band(v, views[k].dev_pixels, pitch_bytes, 0, height, s);
+ * would write on a copy of that world (the aux call: sfrt_voxel_render_band_aux with planes[k]),
+ * and the call writes no other byte.
+ * What a camera owns in this renderer is more than its seven floats: the reference keeps
+ * distToCamera and the ORDER of `dyn` per camera (World.cpp:226-231), and Raycast walks the list in
+ * that order and stops at the first entry farther than the next block, so a list ordered for one
+ * camera draws wrong billboards, or none, from another.  Without the flag every view uses the
+ * world's list as it is (its order and its dist_to_camera values; only the angle term of :361 is
+ * the view's own) -- right for views that share a position (cube-map faces).  With it each view
+ * gets the list sorted for its own camera, always from the world's current list and never from
+ * view k-1's, and a billboard's `cell` value in such a view indexes that view's sorted list
+ * (recompute it with sfrt_voxel_sort_dynamics).
+ * The lights are the world's list for every view: choosing `alights` per camera (World.cpp:233-240)
+ * stays with the caller, as it is for a band.  view_distance and shadow_distance are the world's.
+ * Whole frames only.
+ * The world itself is left as it was: its camera, its dynamics list and that list's order, and
+ * the tables a band has staged -- a sfrt_voxel_render_band after the batch with no setter in
+ * between writes the bytes it wrote before.  A pending sfrt_voxel_set_blocks rewrite is carried out
+ * by the call on its stream, as a band carries it out.
+ * Asynchronous on `hip_stream` with sfrt_voxel_render_band's stream semantics; the texel bit of
+ * every view goes into the world's status word (sfrt_voxel_check).  SFRT_OPT_SUPERSAMPLE is
+ * honoured (planes: the first sample's, as above); the launch is row-major within a view and
+ * view-major across views, so SFRT_OPT_TILE_ORDER has no influence and no chain is touched.
+ * count == 0 returns SFRT_OK with nothing queued.  SFRT_E_INVALID, with nothing queued or written:
+ * a NULL world or `views`, count < 0 or > SFRT_MAX_VIEWS, unknown flag bits, pitch_bytes not a
+ * multiple of 4 or below 4*width, a NULL or not 4-byte-aligned dev_pixels or a camera
+ * sfrt_voxel_set_camera would refuse in any view, (aux) NULL `planes`, an entry with all four
+ * planes NULL or with a pitch sfrt_voxel_render_band_aux would refuse, a sample grid a band would
+ * refuse, or a grid the device cannot be given in one launch (more than 2^31 - 1 tiles over all
+ * views, or more than 2^26 - 1 tiles in one).  SFRT_E_EMPTY as for a band.  Targets (and planes)
+ * that overlap are the caller's responsibility. */
+#define SFRT_VOXEL_VIEWS_DYNAMICS 1   /* flags bit 0: distToCamera and the list order per view */
+SFRT_API int sfrt_voxel_render_views(sfrt_voxel* v, const sfrt_view* views, int count,
+                                     int64_t pitch_bytes, int flags, void* hip_stream);
+SFRT_API int sfrt_voxel_render_views_aux(sfrt_voxel* v, const sfrt_view* views,
+                                         const sfrt_voxel_aux_planes* planes /* count entries */,
+                                         int count, int64_t pitch_bytes, int flags, void* hip_stream);
+/* The per-camera part of World::UpdateDynamics for a list, in place (a pure host function, like
+ * sfrt_sort_spheres): every dist_to_camera becomes the binary32 value of World.cpp:226-227,
+ * sqrtf(to.x*to.x + to.z*to.z) with to = pos - cam_pos (products and sum rounded one by one), and
+ * the list is then ordered by insertion from the front: element i goes before the first already
+ * placed element whose distance is greater, by the `<` of World.cpp:229 (a NaN distance is never
+ * greater and never smaller: such an element stays behind everything placed before it).  That is
+ * a stable ascending sort.  It is NOT the reference's one pass: World.cpp:229-231 swaps each
+ * element at most once with its predecessor per frame, one bubble pass, and reaches this order
+ * only after enough frames with the camera at rest -- this order is that iteration's fixed point,
+ * the list a camera that has stood still sees.  A caller that wants the reference's transient
+ * order does its passes itself and renders without the flag.
+ * SFRT_E_INVALID for count < 0 or a NULL pointer with count > 0. */
+SFRT_API int sfrt_voxel_sort_dynamics(sfrt_dynamic* dyn, int count, const float cam_pos[3]);
 
 /* ---- batched ray queries: World::Raycast (World.cpp:302-453) for caller-supplied rays ----
  * sfrt_voxel_cast_rays[_device] runs Raycast for ray q of a batch.  Line numbers are World.cpp's.

@@ -498,6 +498,30 @@ class VoxelWorld {
                                        hip_stream),
           "render_subset_aux");
   }
+  // A batch of whole frames of this world, one camera and one device target per view, in one
+  // launch (sfrt.h sfrt_voxel_render_views): view k is the frame that `cam = views[k].cam;
+  // [SetDynamics(SortDynamics(list, cam.pos));] RenderBand(...)` would write, and this object's own
+  // cam and dynamics are left as they are.  dynamics: each view gets the list's distToCamera and
+  // order for its own camera (World.cpp:226-231 at rest); without it every view walks the list as
+  // it was set.  The Aux call writes planes[k] beside view k (one entry per view).
+  void RenderViews(const std::vector<sfrt_view>& views, int64_t pitch_bytes, bool dynamics,
+                   void* hip_stream) {
+    if (views.empty()) return;  // nothing to queue (an empty vector's data() may be null)
+    push_state();
+    check(sfrt_voxel_render_views(v_, views.data(), (int)views.size(), pitch_bytes,
+                                  dynamics ? SFRT_VOXEL_VIEWS_DYNAMICS : 0, hip_stream),
+          "render_views");
+  }
+  void RenderViewsAux(const std::vector<sfrt_view>& views,
+                      const std::vector<sfrt_voxel_aux_planes>& planes, int64_t pitch_bytes,
+                      bool dynamics, void* hip_stream) {
+    if (planes.size() != views.size()) throw Error(SFRT_E_INVALID, "render_views_aux");
+    if (views.empty()) return;
+    push_state();
+    check(sfrt_voxel_render_views_aux(v_, views.data(), planes.data(), (int)views.size(), pitch_bytes,
+                                      dynamics ? SFRT_VOXEL_VIEWS_DYNAMICS : 0, hip_stream),
+          "render_views_aux");
+  }
   int fullCycles = 4;
   int cycle = 0;
   void RenderCycles(void* dev_frame, int64_t pitch_bytes, int cycles, void* hip_stream) {
@@ -584,6 +608,13 @@ class VoxelWorld {
   }
   sfrt_voxel* v_ = nullptr;
 };
+
+// distToCamera and the order of a `dyn` list for a camera at rest (sfrt.h
+// sfrt_voxel_sort_dynamics: stable, ascending; not the reference's one bubble pass), in place.
+inline void SortDynamics(std::vector<sfrt_dynamic>& dyn, const Vector3f& cam_pos) {
+  const float c[3] = {cam_pos.x, cam_pos.y, cam_pos.z};
+  check(sfrt_voxel_sort_dynamics(dyn.data(), (int)dyn.size(), c), "sort_dynamics");
+}
 
 // ---------------------------------------------------------------------------
 // Shader: sf::Shader with rayShader.frag loaded (SphereWorld.cpp:47), its

@@ -95,6 +95,93 @@ struct DevTex {
   size_t cap = 0;
 };
 
+// The per-camera tables of a frame (World.cpp:64-87 at the sample size W x H), each into the
+// caller's block: the band path (sfrt_voxel::prepare) builds them for the world's camera, a view
+// batch (render_views_body) once per view.  col_table and row_table return the largest finite
+// |component| they wrote (dda_qlim's xmax is the larger of the two).
+float col_table(const sfrt_camera& cam, int W, float* col) {
+  const float hStart = cam.rotation - cam.fov_h / 2;
+  const float hIncreaseBy = cam.fov_h / W;
+  float xmax = 0.0f;
+  for (int i = 0; i < W; i++) {
+    const float hray = (hStart + hIncreaseBy * i);
+    const float fix = std::cos(cam.rotation - hray);
+    const float dx = std::sin(hray) / fix, dz = std::cos(hray) / fix;
+    col[3 * (size_t)i] = dx;
+    col[3 * (size_t)i + 1] = dz;
+    col[3 * (size_t)i + 2] = sfrt_math::atan2f(dz, dx);  // VAngleXZ's ray term (World.cpp:272)
+    for (float c : {dx, dz})
+      if (std::isfinite(c)) xmax = std::max(xmax, std::fabs(c));
+  }
+  return xmax;
+}
+float row_table(const sfrt_camera& cam, int H, float* row) {
+  const float vStart = cam.fov_v / 2;
+  const float vIncreaseBy = cam.fov_v / H;
+  const float vOff = std::sin(cam.hrotation);
+  float xmax = 0.0f;
+  for (int j = 0; j < H; j++) {
+    const float vray = (vStart - j * vIncreaseBy);
+    row[2 * (size_t)j] = (vOff + std::sin(vray));
+    row[2 * (size_t)j + 1] = std::cos(cam.hrotation + vray);   // r->yscale
+    if (std::isfinite(row[2 * (size_t)j])) xmax = std::max(xmax, std::fabs(row[2 * (size_t)j]));
+  }
+  return xmax;
+}
+// The billboards as the kernel reads them, in the order given, atan_b for this camera.
+void dyn_table(const sfrt_camera& cam, const sfrt_dynamic* dyn, size_t n, sfrt::VoxDyn* vd) {
+  for (size_t k = 0; k < n; k++) {
+    const sfrt_dynamic& d = dyn[k];
+    sfrt::VoxDyn& o = vd[k];
+    o.px = d.pos[0]; o.py = d.pos[1]; o.pz = d.pos[2];
+    o.sx = d.size[0]; o.sy = d.size[1];
+    o.r = d.r; o.g = d.g; o.b = d.b;
+    o.dist = d.dist_to_camera;
+    // VNormalizeXZ(d->pos - cam.pos) (World.cpp:282-285, 361)
+    const float ex = d.pos[0] - cam.pos[0], ez = d.pos[2] - cam.pos[2];
+    const float l = std::sqrt(ex * ex + ez * ez);
+    o.atan_b = sfrt_math::atan2f(ez / l, ex / l);
+    o.tex = d.texture_id;
+    o.pad = 0;
+  }
+}
+void light_table(const sfrt_light* lights, size_t n, sfrt::VoxLight* vl) {
+  for (size_t k = 0; k < n; k++) {
+    const sfrt_light& L = lights[k];
+    sfrt::VoxLight& o = vl[k];
+    o.px = L.pos[0]; o.py = L.pos[1]; o.pz = L.pos[2];
+    o.dd_skip = light_dd_skip(light_dd_pass(L.intensity));
+    o.intensity = L.intensity; o.r = L.r; o.g = L.g; o.b = L.b;
+    o.shadows = L.shadows;
+  }
+}
+size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// sfrt_voxel_sort_dynamics: distToCamera of World.cpp:226-227 for every element, then the list
+// ordered by insertion from the front with World.cpp:229's `<` -- element i goes before the first
+// already placed element whose distance is greater (a NaN distance is greater than nothing and
+// nothing is greater than it).  Stable and ascending.
+void sort_dynamics(sfrt_dynamic* dyn, size_t n, const float cam_pos[3]) {
+  for (size_t i = 0; i < n; i++) {
+    const float tx = dyn[i].pos[0] - cam_pos[0], tz = dyn[i].pos[2] - cam_pos[2];
+    dyn[i].dist_to_camera = std::sqrt(tx * tx + tz * tz);
+  }
+  for (size_t i = 1; i < n; i++) {
+    const sfrt_dynamic e = dyn[i];
+    size_t j = 0;
+    while (j < i && !(e.dist_to_camera < dyn[j].dist_to_camera)) j++;
+    if (j == i) continue;
+    std::memmove(dyn + j + 1, dyn + j, (i - j) * sizeof(sfrt_dynamic));
+    dyn[j] = e;
+  }
+}
+
+bool camera_ok(const sfrt_camera& cam) {  // sfrt_voxel_set_camera's test
+  for (float c : {cam.pos[0], cam.pos[1], cam.pos[2], cam.rotation, cam.hrotation, cam.fov_h, cam.fov_v})
+    if (!std::isfinite(c)) return false;
+  return true;
+}
+
 
 }  // namespace
 
@@ -136,10 +223,16 @@ struct sfrt_voxel {
   // with pinned staging and the event of the last launch that read it, so
   // launches on different streams never see a table overwritten under them.
   // (sfrt::TableSlot, sfrt_host.h: a reuse on another stream waits for the slot's last user.)
-  static constexpr int kSlots = 4;
-  sfrt::TableSlot slots[kSlots];
+  // The view batches (sfrt_voxel_render_views) stage their block -- view records and every view's
+  // tables -- in a ring of their own, the slots past kSlots of the same array: a batch never takes
+  // the band's staged tables away (cur_slot, staged_version stay valid), and every loop over
+  // `slots` -- SharedBuffer::before_write's among them, so that a grid or texture rewrite waits
+  // for the batches that still read the old data -- covers both rings.
+  static constexpr int kSlots = 4, kViewSlots = 4;
+  sfrt::TableSlot slots[kSlots + kViewSlots];
   int next_slot = 0;
   int cur_slot = -1;
+  int next_view_slot = 0;
   // The tables depend only on the size, the camera, the billboards and the lights: every
   // setter of those bumps tables_version, and a launch whose tables are unchanged since the
   // last staging reuses that slot (no host recomputation, no copy).
@@ -199,23 +292,23 @@ struct sfrt_voxel {
   // Builds the frame record and uploads the per-frame arrays on stream s.
   // Everything the reference recomputes per pixel but that depends only on the
   // column, the row or the object is evaluated here, with its expressions.
+  // The part of a frame record that does not depend on the camera (the device pointers come with
+  // fill_world, once the grid is up to date).
+  void begin_frame(sfrt::VoxFrame& f) const {
+    std::memset(&f, 0, sizeof f);
+    f.ss = ss;
+    f.view_distance = view_distance;
+    f.shadow_distance = shadow_distance;
+    f.maxiter = to_u32(view_distance * 1.5f);                       // World.cpp:322
+  }
+
   int prepare(sfrt::VoxFrame& f, hipStream_t s) {
     if (blocks.empty()) return SFRT_E_EMPTY;
     if (width <= 0 || height <= 0) return SFRT_E_INVALID;
     // World.cpp:64-87 is evaluated at the sample size (ints: the frame calls checked sample_grid_ok)
     const int W = width << ss, H = height << ss;
-    std::memset(&f, 0, sizeof f);
-    f.ss = ss;
+    begin_frame(f);
     f.cam[0] = cam.pos[0]; f.cam[1] = cam.pos[1]; f.cam[2] = cam.pos[2];
-    f.view_distance = view_distance;
-    f.shadow_distance = shadow_distance;
-    f.maxiter = to_u32(view_distance * 1.5f);                       // World.cpp:322
-    // World.cpp:64-87
-    const float vStart = cam.fov_v / 2;
-    const float vIncreaseBy = cam.fov_v / H;
-    const float vOff = std::sin(cam.hrotation);
-    const float hStart = cam.rotation - cam.fov_h / 2;
-    const float hIncreaseBy = cam.fov_h / W;
     if (staged_version == tables_version && cur_slot >= 0) {
       sfrt::TableSlot& t = slots[cur_slot];  // still holds this scene's tables; launched() re-marks it
       const int rc = blocks_upload(s);  // first: fill_frame reads d_cells
@@ -225,63 +318,19 @@ struct sfrt_voxel {
       fill_frame(f, t.d.ptr<uint8_t>(), staged_off);
       return SFRT_OK;
     }
-    std::vector<float> col((size_t)W * 3), row((size_t)H * 2);
-    float xmax = 0.0f;
-    for (int i = 0; i < W; i++) {
-      const float hray = (hStart + hIncreaseBy * i);
-      const float fix = std::cos(cam.rotation - hray);
-      const float dx = std::sin(hray) / fix, dz = std::cos(hray) / fix;
-      col[3 * (size_t)i] = dx;
-      col[3 * (size_t)i + 1] = dz;
-      col[3 * (size_t)i + 2] = sfrt_math::atan2f(dz, dx);  // VAngleXZ's ray term (World.cpp:272)
-      for (float c : {dx, dz})
-        if (std::isfinite(c)) xmax = std::max(xmax, std::fabs(c));
-    }
-    for (int j = 0; j < H; j++) {
-      const float vray = (vStart - j * vIncreaseBy);
-      row[2 * (size_t)j] = (vOff + std::sin(vray));
-      row[2 * (size_t)j + 1] = std::cos(cam.hrotation + vray);   // r->yscale
-      if (std::isfinite(row[2 * (size_t)j])) xmax = std::max(xmax, std::fabs(row[2 * (size_t)j]));
-    }
-    std::vector<sfrt::VoxDyn> vd(dyn.size());
-    for (size_t k = 0; k < dyn.size(); k++) {
-      const sfrt_dynamic& d = dyn[k];
-      sfrt::VoxDyn& o = vd[k];
-      o.px = d.pos[0]; o.py = d.pos[1]; o.pz = d.pos[2];
-      o.sx = d.size[0]; o.sy = d.size[1];
-      o.r = d.r; o.g = d.g; o.b = d.b;
-      o.dist = d.dist_to_camera;
-      // VNormalizeXZ(d->pos - cam.pos) (World.cpp:282-285, 361)
-      const float ex = d.pos[0] - cam.pos[0], ez = d.pos[2] - cam.pos[2];
-      const float l = std::sqrt(ex * ex + ez * ez);
-      o.atan_b = sfrt_math::atan2f(ez / l, ex / l);
-      o.tex = d.texture_id;
-      o.pad = 0;
-    }
-    std::vector<sfrt::VoxLight> vl(lights.size());
-    for (size_t k = 0; k < lights.size(); k++) {
-      const sfrt_light& L = lights[k];
-      sfrt::VoxLight& o = vl[k];
-      o.px = L.pos[0]; o.py = L.pos[1]; o.pz = L.pos[2];
-      o.dd_skip = light_dd_skip(light_dd_pass(L.intensity));
-      o.intensity = L.intensity; o.r = L.r; o.g = L.g; o.b = L.b;
-      o.shadows = L.shadows;
-    }
-    // one blob per launch: col | row | dyn | lights, 16-byte aligned parts
-    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t b_col = up16(col.size() * sizeof(float)), b_row = up16(row.size() * sizeof(float)),
-                 b_dyn = up16(vd.size() * sizeof(sfrt::VoxDyn)),
-                 b_lit = up16(vl.size() * sizeof(sfrt::VoxLight));
+    // one blob per launch: col | row | dyn | lights, 16-byte aligned parts, built in place in the
+    // slot's pinned copy (the per-camera parts by the functions a view batch calls per view)
+    const size_t b_col = up16((size_t)W * 3 * sizeof(float)), b_row = up16((size_t)H * 2 * sizeof(float)),
+                 b_dyn = up16(dyn.size() * sizeof(sfrt::VoxDyn)),
+                 b_lit = up16(lights.size() * sizeof(sfrt::VoxLight));
     const size_t bytes = b_col + b_row + b_dyn + b_lit + 16;
     sfrt::TableSlot& t = slots[next_slot];
     HIP_TRY(t.reclaim());
     HIP_TRY(t.grow(bytes, s));  // no wait on other streams (sfrt_host.h)
     uint8_t* h = t.h.ptr<uint8_t>();
-    std::memcpy(h, col.data(), col.size() * sizeof(float));
-    std::memcpy(h + b_col, row.data(), row.size() * sizeof(float));
-    if (!vd.empty()) std::memcpy(h + b_col + b_row, vd.data(), vd.size() * sizeof(sfrt::VoxDyn));
-    if (!vl.empty())
-      std::memcpy(h + b_col + b_row + b_dyn, vl.data(), vl.size() * sizeof(sfrt::VoxLight));
+    const float xmax = std::max(col_table(cam, W, (float*)h), row_table(cam, H, (float*)(h + b_col)));
+    dyn_table(cam, dyn.data(), dyn.size(), (sfrt::VoxDyn*)(h + b_col + b_row));
+    light_table(lights.data(), lights.size(), (sfrt::VoxLight*)(h + b_col + b_row + b_dyn));
     HIP_TRY(hipMemcpyAsync(t.d.ptr(), h, bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(t.staged(s));
     cur_slot = next_slot;
@@ -376,17 +425,22 @@ struct sfrt_voxel {
   void fill_frame(sfrt::VoxFrame& f, uint8_t* d, const size_t* off) {
     f.col = (const float*)d;
     f.row = (const float*)(d + off[0]);
+    f.dda_qlim = dda_qlim(f.cam, f.maxiter, staged_xmax);
+    f.dyn = (const sfrt::VoxDyn*)(d + off[1]);
+    f.lights = (const sfrt::VoxLight*)(d + off[2]);
+    fill_world(f);
+  }
+  // What every view of a batch shares with a band: the grid, the textures and colours, the list
+  // sizes and the status word.
+  void fill_world(sfrt::VoxFrame& f) const {
     f.cells = d_cells.ptr<uint8_t>();
     f.cell_bytes = (uint32_t)nx << 20;
-    f.dda_qlim = dda_qlim(f.cam, f.maxiter, staged_xmax);
     for (int k = 0; k < sfrt::kVoxSlots; k++) {
       f.tex[k] = {tex[k].d, tex[k].w, tex[k].h};
       f.dyn_tex[k] = {dyn_tex[k].d, dyn_tex[k].w, dyn_tex[k].h};
       f.colors[k] = colors[k];
     }
-    f.dyn = (const sfrt::VoxDyn*)(d + off[1]);
     f.ndyn = (int)dyn.size();
-    f.lights = (const sfrt::VoxLight*)(d + off[2]);
     f.nlights = (int)lights.size();
     f.status = d_status;
   }
@@ -450,9 +504,7 @@ int sfrt_voxel_set_size(sfrt_voxel* v, int width, int height) {
 
 int sfrt_voxel_set_camera(sfrt_voxel* v, const sfrt_camera* cam) {
   if (!v || !cam) return SFRT_E_INVALID;
-  for (float c : {cam->pos[0], cam->pos[1], cam->pos[2], cam->rotation, cam->hrotation,
-                  cam->fov_h, cam->fov_v})
-    if (!std::isfinite(c)) return SFRT_E_INVALID;
+  if (!camera_ok(*cam)) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(v->mu);
   v->cam = *cam;
   v->tables_version++;
@@ -728,6 +780,151 @@ int sfrt_voxel_render_subset_aux(sfrt_voxel* v, void* dev_frame, int64_t pitch_b
                                  int xadd, void* hip_stream) {
   return render_subset_body(v, dev_frame, pitch_bytes, aux, true, ystart, yadd, xstart, xadd,
                             hip_stream);
+}
+
+// sfrt_voxel_render_views and sfrt_voxel_render_views_aux (with_aux false for the plain call): view
+// k is the whole frame that set_camera(views[k].cam) [+ set_dynamics(sort_dynamics(the world's
+// list, the view's camera)) with DYNAMICS] + render_band[_aux] would write, all views in one launch
+// of the view kernels (voxel_trace.h launch_voxel_views).  The per-camera state of a band -- the
+// col and row tables, the billboards with atan_b (in the view's own order and with its own
+// distToCamera under DYNAMICS), dda_qlim -- is built per view by the functions prepare() builds
+// the band's with, into one pinned block:
+//   count view records | col tables | row tables | count dyn tables | the lights, once
+// (16-byte aligned parts; views with the same rotation and fov_h share a col table, with the same
+// hrotation and fov_v a row table: the bytes are a function of those and the size alone), sent by
+// one copy on the caller's stream from a slot of the view ring.  Nothing of the world is written:
+// not the camera, the list or its order, nor the band's staged tables (cur_slot, staged_version) --
+// but a pending set_blocks rewrite is carried out, as by a band.
+static int render_views_body(sfrt_voxel* v, const sfrt_view* views,
+                             const sfrt_voxel_aux_planes* planes, bool with_aux, int count,
+                             int64_t pitch_bytes, int flags, void* hip_stream) {
+  if (!v || !views || count < 0 || count > SFRT_MAX_VIEWS ||
+      (flags & ~SFRT_VOXEL_VIEWS_DYNAMICS) != 0 || pitch_bytes % 4 != 0 || (with_aux && !planes))
+    return SFRT_E_INVALID;
+  for (int k = 0; k < count; k++) {
+    if (!views[k].dev_pixels || !sfrt::aligned4({views[k].dev_pixels}) || !camera_ok(views[k].cam))
+      return SFRT_E_INVALID;
+    if (with_aux && !planes[k].depth && !planes[k].cell && !planes[k].face && !planes[k].steps)
+      return SFRT_E_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(v->mu);
+  if (count == 0) return SFRT_OK;
+  if (v->width <= 0 || v->height <= 0 || pitch_bytes < (int64_t)v->width * 4) return SFRT_E_INVALID;
+  std::vector<sfrt::VoxAux> aux(with_aux ? (size_t)count : 0);
+  for (size_t k = 0; k < aux.size(); k++) {
+    const sfrt_voxel_aux_planes& p = planes[k];
+    sfrt::VoxAux& a = aux[k];
+    if (!sfrt::aux_plane(p.depth, p.depth_pitch_bytes, v->width, a.depth, a.depth_pitch) ||
+        !sfrt::aux_plane(p.cell, p.cell_pitch_bytes, v->width, a.cell, a.cell_pitch) ||
+        !sfrt::aux_plane(p.face, p.face_pitch_bytes, v->width, a.face, a.face_pitch) ||
+        !sfrt::aux_plane(p.steps, p.steps_pitch_bytes, v->width, a.steps, a.steps_pitch))
+      return SFRT_E_INVALID;
+  }
+  if (!v->sample_grid_ok(v->width, v->height)) return SFRT_E_INVALID;
+  // The frame geometry of render_band_body for rows [0, height), the same for every view, and the
+  // grid it gives, refused before anything is queued if one launch cannot take it.
+  const int ss = v->ss;
+  const int W = v->width << ss, H = v->height << ss;
+  sfrt::VoxFrame f;
+  v->begin_frame(f);
+  f.xstart = 0; f.xadd = 1 << ss; f.ystart = 0; f.yadd = 1 << ss;
+  f.sub_w = W;
+  f.sub_row0 = 0;
+  f.sub_rows = H;
+  f.out_pitch = pitch_bytes / 4;
+  if (!sfrt::voxel_views_grid_ok(f, count)) return SFRT_E_INVALID;
+  if (v->blocks.empty()) return SFRT_E_EMPTY;
+  sfrt::DeviceGuard g(v->device);
+  hipStream_t s = (hipStream_t)hip_stream;  // HIP convention: NULL = the null stream
+  const bool sorted = (flags & SFRT_VOXEL_VIEWS_DYNAMICS) != 0;
+  // which earlier view's col (row) table a view shares: the first with the same inputs, bit for bit
+  const auto same = [](float a, float b) { return std::memcmp(&a, &b, 4) == 0; };
+  std::vector<int> col_of((size_t)count), row_of((size_t)count);
+  int ncol = 0, nrow = 0;
+  for (int k = 0; k < count; k++) {
+    const sfrt_camera& c = views[k].cam;
+    col_of[k] = row_of[k] = -1;
+    for (int j = 0; j < k && (col_of[k] < 0 || row_of[k] < 0); j++) {
+      const sfrt_camera& o = views[j].cam;
+      if (col_of[k] < 0 && same(c.rotation, o.rotation) && same(c.fov_h, o.fov_h)) col_of[k] = col_of[j];
+      if (row_of[k] < 0 && same(c.hrotation, o.hrotation) && same(c.fov_v, o.fov_v)) row_of[k] = row_of[j];
+    }
+    if (col_of[k] < 0) col_of[k] = ncol++;
+    if (row_of[k] < 0) row_of[k] = nrow++;
+  }
+  const size_t nd = v->dyn.size(), nl = v->lights.size();
+  const size_t b_rec = up16((size_t)count * sizeof(sfrt::VoxViewRec));
+  const size_t b_col = up16((size_t)W * 3 * sizeof(float)), b_row = up16((size_t)H * 2 * sizeof(float)),
+               b_dyn = up16(nd * sizeof(sfrt::VoxDyn)), b_lit = up16(nl * sizeof(sfrt::VoxLight));
+  const size_t at_col = b_rec, at_row = at_col + (size_t)ncol * b_col,
+               at_dyn = at_row + (size_t)nrow * b_row, at_lit = at_dyn + (size_t)count * b_dyn;
+  const size_t bytes = at_lit + b_lit + 16;
+  sfrt::TableSlot& t = v->slots[sfrt_voxel::kSlots + v->next_view_slot];
+  v->next_view_slot = (v->next_view_slot + 1) % sfrt_voxel::kViewSlots;
+  HIP_TRY(t.reclaim());  // the launch that read the slot's last block is done (no device-wide wait)
+  HIP_TRY(t.grow(bytes, s));
+  uint8_t* const h = t.h.ptr<uint8_t>();
+  uint8_t* const d = t.d.ptr<uint8_t>();
+  std::vector<float> col_xmax((size_t)ncol, -1.0f), row_xmax((size_t)nrow, -1.0f);  // -1: not built
+  std::vector<sfrt_dynamic> list;
+  for (int k = 0; k < count; k++) {
+    const sfrt_camera& cam = views[k].cam;
+    const size_t c_at = at_col + (size_t)col_of[k] * b_col, r_at = at_row + (size_t)row_of[k] * b_row,
+                 d_at = at_dyn + (size_t)k * b_dyn;
+    if (col_xmax[col_of[k]] < 0.0f) col_xmax[col_of[k]] = col_table(cam, W, (float*)(h + c_at));
+    if (row_xmax[row_of[k]] < 0.0f) row_xmax[row_of[k]] = row_table(cam, H, (float*)(h + r_at));
+    const sfrt_dynamic* dyn = v->dyn.data();
+    if (sorted) {  // from the world's list every time, not from view k-1's
+      list = v->dyn;
+      sort_dynamics(list.data(), nd, cam.pos);
+      dyn = list.data();
+    }
+    dyn_table(cam, dyn, nd, (sfrt::VoxDyn*)(h + d_at));
+    sfrt::VoxViewRec r;
+    std::memset(&r, 0, sizeof r);
+    r.cam[0] = cam.pos[0]; r.cam[1] = cam.pos[1]; r.cam[2] = cam.pos[2];
+    r.dda_qlim = dda_qlim(r.cam, f.maxiter, std::max(col_xmax[col_of[k]], row_xmax[row_of[k]]));
+    r.col = (const float*)(d + c_at);
+    r.row = (const float*)(d + r_at);
+    r.dyn = (const sfrt::VoxDyn*)(d + d_at);
+    r.out = (uint32_t*)views[k].dev_pixels;
+    if (with_aux) r.aux = aux[(size_t)k];
+    std::memcpy(h + (size_t)k * sizeof r, &r, sizeof r);
+  }
+  light_table(v->lights.data(), nl, (sfrt::VoxLight*)(h + at_lit));
+  HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+  // the copy is queued: on any failure below the slot stays busy until it has run
+  int rc = v->blocks_upload(s);  // before fill_world: it reads d_cells
+  if (rc == SFRT_OK && v->shared.before_read(s) != hipSuccess) rc = SFRT_E_HIP;
+  if (rc == SFRT_OK) {
+    v->fill_world(f);
+    f.lights = (const sfrt::VoxLight*)(d + at_lit);
+    if (sfrt::launch_voxel_views(f, (const sfrt::VoxViewRec*)d, count, with_aux, s, t.launch_event()))
+      rc = SFRT_E_HIP;
+  }
+  if (rc != SFRT_OK) {
+    (void)t.staged(s);
+    return rc;
+  }
+  HIP_TRY(t.launched_with(s));
+  return SFRT_OK;
+}
+
+int sfrt_voxel_render_views(sfrt_voxel* v, const sfrt_view* views, int count, int64_t pitch_bytes,
+                            int flags, void* hip_stream) {
+  return render_views_body(v, views, nullptr, false, count, pitch_bytes, flags, hip_stream);
+}
+
+int sfrt_voxel_render_views_aux(sfrt_voxel* v, const sfrt_view* views,
+                                const sfrt_voxel_aux_planes* planes, int count, int64_t pitch_bytes,
+                                int flags, void* hip_stream) {
+  return render_views_body(v, views, planes, true, count, pitch_bytes, flags, hip_stream);
+}
+
+int sfrt_voxel_sort_dynamics(sfrt_dynamic* dyn, int count, const float cam_pos[3]) {
+  if (count < 0 || (count > 0 && (!dyn || !cam_pos))) return SFRT_E_INVALID;
+  sort_dynamics(dyn, (size_t)count, cam_pos);
+  return SFRT_OK;
 }
 
 // ---- batched ray queries (include/sfrt.h) ----

@@ -1589,7 +1589,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 13; }
+int sfrt_version(void) { return 14; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

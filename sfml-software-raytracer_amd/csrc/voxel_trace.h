@@ -118,6 +118,36 @@ long long voxel_tile_key(const VoxFrame& f, long long* tiles);
 int launch_voxel(const VoxFrame& f, void* stream, void* done_event = nullptr,
                  const VoxAux* aux = nullptr, int place_xstride = 0);
 
+// A batch of camera views in one launch (sfrt_voxel_render_views[_aux]): view k's
+// record at dev_views[k], the per-camera part of a VoxFrame -- what sfrt_voxel.cpp's col_table,
+// row_table, dyn_table and dda_qlim derive from the camera (and, with SFRT_VOXEL_VIEWS_DYNAMICS,
+// from the view's own list order) -- with
+// the view's target and, for the aux call, its planes (pitches in elements).  Read by the kernel
+// through the constant address space, a dword at a time: a multiple of 4 bytes, 8-byte aligned.
+struct VoxViewRec {
+  float cam[3];
+  float dda_qlim;
+  const float* col;
+  const float* row;
+  const VoxDyn* dyn;                        // the frame's ndyn records, this view's atan_b (and order)
+  uint32_t* out;                            // rows f.out_pitch apart
+  VoxAux aux;
+  // a view is row-major and in no tile-order chain: constants where a frame has pointers, so the
+  // kernel's sorter and order lookup fold away (voxel_trace.hip voxel_tile)
+  static constexpr const uint32_t* tile_order = nullptr;
+  static constexpr const uint8_t* prev_cost = nullptr;
+};
+static_assert(sizeof(VoxViewRec) == 112, "the host's table layout (sfrt_voxel.cpp)");
+// Whether `count` views of f's whole frame fit one launch: at most 2^26 - 1 tiles a view (x) and
+// 2^31 - 1 workgroups in all.
+bool voxel_views_grid_ok(const VoxFrame& f, int count);
+// One launch for `count` views of the frame f describes (sub_row0 0, no tile order): grid
+// (tiles, count), workgroup (x, y) tile x, row-major, of view y.  Of f it takes everything but
+// cam, dda_qlim, col, row, dyn and out, which each view's record supplies; aux: the records'
+// planes are written (every record has at least one).  done_event as launch_voxel's.
+int launch_voxel_views(const VoxFrame& f, const VoxViewRec* dev_views, int count, bool aux,
+                       void* stream, void* done_event = nullptr);
+
 // A batch of caller-supplied rays (sfrt_voxel_cast_rays[_device]): device pointers,
 // ray q's direction at dirs[3q..3q+2] (r->dir verbatim), its r->yscale at yscales[q] (null: 1.0f
 // for every ray), its origin at origins[3q..3q+2] (null: f.cam, with the billboards); every

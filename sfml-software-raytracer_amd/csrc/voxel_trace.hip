@@ -265,13 +265,20 @@ struct NoRay {};
 // 2^31 makes numerators that overflow the quotient, where div_recip gives NaN for the division's
 // inf).  The ray batches (RAY = BatchRay) add: OWN, the ray starts at its own origin and the
 // billboard list is not visited; SHADE = false, a block hit is not shaded (returns 0).
-template <bool RECIP, bool FAST, bool AUX, bool OWN = false, bool SHADE = true, class RAY = NoRay>
-__device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
+// VIEW: where the per-camera fields are read -- the camera and the billboard table here, dda_qlim
+// in raycast(), the col / row tables, the target and the tile-order pointers in voxel_tile.  The
+// frame itself everywhere but in the view batches (k_voxel_views), whose waves take them from
+// their view's record (VoxViewRec); every other field is f's.  (A modified copy of the frame
+// would not do: the texture and colour tables are indexed per lane, in the kernel's arguments
+// that is a load, in a copy it is 552 bytes of scratch.)
+template <bool RECIP, bool FAST, bool AUX, bool OWN = false, bool SHADE = true, class RAY = NoRay,
+          class VIEW = VoxFrame>
+__device__ uint32_t raycast_t(const VoxFrame& f, const VIEW& v, V3 dir, float yscale,
                               float atan_dir, uint32_t& work, VoxHit& hit, RAY& ray) {
   static_assert(RECIP == FAST, "the reciprocal divisions are proved under FAST's bound only");
   constexpr bool BATCH = !__is_same(RAY, NoRay);
   static_assert(BATCH || (!OWN && SHADE), "OWN and SHADE = false are the ray batches'");
-  const V3 cam{f.cam[0], f.cam[1], f.cam[2]};
+  const V3 cam{v.cam[0], v.cam[1], v.cam[2]};
   float dist = 0.0f;
   V3 pos = cam;
   if constexpr (OWN) pos = ray.org;
@@ -288,7 +295,7 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
   const float yx = RECIP ? 1.0f / lx : 0.0f, yy = RECIP ? 1.0f / ly : 0.0f,
               yz = RECIP ? 1.0f / lz : 0.0f;
   int DI = 0;
-  float dnext = f.ndyn > 0 ? f.dyn[0].dist : __builtin_nanf("");  // next billboard; NaN: never >=
+  float dnext = f.ndyn > 0 ? v.dyn[0].dist : __builtin_nanf("");  // next billboard; NaN: never >=
   if constexpr (OWN) dnext = __builtin_nanf("");  // no billboard: f.dyn is not read
   int colRay = 0;
   float last_x = 0.0f, last_y = 0.0f, last_z = 0.0f;  // the last step's rays (colRay, below)
@@ -361,7 +368,7 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
         V3 bp = pos;
         float bdist = dist;
         while (tryDist >= dnext) {
-          const VoxDyn& d = f.dyn[DI];
+          const VoxDyn& d = v.dyn[DI];
           const float bs = d.dist - bdist;
           bdist = d.dist;
           bp.x = bp.x + dir.x * bs;
@@ -393,7 +400,7 @@ __device__ uint32_t raycast_t(const VoxFrame& f, V3 dir, float yscale,
             }
           }
           DI++;
-          dnext = DI < f.ndyn ? f.dyn[DI].dist : __builtin_nanf("");
+          dnext = DI < f.ndyn ? v.dyn[DI].dist : __builtin_nanf("");
         }
       }
       dist = tryDist;
@@ -448,18 +455,18 @@ marched:
   return pack(0, 0, 0, 255);  // sf::Color::Black
 }
 
-template <bool AUX>
-__device__ uint32_t raycast(const VoxFrame& f, V3 dir, float yscale,
+template <bool AUX, class VIEW>
+__device__ uint32_t raycast(const VoxFrame& f, const VIEW& v, V3 dir, float yscale,
                             float atan_dir, uint32_t& work, VoxHit& hit) {
   // the reciprocal divisions and, within the host's bound on the direction's spread, the plain
   // position conversions (pos_i32)
   const float lx = fabsf(dir.x), ly = fabsf(dir.y), lz = fabsf(dir.z);
   const bool ok = recip_ok(lx) && recip_ok(ly) && recip_ok(lz) &&
-                  fmaxf(fmaxf(lx, ly), lz) <= f.dda_qlim * fminf(fminf(lx, ly), lz);
+                  fmaxf(fmaxf(lx, ly), lz) <= v.dda_qlim * fminf(fminf(lx, ly), lz);
   NoRay none;
   if (__builtin_amdgcn_ballot_w64(!ok))
-    return raycast_t<false, false, AUX>(f, dir, yscale, atan_dir, work, hit, none);
-  return raycast_t<true, true, AUX>(f, dir, yscale, atan_dir, work, hit, none);
+    return raycast_t<false, false, AUX>(f, v, dir, yscale, atan_dir, work, hit, none);
+  return raycast_t<true, true, AUX>(f, v, dir, yscale, atan_dir, work, hit, none);
 }
 
 // The lane's outcome into the planes of `aux` at output pixel (row r, column a) of the band.
@@ -500,20 +507,20 @@ __device__ __forceinline__ void store_planes(const VoxAux& aux, const VoxHit& hi
 // PLACE (k_voxel_place; sfrt_voxel_render_subset): the subset in place in a whole frame -- output
 // column a is stored xstride elements apart, the host having put the subset's first pixel into
 // f.out and yadd frame rows into f.out_pitch (the planes' pitches likewise).
-template <int SS, bool AUX, bool PLACE = false>
-__device__ __forceinline__ bool voxel_tile(const VoxFrame& f, const VoxAux& aux, int tiles_x,
+template <int SS, bool AUX, bool PLACE = false, class VIEW>
+__device__ __forceinline__ bool voxel_tile(const VoxFrame& f, const VIEW& v, const VoxAux& aux, int tiles_x,
                                            int ntiles, int& tile, uint32_t& cls, uint32_t& work,
                                            [[maybe_unused]] int xstride = 1) {
   const int lane = threadIdx.x & 63;
   int slot = (int)blockIdx.x;
-  if (f.prev_cost) {
+  if (v.prev_cost) {
     if (slot == 0) {
       sort_tiles(f.prev_cost, ntiles, f.next_order);
       return false;
     }
     slot -= 1;
   }
-  tile = slot_tile(f.tile_order, slot, ntiles, cls);
+  tile = slot_tile(v.tile_order, slot, ntiles, cls);
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int a = tx * 8 + (lane & 7);
   const int b = f.sub_row0 + ty * 8 + (lane >> 3);
@@ -524,9 +531,9 @@ __device__ __forceinline__ bool voxel_tile(const VoxFrame& f, const VoxAux& aux,
   const int i = subset_index<SS>(f.xstart, f.xadd, ac);
   const int j = subset_index<SS>(f.ystart, f.yadd, bc);
   work = 0;
-  const V3 dir{f.col[3 * i], f.row[2 * j], f.col[3 * i + 1]};
+  const V3 dir{v.col[3 * i], v.row[2 * j], v.col[3 * i + 1]};
   VoxHit hit;
-  const uint32_t rgba = raycast<AUX>(f, dir, f.row[2 * j + 1], f.col[3 * i + 2], work, hit);
+  const uint32_t rgba = raycast<AUX>(f, v, dir, v.row[2 * j + 1], v.col[3 * i + 2], work, hit);
   // The store's pixel from the lane id again (mbcnt, not threadIdx): kept live across
   // raycast(), a, b and `in` were spilled to scratch (16 bytes per lane).
   const int lane2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -541,12 +548,12 @@ __device__ __forceinline__ bool voxel_tile(const VoxFrame& f, const VoxAux& aux,
       store = store && group_leader<SS>(lane2);
     }
     if (store) {
-      f.out[(long long)(r2 >> SS) * f.out_pitch + c2] = px;
+      v.out[(long long)(r2 >> SS) * f.out_pitch + c2] = px;
       if constexpr (AUX) store_planes(aux, hit, r2 >> SS, c2);
     }
   } else if constexpr (SS == 0) {
     if (a2 < f.sub_w && r2 < f.sub_rows) {
-      f.out[(long long)r2 * f.out_pitch + a2] = rgba;
+      v.out[(long long)r2 * f.out_pitch + a2] = rgba;
       if constexpr (AUX) store_planes(aux, hit, r2, a2);
     }
   } else {
@@ -555,7 +562,7 @@ __device__ __forceinline__ bool voxel_tile(const VoxFrame& f, const VoxAux& aux,
     // (a2 >> SS, r2 >> SS), out and its pitch in output pixels
     const uint32_t px = group_box_rgba8<SS>(rgba);
     if (group_leader<SS>(lane2) && a2 < f.sub_w && r2 < f.sub_rows) {
-      f.out[(long long)(r2 >> SS) * f.out_pitch + (a2 >> SS)] = px;
+      v.out[(long long)(r2 >> SS) * f.out_pitch + (a2 >> SS)] = px;
       if constexpr (AUX) store_planes(aux, hit, r2 >> SS, a2 >> SS);
     }
   }
@@ -568,7 +575,7 @@ template <bool COST>
 __global__ __launch_bounds__(64, SFRT_VOX_WAVES) void k_voxel_ordered(VoxFrame f, int tiles_x, int ntiles) {
   int tile;
   uint32_t cls, work;
-  if (!voxel_tile<0, false>(f, VoxAux{}, tiles_x, ntiles, tile, cls, work)) return;
+  if (!voxel_tile<0, false>(f, f, VoxAux{}, tiles_x, ntiles, tile, cls, work)) return;
   if (COST) {
     // the tile's slowest ray, in DDA + shadow steps / 4 (the classes' scale)
     const uint32_t w = wave_max_u32(work);
@@ -581,7 +588,7 @@ template <bool COST, int SS>
 __global__ __launch_bounds__(64, SFRT_VOX_WAVES) void k_voxel_ordered_ss(VoxFrame f, int tiles_x, int ntiles) {
   int tile;
   uint32_t cls, work;
-  if (!voxel_tile<SS, false>(f, VoxAux{}, tiles_x, ntiles, tile, cls, work)) return;
+  if (!voxel_tile<SS, false>(f, f, VoxAux{}, tiles_x, ntiles, tile, cls, work)) return;
   if (COST) {  // as k_voxel_ordered: the sample tile's slowest ray
     const uint32_t w = wave_max_u32(work);
     if ((threadIdx.x & 63) == 0) store_cost(f.tile_cost, tile, tile_bucket(w >> 2), cls, f.cost_diff);
@@ -601,7 +608,7 @@ __global__ __launch_bounds__(64, SFRT_VOX_AUX_WAVES) void k_voxel_aux(VoxFrame f
                                                                       VoxAux aux) {
   int tile;
   uint32_t cls, work;
-  if (!voxel_tile<SS, true>(f, aux, tiles_x, ntiles, tile, cls, work)) return;
+  if (!voxel_tile<SS, true>(f, f, aux, tiles_x, ntiles, tile, cls, work)) return;
   if (COST) {  // as k_voxel_ordered
     const uint32_t w = wave_max_u32(work);
     if ((threadIdx.x & 63) == 0) store_cost(f.tile_cost, tile, tile_bucket(w >> 2), cls, f.cost_diff);
@@ -617,7 +624,38 @@ __global__ __launch_bounds__(64, AUX ? SFRT_VOX_AUX_WAVES : SFRT_VOX_WAVES) void
     VoxFrame f, int tiles_x, int ntiles, VoxAux aux, int xstride) {
   int tile;
   uint32_t cls, work;
-  (void)voxel_tile<SS, AUX, true>(f, aux, tiles_x, ntiles, tile, cls, work, xstride);
+  (void)voxel_tile<SS, AUX, true>(f, f, aux, tiles_x, ntiles, tile, cls, work, xstride);
+}
+
+// The view batches (sfrt_voxel_render_views[_aux]), one family over SS with AUX as
+// its flag on a two-dimensional grid: workgroup (x, y) is tile x, row-major, of view y.  The view's
+// record is read from the device table once, at entry, as sphere_trace.hip's view_rec_at reads its
+// own: the table is written only by the staging copy that precedes the launch on its stream and
+// the address is wave-uniform, so through the constant address space the fields arrive by scalar
+// loads, as a band kernel's arrive from its arguments.  They replace the per-camera fields of the
+// argument's frame (the camera, dda_qlim, the col / row / dyn tables, the target; the planes for
+// AUX); every other field is the argument's, shared by all views.  The tile-order pointers are
+// constants here, so the sorter, the order lookup and the cost record fold away.  A wave belongs to
+// one view, so raycast()'s fast-DDA vote uses that view's dda_qlim and stays wave-uniform.  Each
+// takes the bound of its sibling (plain: k_voxel_ordered's, planes: k_voxel_aux's).
+__device__ __forceinline__ VoxViewRec vox_view_rec_at(const VoxViewRec* p, uint32_t view) {
+  const __attribute__((address_space(4))) uint32_t* q =
+      (const __attribute__((address_space(4))) uint32_t*)(
+          (const __attribute__((address_space(4))) char*)p + (size_t)view * sizeof(VoxViewRec));
+  uint32_t w[sizeof(VoxViewRec) / 4];
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(VoxViewRec) / 4); i++) w[i] = q[i];
+  VoxViewRec r;
+  __builtin_memcpy(&r, w, sizeof r);
+  return r;
+}
+template <int SS, bool AUX>
+__global__ __launch_bounds__(64, AUX ? SFRT_VOX_AUX_WAVES : SFRT_VOX_WAVES) void k_voxel_views(
+    VoxFrame f, int tiles_x, int ntiles, const VoxViewRec* views) {
+  const VoxViewRec v = vox_view_rec_at(views, blockIdx.y);
+  int tile;
+  uint32_t cls, work;
+  (void)voxel_tile<SS, AUX>(f, v, AUX ? v.aux : VoxAux{}, tiles_x, ntiles, tile, cls, work);
 }
 
 // ---- Ray batches: World::Raycast / World::LRaycast for caller-supplied rays
@@ -687,9 +725,9 @@ __global__ __launch_bounds__(64, SFRT_VOX_WAVES) void k_voxel_cast_rays(VoxFrame
   VoxHit hit;
   uint32_t rgba;
   if (__builtin_amdgcn_ballot_w64(!walk_bounded(ray.org, dir, (float)f.maxiter)))
-    rgba = raycast_t<false, false, true, OWN, SHADE>(f, dir, yscale, atan_dir, work, hit, ray);
+    rgba = raycast_t<false, false, true, OWN, SHADE>(f, f, dir, yscale, atan_dir, work, hit, ray);
   else
-    rgba = raycast_t<true, true, true, OWN, SHADE>(f, dir, yscale, atan_dir, work, hit, ray);
+    rgba = raycast_t<true, true, true, OWN, SHADE>(f, f, dir, yscale, atan_dir, work, hit, ray);
   if (in) {  // an invalid ray: face 0, cell -1, steps 0, all-zero bytes elsewhere
     if (a.pos) {
       float* const o = a.pos + 3 * q;
@@ -848,6 +886,43 @@ int launch_voxel(const VoxFrame& f, void* stream, void* done_event, const VoxAux
   else
     hipExtLaunchKernelGGL(k_voxel_ordered<false>, grid, dim3(64), 0, (hipStream_t)stream, nullptr,
                           (hipEvent_t)done_event, 0, f, (int)((f.sub_w + 7) / 8), (int)tiles);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+namespace {
+template <int SS>
+void launch_views(const VoxFrame& f, const VoxViewRec* views, bool aux, dim3 grid, long long tiles,
+                  void* stream, void* done_event) {
+  if (aux)
+    hipExtLaunchKernelGGL((k_voxel_views<SS, true>), grid, dim3(64), 0, (hipStream_t)stream, nullptr,
+                          (hipEvent_t)done_event, 0, f, (int)((f.sub_w + 7) / 8), (int)tiles, views);
+  else
+    hipExtLaunchKernelGGL((k_voxel_views<SS, false>), grid, dim3(64), 0, (hipStream_t)stream, nullptr,
+                          (hipEvent_t)done_event, 0, f, (int)((f.sub_w + 7) / 8), (int)tiles, views);
+}
+}  // namespace
+
+bool voxel_views_grid_ok(const VoxFrame& f, int count) {
+  long long tiles = 0;
+  if (voxel_tile_key(f, &tiles) == 0) return false;
+  // work-items per grid dimension are 32 bits, workgroups in all at most 2^31 - 1
+  return count > 0 && tiles * 64 <= 0xffffffffLL && tiles * count <= 0x7fffffffLL;
+}
+
+int launch_voxel_views(const VoxFrame& f, const VoxViewRec* dev_views, int count, bool aux,
+                       void* stream, void* done_event) {
+  if (!voxel_views_grid_ok(f, count) || count > 65535 || !dev_views) return -1;
+  long long tiles = 0;
+  (void)voxel_tile_key(f, &tiles);
+  // as launch_voxel: the grid through a buffer resource; the per-view tables come from the records
+  if (!f.cells || f.cell_bytes == 0 || !f.status || (f.nlights > 0 && !f.lights)) return -1;
+  if (f.tile_order || f.tile_cost || f.prev_cost || f.next_order) return -1;
+  if (f.ss < 0 || f.ss > 2 || f.sub_row0 != 0) return -1;
+  if (f.ss && ((f.sub_w | f.sub_rows) & ((1 << f.ss) - 1))) return -1;
+  const dim3 grid((unsigned)tiles, (unsigned)count);
+  if (f.ss == 0) launch_views<0>(f, dev_views, aux, grid, tiles, stream, done_event);
+  else if (f.ss == 1) launch_views<1>(f, dev_views, aux, grid, tiles, stream, done_event);
+  else launch_views<2>(f, dev_views, aux, grid, tiles, stream, done_event);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

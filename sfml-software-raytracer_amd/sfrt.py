@@ -73,10 +73,12 @@ ABI_SYMBOLS = (
     "sfrt_voxel_render_subset", "sfrt_voxel_render_subset_aux",
     "sfrt_world_render_views", "sfrt_world_render_views_aux",
     "sfrt_world_cull_cache_stats", "sfrt_world_hit_cache_stats",
+    "sfrt_voxel_render_views", "sfrt_voxel_render_views_aux", "sfrt_voxel_sort_dynamics",
 )
 
 SFRT_MAX_VIEWS = 1024
 SFRT_VIEWS_SORT = 1
+SFRT_VOXEL_VIEWS_DYNAMICS = 1
 
 SFRT_MULTI_AUTO, SFRT_MULTI_RCCL, SFRT_MULTI_PEER = 0, 1, 2
 SFRT_TRANSFER_AUTO, SFRT_TRANSFER_RGBA, SFRT_TRANSFER_PACKED = 0, 1, 2
@@ -246,6 +248,10 @@ def lib() -> ctypes.CDLL:
         "sfrt_voxel_cast_rays_device": ([vp, vp, vp, vp, ctypes.c_int64, P(VoxelRayHits), vp], c_int),
         "sfrt_voxel_cast_shadow_rays": ([vp, vp, vp, vp, ctypes.c_int64, vp, vp], c_int),
         "sfrt_voxel_cast_shadow_rays_device": ([vp, vp, vp, vp, ctypes.c_int64, vp, vp, vp], c_int),
+        "sfrt_voxel_render_views": ([vp, P(View), c_int, ctypes.c_int64, c_int, vp], c_int),
+        "sfrt_voxel_render_views_aux": ([vp, P(View), P(VoxelAuxPlanes), c_int, ctypes.c_int64, c_int,
+                                         vp], c_int),
+        "sfrt_voxel_sort_dynamics": ([vp, c_int, vp], c_int),
         "sfrt_voxel_check": ([vp, vp], c_int),
         "sfrt_voxel_set_option": ([vp, c_int, c_int], c_int),
         "sfrt_voxel_get_option": ([vp, c_int, P(c_int)], c_int),
@@ -318,6 +324,19 @@ def sort_spheres(spheres, cam_pos=(0.0, 0.0, 0.0)) -> np.ndarray:
     cam = (ctypes.c_float * 3)(*[float(c) for c in cam_pos])
     _check(lib().sfrt_sort_spheres(s.ctypes.data, s.shape[0], cam), "sfrt_sort_spheres")
     return s
+
+
+def sort_dynamics(dyn, cam_pos) -> np.ndarray:
+    """A copy of `dyn` (voxel_scenes.DYN_DTYPE records) with dist_to_camera set for cam_pos and in
+    the stable ascending order of sfrt_voxel_sort_dynamics: the list a camera at rest sees."""
+    d = np.array(dyn, copy=True)
+    if d.ndim != 1 or d.dtype.itemsize != 40 or not d.flags.c_contiguous:
+        raise ValueError("dyn must be a contiguous 1-D array of sfrt_dynamic records (40 bytes)")
+    if len(cam_pos) != 3:
+        raise ValueError("cam_pos must have three components")
+    cam = (ctypes.c_float * 3)(*[float(c) for c in cam_pos])
+    _check(lib().sfrt_voxel_sort_dynamics(d.ctypes.data, d.shape[0], cam), "sfrt_voxel_sort_dynamics")
+    return d
 
 
 def build_flavour() -> str:
@@ -836,6 +855,56 @@ class VoxelWorld:
                                                   int(xstart), int(xadd),
                                                   ctypes.c_void_p(stream or None)),
                "voxel_render_subset_aux")
+
+    def set_camera(self, cam: Camera) -> None:
+        """World::cam alone (sfrt_voxel_set_camera); set_scene sets it with everything else."""
+        _check(lib().sfrt_voxel_set_camera(self._h, ctypes.byref(cam)), "voxel_set_camera")
+
+    def set_dynamics(self, dyn) -> None:
+        """The `dyn` list alone, in list order (sfrt_voxel_set_dynamics; voxel_scenes.DYN_DTYPE)."""
+        d = np.ascontiguousarray(dyn)
+        if d.ndim != 1 or d.dtype.itemsize != 40:
+            raise ValueError("dyn must be a 1-D array of sfrt_dynamic records (40 bytes)")
+        _check(lib().sfrt_voxel_set_dynamics(self._h, d.ctypes.data, d.shape[0]), "voxel_set_dynamics")
+
+    def render_views(self, views, pitch_bytes: int, dynamics: bool = False, stream: int = 0) -> None:
+        """A batch of whole frames of this world in one launch (sfrt_voxel_render_views): view k
+        is the frame set_camera(views[k].cam) [+ the list sorted for that camera with dynamics] +
+        render_band would write at views[k].dev_pixels; the world itself is left as it was.
+        views: View objects or (Camera, device pointer) pairs.  Asynchronous on `stream`."""
+        if len(views) > SFRT_MAX_VIEWS:
+            raise ValueError(f"at most {SFRT_MAX_VIEWS} views")
+        arr = World._view_array(views)
+        _check(lib().sfrt_voxel_render_views(self._h, arr, len(views), int(pitch_bytes),
+                                             SFRT_VOXEL_VIEWS_DYNAMICS if dynamics else 0,
+                                             ctypes.c_void_p(stream or None)), "voxel_render_views")
+
+    def render_views_aux(self, views, planes, pitch_bytes: int, dynamics: bool = False,
+                         stream: int = 0) -> None:
+        """render_views plus each view's planes (sfrt_voxel_render_views_aux): planes[k] is a
+        VoxelAuxPlanes, or a dict of render_band_aux's (device pointer, pitch in bytes) pairs
+        under "depth", "cell", "face" and "steps"."""
+        if len(views) > SFRT_MAX_VIEWS:
+            raise ValueError(f"at most {SFRT_MAX_VIEWS} views")
+        if len(planes) != len(views):
+            raise ValueError("one planes entry per view")
+        arr = World._view_array(views)
+        pl = (VoxelAuxPlanes * max(1, len(views)))()
+        for k, p in enumerate(planes):
+            if not isinstance(p, VoxelAuxPlanes):
+                q = VoxelAuxPlanes()
+                for name, plane in p.items():
+                    if name not in ("depth", "cell", "face", "steps"):
+                        raise ValueError(f"unknown plane {name!r}")
+                    if plane is not None:
+                        setattr(q, name, int(plane[0]))
+                        setattr(q, name + "_pitch_bytes", int(plane[1]))
+                p = q
+            pl[k] = p
+        _check(lib().sfrt_voxel_render_views_aux(self._h, arr, pl, len(views), int(pitch_bytes),
+                                                 SFRT_VOXEL_VIEWS_DYNAMICS if dynamics else 0,
+                                                 ctypes.c_void_p(stream or None)),
+               "voxel_render_views_aux")
 
     def update_image_aux(self, pixels: np.ndarray, depth=None, cell=None, face=None, steps=None,
                          ystart=0, yadd=1, xstart=0, xadd=1) -> np.ndarray:
