@@ -392,13 +392,29 @@ SFRT_API int sfrt_world_cast_rays(sfrt_world* w, const float* dirs, const float*
  * the limit is not created (at the default an 8K frame's 530.8 MB: raise the option to 600 to
  * serve such frames from it) and the launch stays on the cull cache; lowering the limit below what is held waits
  * for the device and frees every hit cache.  sfrt_world_row_costs keeps answering from the last
- * launch that marched.  See sfrt_world_hit_cache_stats. */
+ * launch that marched.  See sfrt_world_hit_cache_stats.
+ * SFRT_OPT_TEXEL_CACHE (1 = default; 0 = off; negative values return SFRT_E_INVALID): the texel
+ * cache on top of the hit cache.  What a launch that shades from the hit cache still computes per
+ * ray -- the texel's index in the texture atlas -- depends on the hit cache's state and on the
+ * texture sizes and the spheres' texture slots, not on the textures' contents.  While those stand
+ * still too, the second consecutive launch that reads the hit cache also writes, per ray, that
+ * index and the brightness (8 bytes per ray: 66.4 MB for a 4K frame; supersampled, per sample),
+ * and later launches read those 8 bytes in place of the 16 of the hit cache and no sphere record:
+ * the same bytes and the same status.  Loading a texture of the same size into a slot keeps the
+ * cache (the texels are read every frame); a texture of another size, another slot for a sphere,
+ * or a load that moves another slot in the atlas makes the next launch shade from the hit cache,
+ * which stays allocated, and the one after write the indices again.  The bytes count against
+ * SFRT_OPT_HIT_CACHE_MB beside the hit cache's (two 4K streams: 2 x (132.7 + 66.4) = 398 MB);
+ * where they do not fit, launches stay on the hit cache.  Whatever drops or refills the hit cache
+ * drops the texel cache; setting the option to 0 waits for the device and frees the texel caches
+ * only.  See sfrt_world_texel_cache_stats. */
 #define SFRT_OPT_CULL 1
 #define SFRT_OPT_RAYS_PER_LANE 2
 #define SFRT_OPT_TILE_ORDER 3
 #define SFRT_OPT_SUPERSAMPLE 4
 #define SFRT_OPT_RAY_CACHE_MB 5
 #define SFRT_OPT_HIT_CACHE_MB 6
+#define SFRT_OPT_TEXEL_CACHE 7
 SFRT_API int sfrt_world_set_option(sfrt_world* w, int option, int value);
 /* The current value of any of the options above (SFRT_OPT_SUPERSAMPLE: the factor 1, 2 or 4). */
 SFRT_API int sfrt_world_get_option(const sfrt_world* w, int option, int* value);
@@ -424,6 +440,13 @@ SFRT_API int sfrt_world_cull_cache_stats(const sfrt_world* w, int64_t* fills, in
  * of the other caches' bytes. */
 SFRT_API int sfrt_world_hit_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits,
                                         int64_t* bytes);
+/* The texel cache's counters since the world was created (SFRT_OPT_TEXEL_CACHE): *fills = launches
+ * that shaded from the hit cache and stored their texel indices, *hits = launches that shaded from
+ * stored indices (each also counts as a hit of sfrt_world_hit_cache_stats and of the caches under
+ * it), *bytes = device memory the world's texel caches hold now.  Counted against
+ * SFRT_OPT_HIT_CACHE_MB, not part of sfrt_world_hit_cache_stats' bytes. */
+SFRT_API int sfrt_world_texel_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits,
+                                          int64_t* bytes);
 
 /* ---- stateless helpers ---- */
 /* UpdateSpheres ordering of an array in place (SphereWorld.cpp:199-212). */

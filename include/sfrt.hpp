@@ -314,6 +314,16 @@ class SphereWorld {
     check(sfrt_world_hit_cache_stats(w_, &s.fills, &s.hits, &s.bytes), "hit_cache_stats");
     return s;
   }
+  // SFRT_OPT_TEXEL_CACHE (sfrt.h): the texel cache on the hit cache, under its budget; 0 = off.
+  void SetTexelCache(bool on) { SetOption(SFRT_OPT_TEXEL_CACHE, on ? 1 : 0); }
+  bool TexelCache() const { return GetOption(SFRT_OPT_TEXEL_CACHE) != 0; }
+  // The texel cache's counters (sfrt.h sfrt_world_texel_cache_stats).
+  using TexelCacheStats = CullCacheStats;  // the same three counters
+  TexelCacheStats GetTexelCacheStats() const {
+    TexelCacheStats s{};
+    check(sfrt_world_texel_cache_stats(w_, &s.fills, &s.hits, &s.bytes), "texel_cache_stats");
+    return s;
+  }
   sfrt_world* handle() { return w_; }
 
  private:

@@ -7,12 +7,14 @@
 // and reads them from then on (sphere_trace.hip: k_ray_fill, the CACHED kernels).  On the tile
 // records rides the cull cache (CullKey: what each tile's wave culls before it marches), and on
 // that, under the same key, the hit cache (HitRec: what each ray's march leaves the shading).
-// One policy (CacheLayer) decides for each of the three; one object per chain (ChainCaches, at
-// the end) owns the layers, their five buffers and the order in which a launch decides, fills
+// On the hit cache rides the texel cache (TexKey, TexelRec: the texel index and the brightness
+// the shading is left with once the texture sizes and slots stand still too).
+// One policy (CacheLayer) decides for each of the four; one object per chain (ChainCaches, at
+// the end) owns the layers, their six buffers and the order in which a launch decides, fills
 // and drops them.  This header makes no HIP call -- the device is a parameter of
 // ChainCaches::begin -- so all of it is tested on the host as it ships: tests/native/
-// raycache_check.cpp (the layer), tilerec_check.cpp, cullcache_check.cpp, hitcache_check.cpp
-// (the chain, through counting allocators).
+// raycache_check.cpp (the layer), tilerec_check.cpp, cullcache_check.cpp, hitcache_check.cpp,
+// texelcache_check.cpp (the chain, through counting allocators).
 #pragma once
 
 #include <cstdint>
@@ -242,6 +244,74 @@ inline long long hit_cache_bytes(long long tiles, int rays) {
   return tiles * rays * 64 * (long long)sizeof(HitRec);
 }
 
+// ---- The texel cache (DESIGN.md 5 "Texel cache") ----
+//
+// What the reading kernels still compute of a HitRec every frame -- tw, th of the drawn record's
+// tex_wh, tx = cvt(fu * tw), ty = cvt(fw * th), idx = tx + ty * tw, outside = !(idx < tw * th),
+// tex = tex_off + idx -- depends on the record (fixed under CullKey) and on the drawn records'
+// tex_off and tex_wh, and on nothing else: not on the atlas pointer and not on a texel's value.
+// While those stand still too (TexKey), a ray needs 8 bytes: the texel's index in the atlas and
+// the brightness.  Filled by the _tf instantiation of the k_shade_hits kernels (a launch that
+// reads the hit layer anyway), read by k_shade_texels, which gathers no SphereRec at all.
+//
+// Per ray one 8-byte record, 8-byte aligned, indexed like HitRec: [tile][r][lane], every lane,
+// clamped duplicates included, per sample when supersampled.
+//   tex: Shading::tex as shade_texel leaves it (tex_off + idx), or kTexelRecOutside where the index
+//     fell outside the texture.  sfrt_world_load_texture refuses an atlas above 0xffffffff texels,
+//     so a valid index is at most 0xfffffffe and the sentinel is free (texel_index_fits: asserted
+//     where the key is made; the layer is not filled otherwise).
+//   bright: the brightness' binary32 bits with bit 31 reused for "the ray still moved at the guard"
+//     (kHitRecMoving's meaning).  The brightness is 3 / max(bl, 3) with bl a correctly rounded root
+//     or NaN: max(bl, 3) is >= 3 or NaN, so the quotient is in [+0, 1] or NaN -- never negative,
+//     never -0 -- and its sign bit carries nothing unless it is a NaN.  A NaN's sign cannot reach
+//     a byte: shade_rgba multiplies (NaN of either sign) and ends in v_cvt_u32_f32, which gives 0
+//     for every NaN.  The reading kernel clears bit 31 and feeds the rest into that shade_rgba.
+struct alignas(8) TexelRec {
+  uint32_t tex;
+  uint32_t bright;
+};
+static_assert(sizeof(TexelRec) == 8 && alignof(TexelRec) == 8, "one 8-byte access per ray");
+constexpr uint32_t kTexelRecOutside = 0xffffffffu;
+constexpr uint32_t kTexelRecMoving = 0x80000000u;
+
+#if defined(__HIP__)
+#define SFRT_TEXEL_HD __host__ __device__ __forceinline__
+#else
+#define SFRT_TEXEL_HD inline
+#endif
+SFRT_TEXEL_HD uint32_t texel_pack_tex(uint32_t tex, bool outside) { return outside ? kTexelRecOutside : tex; }
+SFRT_TEXEL_HD uint32_t texel_pack_bright(uint32_t brightness_bits, bool moving) {
+  return (brightness_bits & ~kTexelRecMoving) | (moving ? kTexelRecMoving : 0u);
+}
+SFRT_TEXEL_HD bool texel_outside(uint32_t tex) { return tex == kTexelRecOutside; }
+SFRT_TEXEL_HD bool texel_moving(uint32_t bright) { return (bright & kTexelRecMoving) != 0; }
+SFRT_TEXEL_HD uint32_t texel_bright_bits(uint32_t bright) { return bright & ~kTexelRecMoving; }
+#undef SFRT_TEXEL_HD
+
+inline long long texel_cache_bytes(long long tiles, int rays) {
+  return tiles * rays * 64 * (long long)sizeof(TexelRec);
+}
+// Whether every texel index of an atlas of `texels` texels stays below the sentinel.
+inline bool texel_index_fits(unsigned long long texels) { return texels <= 0xffffffffull; }
+
+// The launch's CullKey plus tex_off and tex_wh of records 0..n-1.  Neither the atlas pointer nor a
+// texel's value: a texture reloaded at its size keeps the layer; a resize, a slot change or a
+// reload that shifts another slot's offset changes the key.
+struct TexKey {
+  CullKey cull;
+  std::vector<uint32_t> tex;  // tex_off, tex_wh per record, n records
+
+  template <class Rec>
+  void set_textures(const Rec* recs, int count) {
+    tex.resize((size_t)(count > 0 ? count : 0) * 2);
+    for (int k = 0; k < count; k++) {
+      tex[(size_t)k * 2] = recs[k].tex_off;
+      tex[(size_t)k * 2 + 1] = recs[k].tex_wh;
+    }
+  }
+  bool same(const TexKey& o) const { return tex == o.tex && cull.same(o.cull); }
+};
+
 // ---- One chain's caches (DESIGN.md 5 "The chain's caches") ----
 
 // What ChainCaches::begin decided for one launch and what that launch reads: launch_trace's cache
@@ -249,39 +319,52 @@ inline long long hit_cache_bytes(long long tiles, int rays) {
 struct TraceCaches {
   bool decided = false;  // begin() made it: end() has something to commit
   RayAction ray = RayAction::kTrace, cull = RayAction::kTrace, hit = RayAction::kTrace;
+  RayAction texel = RayAction::kTrace;  // kRead implies hit == kRead; kFill rides on a hit read
   const float* dirs = nullptr;
   const TileRec* tile_recs = nullptr;
   const CullRec* cull_recs = nullptr;
   const void* cull_wins = nullptr;  // CullWin or CullWinList
   HitRec* hit_recs = nullptr;       // written by a filling launch (hit == kFill), read by a reading one
+  TexelRec* texel_recs = nullptr;   // likewise (a launch that reads them still gets hit_recs, unread)
   bool reading() const { return hit == RayAction::kRead; }  // no march: outside the tile order
 };
 
 struct CacheSizes {  // of one launch's grid: ray_cache_bytes, tile_rec_bytes, cull_*_bytes, hit_cache_bytes
   long long dirs = 0, tile_recs = 0, cull_recs = 0, cull_wins = 0, hit_recs = 0;
+  long long texel_recs = 0;  // texel_cache_bytes (0: no texel layer)
 };
 
-struct CacheCounters {  // sfrt_world_{ray,cull,hit}_cache_stats
+struct CacheCounters {  // sfrt_world_{ray,cull,hit,texel}_cache_stats
   int64_t ray_cached_frames = 0, ray_fills = 0, cull_fills = 0, cull_hits = 0, hit_fills = 0, hit_hits = 0;
+  int64_t texel_fills = 0, texel_hits = 0;
 };
 
-// The three layers and the five buffers of one tile-order chain, and the one rule between them:
+// The four layers and the six buffers of one tile-order chain, and the one rule between them:
 // an upper cache is never valid without the one under it.  A refill below drops what is above; a
-// failed fill drops its own layer and everything above it; a failed launch drops all three.
+// failed fill drops its own layer and everything above it; a failed launch drops all four.
+// The texel layer (TexKey) has no fill kernel of its own and is not filled by a marching launch:
+// only a launch that reads the hit layer fills it (the _tf kernels), and a launch that reads it
+// counts as a read of the three layers under it.
 struct ChainCaches {
   CacheLayer<RayKey> ray;
   CacheLayer<CullKey> cull, hit;
+  CacheLayer<TexKey> texel;
   CacheBuf dirs, tile_recs;  // ray_cache_bytes, tile_rec_bytes: one layer, two buffers
   CacheBuf cull_recs, cull_wins;
   CacheBuf hit_recs;
+  CacheBuf texel_recs;
   RayKey ray_key{};  // begin() -> end(): the launch being queued
   CullKey cull_key;
+  TexKey tex_key;
+  bool have_tex_key = false;
 
   long long cull_bytes() const { return cull_recs.bytes + cull_wins.bytes; }
   // What SFRT_OPT_RAY_CACHE_MB limits (the tile records ride free: 0.3 to 1 % of the directions),
   // what SFRT_OPT_HIT_CACHE_MB limits, and the tile records, reported on their own.
   long long bytes_under_ray_budget() const { return dirs.bytes + cull_bytes(); }
-  long long hit_bytes() const { return hit_recs.bytes; }
+  long long hit_bytes() const { return hit_recs.bytes; }  // the hit records alone (the stats)
+  long long texel_bytes() const { return texel_recs.bytes; }
+  long long bytes_under_hit_budget() const { return hit_recs.bytes + texel_recs.bytes; }
   long long tile_rec_bytes() const { return tile_recs.bytes; }
 
   // Before a launch that takes part.  other_ray, other_hit: what the world's other chains hold
@@ -289,24 +372,29 @@ struct ChainCaches {
   // alloc(n) -> pointer or null, fill_rays(dirs, tile_recs) -> bool and fill_cull(tile_recs,
   // cull_recs, cull_wins) -> bool queue the fill kernels for this launch's frame.  A fill that
   // fails is no error of the frame: the launch runs what it would run without that cache.
+  // tk: the launch's TexKey (tk->cull equal to ck), or null: no texel layer for this launch.
   template <class Dev>
   TraceCaches begin(const RayKey& rk, const CullKey& ck, const CacheSizes& n, long long other_ray,
-                    long long other_hit, long long ray_budget, long long hit_budget, Dev&& dev) {
+                    long long other_hit, long long ray_budget, long long hit_budget, Dev&& dev,
+                    const TexKey* tk = nullptr) {
     const auto free_fn = [&dev](void* p) { return dev.free(p); };
     const auto reserve = [&](CacheBuf& b, long long m) {
       return b.reserve(m, free_fn, [&dev](long long q) { return dev.alloc(q); });
     };
     ray_key = rk;
     cull_key = ck;
+    have_tex_key = tk != nullptr;
+    if (tk) tex_key = *tk;
     TraceCaches d;
     d.decided = true;
     d.ray = ray.decide(rk, RayAction::kRead, n.dirs, dirs.bytes, other_ray, ray_budget);
     if (d.ray == RayAction::kFill) {
       // The tile records are rewritten: what rides on them goes first and takes no room from the
       // directions.  have_prev stays, so this very launch can go on to fill all three.
-      for (CacheBuf* b : {&cull_recs, &cull_wins, &hit_recs}) b->release(free_fn);
+      for (CacheBuf* b : {&cull_recs, &cull_wins, &hit_recs, &texel_recs}) b->release(free_fn);
       cull.valid = false;
       hit.valid = false;
+      texel.valid = false;
       if (!reserve(dirs, n.dirs) || !reserve(tile_recs, n.tile_recs) ||
           !dev.fill_rays((float*)dirs.ptr, (TileRec*)tile_recs.ptr)) {
         invalidate();  // the buffers may be gone or half written
@@ -325,6 +413,7 @@ struct ChainCaches {
          !dev.fill_cull((const TileRec*)tile_recs.ptr, (CullRec*)cull_recs.ptr, cull_wins.ptr))) {
       cull.invalidate();  // the tile records are whole: the launch reads them
       hit.invalidate();
+      texel.invalidate();
       d.cull = RayAction::kTrace;
     }
     if (d.cull != RayAction::kTrace) {
@@ -333,12 +422,31 @@ struct ChainCaches {
     }
     // The hit cache, on top of the cull cache, under the same key and a budget of its own; the
     // launch that marches anyway fills it, so there is only room to find.
-    d.hit = hit.decide(ck, d.cull, n.hit_recs, hit_recs.bytes, other_hit, hit_budget);
-    if (d.hit == RayAction::kFill && !reserve(hit_recs, n.hit_recs)) {
-      hit.invalidate();  // no memory for it: the launch stays on the cull-cache path
-      d.hit = RayAction::kTrace;
+    // (a fill rewrites the records the texel layer was made from: that layer's bytes go first and
+    // are this chain's to reuse)
+    d.hit = hit.decide(ck, d.cull, n.hit_recs, bytes_under_hit_budget(), other_hit, hit_budget);
+    if (d.hit == RayAction::kFill) {
+      texel_recs.release(free_fn);
+      texel.valid = false;
+      if (!reserve(hit_recs, n.hit_recs)) {
+        hit.invalidate();  // no memory for it: the launch stays on the cull-cache path
+        texel.invalidate();
+        d.hit = RayAction::kTrace;
+      }
     }
     if (d.hit != RayAction::kTrace) d.hit_recs = (HitRec*)hit_recs.ptr;
+    // The texel cache, on top of the hit cache and under its budget.  It has no fill kernel and the
+    // _hf kernels do not store it: only a launch that reads the hit layer fills it.
+    if (tk) {
+      d.texel = texel.decide(*tk, d.hit, n.texel_recs, texel_recs.bytes, other_hit + hit_recs.bytes,
+                             hit_budget);
+      if (d.texel == RayAction::kFill && d.hit != RayAction::kRead) d.texel = RayAction::kTrace;
+      if (d.texel == RayAction::kFill && !reserve(texel_recs, n.texel_recs)) {
+        texel.invalidate();  // no memory for it: the launch reads the hit layer
+        d.texel = RayAction::kTrace;
+      }
+      if (d.texel != RayAction::kTrace) d.texel_recs = (TexelRec*)texel_recs.ptr;
+    }
     return d;
   }
 
@@ -352,30 +460,46 @@ struct ChainCaches {
     ray.commit(ray_key, d.ray, false);
     cull.commit(cull_key, d.cull, ray_filled);
     hit.commit(cull_key, d.hit, ray_filled || cull_filled);
+    const bool hit_filled = d.hit == RayAction::kFill;
+    if (have_tex_key) texel.commit(tex_key, d.texel, ray_filled || cull_filled || hit_filled);
+    else if (ray_filled || cull_filled || hit_filled) texel.valid = false;
     n.ray_fills += ray_filled;
     n.ray_cached_frames += d.ray != RayAction::kTrace;
     n.cull_fills += cull_filled;
     n.cull_hits += d.cull == RayAction::kRead;
     n.hit_fills += d.hit == RayAction::kFill;
     n.hit_hits += d.hit == RayAction::kRead;
+    n.texel_fills += d.texel == RayAction::kFill;
+    n.texel_hits += d.texel == RayAction::kRead;
   }
 
   void invalidate() {
     ray.invalidate();
     cull.invalidate();
     hit.invalidate();
+    texel.invalidate();
   }
-  void invalidate_hit() { hit.invalidate(); }
+  void invalidate_hit() {
+    hit.invalidate();
+    texel.invalidate();
+  }
+  void invalidate_texel() { texel.invalidate(); }
 
   // Freed by the host once the device has drained (an option lowered, the world going away).
   template <class Free>
   void release_hit(Free&& free_fn) {
     hit_recs.release(free_fn);
-    hit.invalidate();
+    texel_recs.release(free_fn);
+    invalidate_hit();
+  }
+  template <class Free>
+  void release_texel(Free&& free_fn) {
+    texel_recs.release(free_fn);
+    texel.invalidate();
   }
   template <class Free>
   void release_all(Free&& free_fn) {
-    for (CacheBuf* b : {&dirs, &tile_recs, &cull_recs, &cull_wins, &hit_recs}) b->release(free_fn);
+    for (CacheBuf* b : {&dirs, &tile_recs, &cull_recs, &cull_wins, &hit_recs, &texel_recs}) b->release(free_fn);
     invalidate();
   }
 };

@@ -136,6 +136,7 @@ struct sfrt_world {
   int ss = 0;             // SFRT_OPT_SUPERSAMPLE: log2 of the factor S (0, 1, 2)
   int ray_cache_mb = 512;  // SFRT_OPT_RAY_CACHE_MB: MiB of ray caches over all chains (0: off)
   int hit_cache_mb = 512;  // SFRT_OPT_HIT_CACHE_MB: MB (10^6 bytes) of hit caches over all chains (0: off)
+  int texel_cache = 1;     // SFRT_OPT_TEXEL_CACHE: the texel layer on the hit cache, under its budget (0: off)
   // --- device resources ---
   hipStream_t stream = nullptr;
   uint32_t* d_tex = nullptr;  // texture atlas: every loaded slot, back to back
@@ -158,7 +159,7 @@ struct sfrt_world {
   // launch between sched_begin and sched_end: what its chain decided, which launch_trace reads
   // (decided == false: the launch takes no part).  Counters: the three sfrt_world_*_cache_stats.
   sfrt::ChainCaches caches[sfrt::TileChains::kChains];
-  sfrt::CullKey cull_key;  // sched_begin's scratch: the records' vector keeps its capacity
+  sfrt::TexKey tex_key;  // sched_begin's scratch (its .cull: the launch's CullKey): the vectors keep their capacity
   sfrt::TraceCaches launch_caches;
   sfrt::CacheCounters cache_stats;
   // Device copies of the sphere records for launches that read them from memory
@@ -442,18 +443,26 @@ struct sfrt_world {
                      std::memcmp(&chain_last.cam, &cam, sizeof cam) != 0;
     launch_caches = sfrt::TraceCaches{};
     if (!aux && tile_order_on == 1 && p.tile_cost && sched.pending_key != 0) {
+      sfrt::CullKey& cull_key = tex_key.cull;
       make_cull_key(cull_key, make_ray_key(f, key), f, recs);
+      // The texel layer: every index below the sentinel (load_texture refuses larger atlases;
+      // were that to change, the layer is not filled).
+      const bool texels = texel_cache != 0 && sfrt::texel_index_fits(d_tex_texels);
+      if (texels) make_tex_key(tex_key, recs, f.n);
       const int rays = (int)((key >> 56) & 7);
       const sfrt::CacheSizes sizes{sfrt::ray_cache_bytes(tiles, rays), sfrt::tile_rec_bytes(tiles),
                                    sfrt::cull_rec_bytes(tiles),
                                    sfrt::cull_win_bytes(tiles, f.n > sfrt::kInlineSpheres),
-                                   sfrt::hit_cache_bytes(tiles, rays)};
+                                   sfrt::hit_cache_bytes(tiles, rays),
+                                   texels ? sfrt::texel_cache_bytes(tiles, rays) : 0};
       sfrt::ChainCaches& mine = caches[cur_chain];
       // (the diagnostic builds exist to time the march: no hit cache)
       launch_caches = mine.begin(cull_key.ray, cull_key, sizes,
                                  cache_bytes_held() - mine.bytes_under_ray_budget(),
-                                 hit_bytes_held() - mine.hit_bytes(), (long long)ray_cache_mb << 20,
-                                 sfrt::kDiagnosticBuild ? 0 : hit_budget_bytes(), CacheDevice{s, f, recs});
+                                 hit_bytes_budgeted() - mine.bytes_under_hit_budget(),
+                                 (long long)ray_cache_mb << 20,
+                                 sfrt::kDiagnosticBuild ? 0 : hit_budget_bytes(), CacheDevice{s, f, recs},
+                                 texels ? &tex_key : nullptr);
       // A reading launch marches nothing and takes no part in the tile order: nothing is linked.
       if (launch_caches.reading()) {
         sfrt::TileSchedPtrs{}.link(f);
@@ -471,6 +480,12 @@ struct sfrt_world {
     k.first_l = sfrt::ray_key_bits(f.first_l);
     k.cull = f.cull;  // the option, cleared by prepare_frame for non-finite inputs
     k.set_records(recs.data(), f.n);
+  }
+
+  // k.cull is the launch's CullKey already (sched_begin); tex_off and tex_wh as prepare_records
+  // wrote them.
+  static void make_tex_key(sfrt::TexKey& k, const std::vector<sfrt::SphereRec>& recs, int n) {
+    k.set_textures(recs.data(), n);
   }
 
   static sfrt::RayKey make_ray_key(const sfrt::FrameRec& f, long long tile_key) {
@@ -502,8 +517,14 @@ struct sfrt_world {
   long long cache_bytes_held() const {
     return held([](const sfrt::ChainCaches& c) { return c.bytes_under_ray_budget(); });
   }
-  long long hit_bytes_held() const {
+  long long hit_bytes_held() const {  // the hit records alone (sfrt_world_hit_cache_stats)
     return held([](const sfrt::ChainCaches& c) { return c.hit_bytes(); });
+  }
+  long long texel_bytes_held() const {
+    return held([](const sfrt::ChainCaches& c) { return c.texel_bytes(); });
+  }
+  long long hit_bytes_budgeted() const {  // with the texel records: what the option limits
+    return held([](const sfrt::ChainCaches& c) { return c.bytes_under_hit_budget(); });
   }
 
   // The device as a chain's caches see it (ChainCaches::begin): buffers freed and allocated in
@@ -535,10 +556,15 @@ struct sfrt_world {
   // An option lowered below what the chains hold (hit_only: SFRT_OPT_HIT_CACHE_MB, the hit caches
   // go; else SFRT_OPT_RAY_CACHE_MB, every cache goes).  The chains' streams may be gone
   // (sfrt_sched.h), so the host waits for the device.
-  int release_caches(bool hit_only) {
+  // texel_only: SFRT_OPT_TEXEL_CACHE, that layer alone.
+  int release_caches(bool hit_only, bool texel_only = false) {
     HIP_TRY(hipDeviceSynchronize());
     const auto free_now = [](void* p) { return hipFree(p) == hipSuccess; };
-    for (sfrt::ChainCaches& c : caches) hit_only ? c.release_hit(free_now) : c.release_all(free_now);
+    for (sfrt::ChainCaches& c : caches) {
+      if (texel_only) c.release_texel(free_now);
+      else if (hit_only) c.release_hit(free_now);
+      else c.release_all(free_now);
+    }
     return SFRT_OK;
   }
 
@@ -916,7 +942,7 @@ int sfrt_world_set_option(sfrt_world* w, int option, int value) {
   }
   if (option == SFRT_OPT_HIT_CACHE_MB) {
     if (value < 0) return SFRT_E_INVALID;
-    if ((long long)value * 1000000ll < w->hit_bytes_held()) {
+    if ((long long)value * 1000000ll < w->hit_bytes_budgeted()) {
       sfrt::DeviceGuard g(w->device);
       const int rc = w->release_caches(true);
       if (rc) return rc;
@@ -924,6 +950,19 @@ int sfrt_world_set_option(sfrt_world* w, int option, int value) {
     if (value == 0)
       for (sfrt::ChainCaches& c : w->caches) c.invalidate_hit();
     w->hit_cache_mb = value;
+    return SFRT_OK;
+  }
+  if (option == SFRT_OPT_TEXEL_CACHE) {
+    if (value < 0) return SFRT_E_INVALID;
+    if (value == 0) {
+      if (w->texel_bytes_held() > 0) {
+        sfrt::DeviceGuard g(w->device);
+        const int rc = w->release_caches(false, true);
+        if (rc) return rc;
+      }
+      for (sfrt::ChainCaches& c : w->caches) c.invalidate_texel();
+    }
+    w->texel_cache = value ? 1 : 0;
     return SFRT_OK;
   }
   return SFRT_E_INVALID;
@@ -957,6 +996,15 @@ int sfrt_world_hit_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hit
   return SFRT_OK;
 }
 
+int sfrt_world_texel_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits, int64_t* bytes) {
+  if (!w || !fills || !hits || !bytes) return SFRT_E_INVALID;
+  std::lock_guard<std::mutex> lk(w->mu);
+  *fills = w->cache_stats.texel_fills;
+  *hits = w->cache_stats.texel_hits;
+  *bytes = w->texel_bytes_held();
+  return SFRT_OK;
+}
+
 int sfrt_world_tile_record_bytes(const sfrt_world* w, int64_t* bytes) {
   if (!w || !bytes) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
@@ -974,6 +1022,7 @@ int sfrt_world_get_option(const sfrt_world* w, int option, int* value) {
     case SFRT_OPT_SUPERSAMPLE: *value = 1 << w->ss; return SFRT_OK;
     case SFRT_OPT_RAY_CACHE_MB: *value = w->ray_cache_mb; return SFRT_OK;
     case SFRT_OPT_HIT_CACHE_MB: *value = w->hit_cache_mb; return SFRT_OK;
+    case SFRT_OPT_TEXEL_CACHE: *value = w->texel_cache; return SFRT_OK;
     default: return SFRT_E_INVALID;
   }
 }
@@ -1589,7 +1638,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 14; }
+int sfrt_version(void) { return 15; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

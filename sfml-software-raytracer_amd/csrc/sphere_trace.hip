@@ -543,6 +543,60 @@ __device__ __forceinline__ bool hit_load(const HitRec* __restrict__ hr, int tile
   return moving;
 }
 
+// The texel cache (sfrt_raycache.h TexelRec; DESIGN.md 5 "Texel cache"): what shade_texel leaves a
+// ray once the drawn record's texture offset and size have entered -- the texel's index in the
+// atlas (or the sentinel: outside) and the brightness with the moving bit in its sign --
+// [tile][r][lane] like the hit records.  Stored by the _tf kernels (k_shade_hits that run once per
+// TexKey; one 8-byte store per ray slot, 512 B contiguous per wave), loaded by k_shade_texels.
+// hit_load_w: hit_load with each record's fourth dword as stored, the moving bit per ray.
+template <int R>
+__device__ __forceinline__ bool hit_load_w(const HitRec* __restrict__ hr, int tile, int lane,
+                                           float (&fu)[R], float (&fw)[R], float (&br)[R],
+                                           int (&draw)[R], uint32_t (&w)[R]) {
+  uint4 v[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) v[r] = *(const uint4*)(hr + hit_rec_at(tile, R, r, lane));
+  bool moving = false;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    fu[r] = __uint_as_float(v[r].x);
+    fw[r] = __uint_as_float(v[r].y);
+    br[r] = __uint_as_float(v[r].z);
+    draw[r] = hit_draw(v[r].w);
+    w[r] = v[r].w;
+    moving = moving || hit_moving(v[r].w);
+  }
+  return moving;
+}
+template <int R>
+__device__ __forceinline__ void texel_store(TexelRec* __restrict__ xr, int tile, int lane,
+                                            const Shading (&sh)[R], const uint32_t (&hw)[R]) {
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    uint2 v;
+    v.x = texel_pack_tex(sh[r].tex, sh[r].outside);
+    v.y = texel_pack_bright(__float_as_uint(sh[r].brightness), hit_moving(hw[r]));
+    *(uint2*)(xr + hit_rec_at(tile, R, r, lane)) = v;
+  }
+}
+// tex: the records' first dwords as stored (the sentinel included); br: the brightness, bit 31
+// cleared.  Returns whether some ray of the lane still moved at the guard.
+template <int R>
+__device__ __forceinline__ bool texel_load(const TexelRec* __restrict__ xr, int tile, int lane,
+                                           int (&tex)[R], float (&br)[R]) {
+  uint2 v[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) v[r] = *(const uint2*)(xr + hit_rec_at(tile, R, r, lane));
+  bool moving = false;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    tex[r] = (int)v[r].x;
+    br[r] = __uint_as_float(texel_bright_bits(v[r].y));
+    moving = moving || texel_moving(v[r].y);
+  }
+  return moving;
+}
+
 // L = +0 for a lane's R rays at the start of a march step, two registers per
 // v_mov_b64 (left to itself the compiler copies one zero register into three
 // others and then pairs them: five moves a step for R = 4, not two).
@@ -858,7 +912,14 @@ __device__ __forceinline__ Rays<R> march_wave(const FrameRec& f, const SphereRec
 // the texture-independent part of the tail, of the drawn records only tex_off and tex_wh, then
 // the rest of the same tail (shade_texel's FRAC): it is this function's, so there is one copy of
 // it and the marching kernels' code cannot move when the reading kernels change.  A ray that
-// still moved at the guard raises status bit 0 again.
+// still moved at the guard raises status bit 0 again;
+// 3, the _tf kernels (DESIGN.md 5 "Texel cache") -- 2, which also stores, after shade_texel, each
+// lane's texel record in the chain's texel cache xr (texel_store): the texel's index in the atlas
+// or the sentinel, and the brightness with the record's moving bit in its sign;
+// 4, k_shade_texels -- 2 with the rays' texel records loaded from xr in place of the hit records:
+// no SphereRec is read and shade_texel is not entered, the index is the one it left; then the
+// same texel loads, shade_rgba, box filter and stores.  Status bit 0 comes from the moving bits,
+// bit 2 from the sentinel of a valid lane.
 // PLACE (sfrt_world_render_subset): the subset goes in place into a whole frame --
 // compact column a (output pixel a >> SS) is stored xstride elements apart, the host having put
 // the subset's first pixel into f.out and yadd frame rows into f.out_pitch (the planes' pitches
@@ -874,7 +935,11 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
                                                     [[maybe_unused]] int xstride = 1,
                                                     [[maybe_unused]] const CullRec* cr = nullptr,
                                                     [[maybe_unused]] const CullLane<LIST>* cw = nullptr,
-                                                    [[maybe_unused]] HitRec* hr = nullptr) {
+                                                    [[maybe_unused]] HitRec* hr = nullptr,
+                                                    [[maybe_unused]] TexelRec* xr = nullptr) {
+  // the launches that march nothing: 2 and 3 shade from the hit records, 4 from the texel records
+  constexpr bool READS = HIT >= 2;
+  static_assert(HIT >= 0 && HIT <= 4, "0, _hf, k_shade_hits, _tf, k_shade_texels");
   static_assert(!CULLED || CACHED, "the cull cache rides on the ray cache");
   static_assert(HIT == 0 || (CULLED && !DUMP && !AUX && !PLACE), "the hit cache rides on the cull cache");
   static_assert(!PLACE || (!DUMP && !CACHED), "the placing kernels compute their directions and dump nothing");
@@ -887,7 +952,7 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   // Adaptive tile order (sfrt_trace.h FrameRec): workgroup 0 may be the sorter.
   const int ntiles = f.tiles_x * ((f.sub_rows + kTile - 1) / kTile);
   int slot = (int)blockIdx.x;
-  if constexpr (HIT != 2) {
+  if constexpr (!READS) {
     if (f.prev_cost) {
       if (blockIdx.x == 0) {
         sort_tiles(f.prev_cost, ntiles, f.next_order, f.order_dilate != 0);
@@ -897,7 +962,7 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
     }
   }
   [[maybe_unused]] uint32_t cls;  // the tile's class in the order (sfrt_device.h slot_tile)
-  const int tile = HIT == 2 ? slot : slot_tile(f.tile_order, slot, ntiles, cls);
+  const int tile = READS ? slot : slot_tile(f.tile_order, slot, ntiles, cls);
   int tile_x, tile_y;
   [[maybe_unused]] TileRec trec;
   [[maybe_unused]] CullRec crec;
@@ -925,8 +990,15 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   const float l0 = f.first_l;
   Rays<R> ray;  // iters: DUMP and AUX only, the host's first trip included
   uint64_t m_end = 0;  // the wave's culling mask, for the probe's tile_end
-  [[maybe_unused]] uint32_t hit_w[HIT == 1 ? R : 1];
-  if constexpr (HIT == 2) {
+  [[maybe_unused]] uint32_t hit_w[(HIT == 1 || HIT == 3) ? R : 1];
+  if constexpr (HIT == 4) {
+    // ray.draw holds the records' texel indices from here on, ray.pz the brightness
+    const bool moving = texel_load<R>(xr, tile, lane, ray.draw, ray.pz);
+    if (__builtin_amdgcn_ballot_w64(moving) != 0 && lane == 0) atomicOr(f.status, 1);
+  } else if constexpr (HIT == 3) {
+    const bool moving = hit_load_w<R>(hr, tile, lane, ray.px, ray.py, ray.pz, ray.draw, hit_w);
+    if (__builtin_amdgcn_ballot_w64(moving) != 0 && lane == 0) atomicOr(f.status, 1);
+  } else if constexpr (HIT == 2) {
     // every lane, clamped duplicates included: a duplicate is some stored pixel's ray again, so
     // "some ray of the wave still moved" is what march_wave's own test saw.  ray.px, py, pz hold
     // the records' fu, fw and brightness from here on (shade_texel's FRAC), not a position.
@@ -994,8 +1066,8 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
     }
     m_end = m;
   }
-  const int trips = HIT == 2 ? 0 : ray.trips;  // (2: no march; `ray` holds the loaded results only)
-  if constexpr (HIT != 2) {
+  const int trips = READS ? 0 : ray.trips;  // (no march; `ray` holds the loaded results only)
+  if constexpr (!READS) {
     if (f.tile_cost && lane == 0) store_cost(f.tile_cost, tile, tile_bucket((uint32_t)trips), cls, f.cost_diff);
   }
   // Pixel (a, b) of ray r, recomputed here from a fresh lane id (mbcnt, so that the
@@ -1035,17 +1107,27 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
     // Shading: the R records gathered first, then the R texel indices, the R texel
     // loads back to back, and the stores.  Edge lanes shade their duplicates too
     // (same values as the real pixel) and store nothing.
-    SphereRec d[R];
+    [[maybe_unused]] SphereRec d[HIT == 4 ? 1 : R];
+    if constexpr (HIT != 4) {
 #pragma unroll
-    for (int r = 0; r < R; r++)  // draw < n <= 1024: a 32-bit byte offset from the records' base
-      d[r] = *(const SphereRec*)((const char*)sph + (uint32_t)ray.draw[r] * (uint32_t)sizeof(SphereRec));
+      for (int r = 0; r < R; r++)  // draw < n <= 1024: a 32-bit byte offset from the records' base
+        d[r] = *(const SphereRec*)((const char*)sph + (uint32_t)ray.draw[r] * (uint32_t)sizeof(SphereRec));
+    }
     Shading sh[R];
     PixelDump dl[DUMP ? R : 1];
 #pragma unroll
-    for (int r = 0; r < R; r++)
-      sh[r] = shade_texel<P, AUX, false, HIT == 2>(f, d[r], ray.px[r], ray.py[r], ray.pz[r], DUMP ? &dl[DUMP ? r : 0] : nullptr);
+    for (int r = 0; r < R; r++) {
+      if constexpr (HIT == 4) {  // the texel record is what shade_texel left: no SphereRec is read
+        sh[r].outside = texel_outside((uint32_t)ray.draw[r]);
+        sh[r].tex = sh[r].outside ? 0u : (uint32_t)ray.draw[r];  // (some texel of the atlas; unused)
+        sh[r].brightness = ray.pz[r];
+      } else {
+        sh[r] = shade_texel<P, AUX, false, HIT == 2 || HIT == 3>(f, d[HIT == 4 ? 0 : r], ray.px[r], ray.py[r], ray.pz[r], DUMP ? &dl[DUMP ? r : 0] : nullptr);
+      }
+    }
     // every lane, clamped duplicates included, as the reading kernels load them
     if constexpr (HIT == 1) hit_store<R>(hr, tile, lane_s, sh, hit_w);
+    if constexpr (HIT == 3) texel_store<R>(xr, tile, lane_s, sh, hit_w);
     // AUX: ray r's plane values beside its colour store (plain vector stores)
     [[maybe_unused]] auto aux_store = [&](int r) {
       const int c = col_out(r);
@@ -1056,6 +1138,15 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
     uint32_t texel[R];
 #pragma unroll
     for (int r = 0; r < R; r++) texel[r] = f.tex[sh[r].tex];
+    // k_shade_texels<4, *>: all four texels before the first is used.  Left alone the compiler
+    // issues three loads here and sinks the first slot's into that slot's store branch, where
+    // the wave waits out a third memory trip (records, three texels, one texel); as one operand
+    // list the four are issued back to back and waited for once.  4K static 16.7 -> 15.8 us,
+    // 256 spheres 27.5 -> 26.6 (DESIGN.md 5 "Texel cache"); R < 4 was not tried and is left to
+    // the compiler.
+    if constexpr (HIT == 4 && R == 4) {
+      __asm__ volatile("" : "+v"(texel[0]), "+v"(texel[1]), "+v"(texel[2]), "+v"(texel[3]));
+    }
     if constexpr (SS > 0) {
       // Box filter, out_c = (sum of the S*S samples' c + S*S/2) >> log2(S*S) for each of the
       // four channels: every lane shades its sample (edge lanes their duplicates) with the
@@ -1266,6 +1357,32 @@ __global__ __launch_bounds__(64, 8) void k_shade_hits_list(FrameRec f, const Cul
                                                            const HitRec* __restrict__ hr) {
   trace_tile_window_r<R, true, false, NoProbe, SS, true, false, false, true, 2>(
       f, f.spheres, DumpArgs{}, nullptr, nullptr, AuxArgs{}, 1, cr, nullptr, const_cast<HitRec*>(hr));
+}
+
+// The texel cache's kernels (sfrt_raycache.h TexelRec, ChainCaches).  The _tf kernels are
+// k_shade_hits[_list] that also store each lane's texel record after shade_texel (HIT = 3; once per
+// TexKey, so their occupancy is left to the compiler); k_shade_texels shades a frame from those
+// records (HIT = 4): per ray one 8-byte load, the texel, shade_rgba, the store.  It reads no
+// SphereRec, so it takes the frame record alone whatever n is and has no _list twin.
+template <int R, int SS>
+__global__ __launch_bounds__(64) void k_shade_hits_tf(InlineArgs args, const CullRec* cr,
+                                                      const HitRec* __restrict__ hr,
+                                                      TexelRec* __restrict__ xr) {
+  trace_tile_window_r<R, false, false, NoProbe, SS, true, false, false, true, 3>(
+      args.f, args.s, DumpArgs{}, nullptr, nullptr, AuxArgs{}, 1, cr, nullptr, const_cast<HitRec*>(hr), xr);
+}
+template <int R, int SS>
+__global__ __launch_bounds__(64) void k_shade_hits_list_tf(FrameRec f, const CullRec* cr,
+                                                           const HitRec* __restrict__ hr,
+                                                           TexelRec* __restrict__ xr) {
+  trace_tile_window_r<R, true, false, NoProbe, SS, true, false, false, true, 3>(
+      f, f.spheres, DumpArgs{}, nullptr, nullptr, AuxArgs{}, 1, cr, nullptr, const_cast<HitRec*>(hr), xr);
+}
+template <int R, int SS>
+__global__ __launch_bounds__(64, 8) void k_shade_texels(FrameRec f, const CullRec* cr,
+                                                        const TexelRec* __restrict__ xr) {
+  trace_tile_window_r<R, false, false, NoProbe, SS, true, false, false, true, 4>(
+      f, nullptr, DumpArgs{}, nullptr, nullptr, AuxArgs{}, 1, cr, nullptr, nullptr, const_cast<TexelRec*>(xr));
 }
 
 // The DUMP instantiations of both (sfrt_world_trace_points): the shipped march and
@@ -1612,9 +1729,13 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
   const CullRec* const cull_recs = c.cull_recs;
   const void* const cull_wins = c.cull_wins;
   HitRec* const hit_recs = c.hit_recs;
+  TexelRec* const texel_recs = c.texel_recs;
   const int hit_mode = c.hit == RayAction::kRead ? 2 : c.hit == RayAction::kFill ? 1 : 0;
+  // the texel cache rides on a launch that reads the hit cache: 1 also stores it, 2 shades from it
+  const int texel_mode = c.texel == RayAction::kRead ? 2 : c.texel == RayAction::kFill ? 1 : 0;
   // the hit cache rides on the cull cache: 1 fills it from the marching launch, 2 shades from it
   if (hit_mode < 0 || hit_mode > 2 || (hit_mode != 0) != (hit_recs != nullptr)) return -1;
+  if ((texel_mode != 0) != (texel_recs != nullptr) || (texel_mode && hit_mode != 2)) return -1;
   if (hit_mode && (!cull_recs || dump || aux || place_xstride || kDiagnosticBuild)) return -1;
   // (2: the caller linked nothing of the tile order into f, but the grid is the ordered one)
   const bool ordered = hit_mode == 2 || f.tile_cost != nullptr;  // linked into the tile-order chain
@@ -1674,6 +1795,12 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                   : inl(k_trace_place_r<R, SS, false>, no_planes, place_xstride);
       } else if (aux) {
         list ? lst(k_trace_window_list_aux<R, SS>, *aux) : inl(k_trace_window_r_aux<R, SS>, *aux);
+      } else if (texel_mode == 2) {
+        list ? lst(k_shade_texels<R, SS>, cull_recs, (const TexelRec*)texel_recs)
+             : lst_no_event(k_shade_texels<R, SS>, cull_recs, (const TexelRec*)texel_recs);
+      } else if (texel_mode == 1) {
+        list ? lst(k_shade_hits_list_tf<R, SS>, cull_recs, (const HitRec*)hit_recs, texel_recs)
+             : inl(k_shade_hits_tf<R, SS>, cull_recs, (const HitRec*)hit_recs, texel_recs);
       } else if (hit_mode == 2) {
         list ? lst(k_shade_hits_list<R, SS>, cull_recs, (const HitRec*)hit_recs)
              : inl(k_shade_hits<R, SS>, cull_recs, (const HitRec*)hit_recs);

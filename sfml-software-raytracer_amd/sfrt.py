@@ -26,6 +26,7 @@ SFRT_OPT_TILE_ORDER = 3
 SFRT_OPT_SUPERSAMPLE = 4  # 1 (default), 2 or 4: S x S samples per pixel, box-filtered in the kernel
 SFRT_OPT_RAY_CACHE_MB = 5  # MiB per world for cached primary ray directions (512 default, 0 off)
 SFRT_OPT_HIT_CACHE_MB = 6  # MB (10^6 B) per world for cached march results, a budget of its own (512, 0 off)
+SFRT_OPT_TEXEL_CACHE = 7  # the texel cache on the hit cache, under the hit cache's budget (1 default, 0 off)
 ERRORS = {
     0: "SFRT_OK", -1: "SFRT_E_INVALID", -2: "SFRT_E_EMPTY", -3: "SFRT_E_NO_TEXTURE",
     -4: "SFRT_E_TOO_MANY", -5: "SFRT_E_HIP", -6: "SFRT_E_MARCH_LIMIT", -7: "SFRT_E_TEXEL",
@@ -74,6 +75,7 @@ ABI_SYMBOLS = (
     "sfrt_world_render_views", "sfrt_world_render_views_aux",
     "sfrt_world_cull_cache_stats", "sfrt_world_hit_cache_stats",
     "sfrt_voxel_render_views", "sfrt_voxel_render_views_aux", "sfrt_voxel_sort_dynamics",
+    "sfrt_world_texel_cache_stats",
 )
 
 SFRT_MAX_VIEWS = 1024
@@ -217,6 +219,8 @@ def lib() -> ctypes.CDLL:
                                          P(ctypes.c_int64)], c_int),
         "sfrt_world_hit_cache_stats": ([W, P(ctypes.c_int64), P(ctypes.c_int64),
                                         P(ctypes.c_int64)], c_int),
+        "sfrt_world_texel_cache_stats": ([W, P(ctypes.c_int64), P(ctypes.c_int64),
+                                          P(ctypes.c_int64)], c_int),
         "sfrt_world_submit_frame": ([W, vp, P(ctypes.c_int64)], c_int),
         "sfrt_world_wait_frame": ([W, ctypes.c_int64], c_int),
         "sfrt_host_alloc": ([P(vp), ctypes.c_int64], c_int),
@@ -510,6 +514,15 @@ class World:
         f, h, b = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         _check(lib().sfrt_world_hit_cache_stats(self._h, ctypes.byref(f), ctypes.byref(h),
                                                 ctypes.byref(b)), "hit_cache_stats")
+        return {"fills": f.value, "hits": h.value, "bytes": b.value}
+
+    def texel_cache_stats(self) -> dict:
+        """The texel cache's counters (sfrt_world_texel_cache_stats): launches that shaded from the
+        hit cache and stored their texel indices, launches that shaded from stored indices, and the
+        device bytes the texel caches hold now."""
+        f, h, b = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().sfrt_world_texel_cache_stats(self._h, ctypes.byref(f), ctypes.byref(h),
+                                                  ctypes.byref(b)), "texel_cache_stats")
         return {"fills": f.value, "hits": h.value, "bytes": b.value}
 
     def set_scene(self, scene, width: int, height: int) -> None:
