@@ -18,6 +18,11 @@ tests use, every frame against the CPU restatement byte for byte --
 
 * the multi-GPU object (sfrt_multi): N / 10 sphere scenes over 2-4 ranks on cuda:0.
 
+* the sphere kernel families (test_sphere_family_sweep, recorded as "sphere_families"): the checks
+  of tests/test_sphere_family_fuzz.py -- planes, supersampling, subsets in place, view batches,
+  ray batches, the caches at rest and under one step -- on N sphere scenes at the short ragged
+  sizes of tests/sphere_fuzz_cases.py (SFRT_PARITY_SWEEP_SIZE does not apply).
+
 Every fifth scene is drawn as 2-4 random row bands (global row indices, as the multi-GPU bands).
 SFRT_PARITY_SWEEP_MODE=adversarial pushes each generator to its degenerate corners;
 SFRT_PARITY_SWEEP_SIZE=WxH draws every scene at that size.  The summary (scenes, pixels and
@@ -237,6 +242,89 @@ def test_sphere_sweep(built, floor):
             pixels += w * h
             _progress("sphere", seed - SEED0 + 1, bad)
     _record("sphere", N, pixels, bad)
+    assert not bad, bad[:3]
+
+
+def _march_lengths(seed):
+    """sphere_fuzz_cases.march_lengths of a sweep scene, from a child process under a time limit
+    (the oracle's march has no guard of its own); None if it did not end in time."""
+    import subprocess
+    import sys
+    cmd = [sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "sphere_fuzz_cases.py"),
+           MODE, str(seed), str(seed - SEED0)]
+    try:
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=120)
+    except subprocess.TimeoutExpired:
+        return None
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads(r.stdout.splitlines()[-1])
+
+
+def _gpu_reaches_the_guard(fam, c):
+    """Whether the case's own frame at 1, 2x2 or 4x4 samples ends in SFRT_E_MARCH_LIMIT."""
+    import sfrt
+    for s in (1, 2, 4):
+        with fam._world(c, s) as w:
+            try:
+                w.render()
+            except sfrt.SfrtError as e:
+                if e.code != -6:  # SFRT_E_MARCH_LIMIT
+                    raise
+                return True
+    return False
+
+
+def test_sphere_family_sweep(built):
+    """tests/test_sphere_family_fuzz.py's family checks (planes, supersampling, subsets in place,
+    views, ray batches, the caches at rest and under one step) over N consecutive seeds of
+    `_fuzz_scene` or `_sphere_adversarial` (SFRT_PARITY_SWEEP_MODE), at the short size list of
+    tests/sphere_fuzz_cases.py, each scene borrowing the next four seeds' cameras.  A scene for
+    which the oracle reaches the kernels' march guard is skipped when the library reports the
+    guard as well, and a mismatch when it does not."""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    import sfrt
+    import sphere_fuzz_cases as fuzz
+    import test_sphere_family_fuzz as fam
+    seed0 = SEED0 - (100000 if SIZE else 0)  # the frame sizes here are the short list's
+    t0 = time.time()
+    bad, pixels, skipped, borrowed = [], 0, 0, 0
+    seeds = range(seed0, seed0 + N)
+    with ThreadPoolExecutor(8) as pool:
+        for seed, lengths in zip(seeds, pool.map(_march_lengths, seeds)):
+            index = seed - seed0
+            case = fuzz.make_case(MODE, fuzz.generated(MODE, seed), index)
+            c = fam.Ctx(case, index, [fuzz.generated(MODE, seed + q) for q in range(1, 5)])
+            if lengths is None or max(lengths.values()) >= fuzz.MARCH_GUARD:
+                own = lengths is None or max(v for k, v in lengths.items() if k.startswith("own")) \
+                    >= fuzz.MARCH_GUARD
+                if _gpu_reaches_the_guard(fam, c):
+                    skipped += 1
+                elif own:
+                    bad.append({"seed": seed, "oracle": "march cap", "library": "none"})
+                else:
+                    borrowed += 1  # a borrowed camera's march: no defined frame to compare
+                continue
+            checks = dict(fam.FAMILIES)
+            if index % 4 == 0:
+                checks["caches 2x2"] = lambda ctx: fam.check_caches(ctx, 2)
+            for name, check in checks.items():
+                try:
+                    check(c)
+                except AssertionError as e:
+                    bad.append({"seed": seed, "family": name, "diff": str(e)[:300]})
+                except sfrt.SfrtError as e:  # nothing more runs on a device that reported an error
+                    bad.append({"seed": seed, "family": name, "error": str(e)})
+                    _record("sphere_families", index + 1, pixels, bad, skipped)
+                    raise
+            pixels += case.width * case.height
+            _progress("sphere families", index + 1, bad)
+    _record("sphere_families", N, pixels, bad, skipped)
+    RESULTS["sphere_families"].update(
+        families=list(fam.FAMILIES), sizes=["%dx%d" % s for s in fuzz.SIZES], first_seed=seed0,
+        share_skipped_march_cap_both_sides=skipped / N,
+        skipped_march_cap_in_a_borrowed_view=borrowed, wall_s=round(time.time() - t0, 1))
+    _record_flush()
     assert not bad, bad[:3]
 
 

@@ -75,6 +75,11 @@ class Trio:
             assert np.array_equal(frame, other), (what, name)
         assert got == 0, (what, got)
         assert np.array_equal(frame, self.r.want()), what
+        self.counted(what, launch)
+        return frame
+
+    def counted(self, what, launch):
+        """The counters of the three worlds after a frame whose first world's launch was `launch`."""
         if launch == HIT_FILL:
             self.hfills += 1
             self.hheld, self.theld = self.r.hit_bytes(), 0  # a hit refill frees the texel records
@@ -88,7 +93,6 @@ class Trio:
         assert self.tstats(self.r) == (self.tfills, self.thits, self.theld), (what, launch)
         assert self.m.hstats() == (0, 0, 0) and self.tstats(self.m) == (0, 0, 0), what
         assert self.tstats(self.h) == (0, 0, 0), what
-        return frame
 
     def frames(self, what, *launches):
         return [self.frame(f"{what}, frame {k + 1}", launch) for k, launch in enumerate(launches)]
