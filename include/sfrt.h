@@ -407,7 +407,24 @@ SFRT_API int sfrt_world_cast_rays(sfrt_world* w, const float* dirs, const float*
  * SFRT_OPT_HIT_CACHE_MB beside the hit cache's (two 4K streams: 2 x (132.7 + 66.4) = 398 MB);
  * where they do not fit, launches stay on the hit cache.  Whatever drops or refills the hit cache
  * drops the texel cache; setting the option to 0 waits for the device and frees the texel caches
- * only.  See sfrt_world_texel_cache_stats. */
+ * only.  See sfrt_world_texel_cache_stats.
+ * SFRT_OPT_COMPACT_TEXELS (1 = default; 0 = off; 2 = every eligible launch; other values return
+ * SFRT_E_INVALID): the compact layer on top of the texel cache.  At 1 it serves the launches it was
+ * measured to pay for by the project's rule -- four pixels per lane (frames of about 4K and more)
+ * with at most 64 spheres -- and at 2 also the others (smaller frames, more spheres: a gain of 4 to
+ * 11 % that the rule did not confirm).  A pixel's bytes depend on the brightness only through
+ * the 256 products with a channel byte, so the brightness can be replaced by one of 20,229 classes
+ * (15 bits) without changing a byte; while no sphere's texture ends beyond texel 65,535 of the
+ * atlas and the world is not supersampled, the second consecutive launch that reads the texel
+ * cache also writes each ray as 4 bytes (33.2 MB for a 4K frame) and later launches read those in
+ * place of the 8: the same bytes and the same status.  The bytes count against
+ * SFRT_OPT_HIT_CACHE_MB after the hit and texel caches have theirs; where they do not fit, or the
+ * atlas is larger, launches stay on the texel cache, which stays allocated either way.  Whatever
+ * drops or refills the texel cache of a stream drops its compact layer first, so within a stream
+ * the layer never keeps a lower one from filling; between streams its bytes count like any others
+ * under the limit (two 4K streams hold 2 x 232 MB of 512: a third stream's caches may find less
+ * room than without the layer -- raise the limit or set this option to 0 there).  Lowering the
+ * option waits for the device and frees that layer only.  See sfrt_world_compact_cache_stats. */
 #define SFRT_OPT_CULL 1
 #define SFRT_OPT_RAYS_PER_LANE 2
 #define SFRT_OPT_TILE_ORDER 3
@@ -415,6 +432,7 @@ SFRT_API int sfrt_world_cast_rays(sfrt_world* w, const float* dirs, const float*
 #define SFRT_OPT_RAY_CACHE_MB 5
 #define SFRT_OPT_HIT_CACHE_MB 6
 #define SFRT_OPT_TEXEL_CACHE 7
+#define SFRT_OPT_COMPACT_TEXELS 8
 SFRT_API int sfrt_world_set_option(sfrt_world* w, int option, int value);
 /* The current value of any of the options above (SFRT_OPT_SUPERSAMPLE: the factor 1, 2 or 4). */
 SFRT_API int sfrt_world_get_option(const sfrt_world* w, int option, int* value);
@@ -447,6 +465,13 @@ SFRT_API int sfrt_world_hit_cache_stats(const sfrt_world* w, int64_t* fills, int
  * SFRT_OPT_HIT_CACHE_MB, not part of sfrt_world_hit_cache_stats' bytes. */
 SFRT_API int sfrt_world_texel_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits,
                                           int64_t* bytes);
+/* The compact layer's counters since the world was created (SFRT_OPT_COMPACT_TEXELS): *fills =
+ * launches that shaded from the texel cache and stored their 4-byte records, *hits = launches that
+ * shaded from those (each also counts as a hit of sfrt_world_texel_cache_stats and of the caches
+ * under it), *bytes = device memory the world's compact records hold now.  Counted against
+ * SFRT_OPT_HIT_CACHE_MB, not part of the other caches' bytes. */
+SFRT_API int sfrt_world_compact_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits,
+                                            int64_t* bytes);
 
 /* ---- stateless helpers ---- */
 /* UpdateSpheres ordering of an array in place (SphereWorld.cpp:199-212). */

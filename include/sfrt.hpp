@@ -324,6 +324,17 @@ class SphereWorld {
     check(sfrt_world_texel_cache_stats(w_, &s.fills, &s.hits, &s.bytes), "texel_cache_stats");
     return s;
   }
+  // SFRT_OPT_COMPACT_TEXELS (sfrt.h): the 4-byte compact layer on the texel cache; 0 = off, 1 = the
+  // launches it was proven at (default), 2 = every eligible launch.
+  void SetCompactTexels(int mode) { SetOption(SFRT_OPT_COMPACT_TEXELS, mode); }
+  int CompactTexels() const { return GetOption(SFRT_OPT_COMPACT_TEXELS); }
+  // The compact layer's counters (sfrt.h sfrt_world_compact_cache_stats).
+  using CompactCacheStats = CullCacheStats;  // the same three counters
+  CompactCacheStats GetCompactCacheStats() const {
+    CompactCacheStats s{};
+    check(sfrt_world_compact_cache_stats(w_, &s.fills, &s.hits, &s.bytes), "compact_cache_stats");
+    return s;
+  }
   sfrt_world* handle() { return w_; }
 
  private:

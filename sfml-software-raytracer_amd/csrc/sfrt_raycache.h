@@ -9,14 +9,17 @@
 // that, under the same key, the hit cache (HitRec: what each ray's march leaves the shading).
 // On the hit cache rides the texel cache (TexKey, TexelRec: the texel index and the brightness
 // the shading is left with once the texture sizes and slots stand still too).
-// One policy (CacheLayer) decides for each of the four; one object per chain (ChainCaches, at
-// the end) owns the layers, their six buffers and the order in which a launch decides, fills
+// On the texel cache rides the compact layer (CompactRec: the same ray in 4 bytes while the atlas
+// is small enough, the brightness as its class in a table of binary32 constants).
+// One policy (CacheLayer) decides for each of the five; one object per chain (ChainCaches, at
+// the end) owns the layers, their seven buffers and the order in which a launch decides, fills
 // and drops them.  This header makes no HIP call -- the device is a parameter of
 // ChainCaches::begin -- so all of it is tested on the host as it ships: tests/native/
 // raycache_check.cpp (the layer), tilerec_check.cpp, cullcache_check.cpp, hitcache_check.cpp,
-// texelcache_check.cpp (the chain, through counting allocators).
+// texelcache_check.cpp, compactrec_check.cpp (the chain, through counting allocators).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <initializer_list>
@@ -312,6 +315,142 @@ struct TexKey {
   bool same(const TexKey& o) const { return tex == o.tex && cull.same(o.cull); }
 };
 
+// ---- The compact layer (DESIGN.md 5 "Compact layer") ----
+//
+// A TexelRec holds more than a pixel needs.  shade_rgba uses the brightness b only in
+// cvt_u32(float(c) * b) for the three channel bytes c in 0..255; each is monotone in b, and b is
+// 3 / max(bl, 3): in [+0, 1] or NaN, a NaN giving 0 for every c as b = 0 does.  Two brightnesses
+// with the same 256 results are interchangeable byte for byte under every texel, and the classes
+// are intervals of b: their lower ends are, for c in 1..255 and k in 1..c, the smallest binary32 t
+// with cvt_u32(fl(c * t)) >= k -- at most 32,640 of them, 20,228 distinct in binary32 (thresholds
+// k/c and 2k/2c that rounding splits by an ulp included), so a class fits 15 bits.  With an atlas
+// of at most 0xffff texels the index fits 16, and a ray fits one dword.
+//
+// Per ray one 4-byte record, [tile][lane][r] -- the reading kernel's lane owns R consecutive
+// pixels of one row (sphere_trace.hip k_shade_compact) and loads its R records with one access --
+// every slot written, clamped duplicates included.
+//   bits 0-15: Shading::tex, or kCompactOutside where the index fell outside the texture
+//   bits 16-30: the brightness' class (BrightClasses::class_of)
+//   bit 31: kTexelRecMoving's meaning
+struct CompactRec {
+  uint32_t w;
+};
+static_assert(sizeof(CompactRec) == 4 && alignof(CompactRec) == 4, "one dword per ray");
+constexpr uint32_t kCompactOutside = 0xffffu;
+constexpr uint32_t kCompactMoving = 0x80000000u;
+constexpr uint32_t kCompactClassLimit = 1u << 15;  // classes a record can name
+
+#if defined(__HIP__)
+#define SFRT_COMPACT_HD __host__ __device__ __forceinline__
+#else
+#define SFRT_COMPACT_HD inline
+#endif
+SFRT_COMPACT_HD uint32_t compact_pack(uint32_t tex, bool outside, uint32_t cls, bool moving) {
+  return (outside ? kCompactOutside : (tex & 0xffffu)) | ((cls & (kCompactClassLimit - 1u)) << 16) |
+         (moving ? kCompactMoving : 0u);
+}
+SFRT_COMPACT_HD uint32_t compact_tex(uint32_t w) { return w & 0xffffu; }
+SFRT_COMPACT_HD bool compact_outside(uint32_t w) { return (w & 0xffffu) == kCompactOutside; }
+SFRT_COMPACT_HD uint32_t compact_class(uint32_t w) { return (w >> 16) & (kCompactClassLimit - 1u); }
+SFRT_COMPACT_HD bool compact_moving(uint32_t w) { return (w & kCompactMoving) != 0; }
+SFRT_COMPACT_HD size_t compact_rec_at(int tile, int rays, int lane, int r) {
+  return ((size_t)tile * 64u + (size_t)lane) * (size_t)rays + (size_t)r;
+}
+// The class of a brightness, given as its binary32 bits with bit 31 clear, in the table rep[0 ..
+// classes): 0 for a NaN, else the number of thresholds rep[1 .. classes) that are <= b.  Unsigned
+// compares of the bit patterns, exact because b >= +0; fifteen steps whatever the table's size
+// (classes <= kCompactClassLimit).  The device searches the uploaded table with this very function:
+// no arithmetic decides a class.
+SFRT_COMPACT_HD uint32_t bright_class_of(const uint32_t* rep, uint32_t classes, uint32_t b) {
+  if (b > 0x7f800000u) return 0u;  // NaN (the sign is not part of b)
+  uint32_t cls = 0;                // rep[0] = +0 <= b
+  for (uint32_t step = kCompactClassLimit >> 1; step; step >>= 1) {
+    const uint32_t m = cls + step;
+    if (m < classes && rep[m] <= b) cls = m;
+  }
+  return cls;
+}
+#undef SFRT_COMPACT_HD
+
+inline long long compact_cache_bytes(long long tiles, int rays) {
+  return tiles * rays * 64 * (long long)sizeof(CompactRec);
+}
+// Whether every texel index of an atlas of `texels` texels stays below kCompactOutside.
+inline bool compact_index_fits(unsigned long long texels) { return texels <= 0xffffull; }
+// The largest tex_off + tw * th over records recs[0..count) (any struct with SphereRec's members):
+// one past the last texel index a ray of the launch can be left with.  A function of the TexKey's
+// fields, computed where the key is made.
+template <class Rec>
+unsigned long long compact_texel_end(const Rec* recs, int count) {
+  unsigned long long end = 0;
+  for (int k = 0; k < count; k++) {
+    const unsigned long long e = (unsigned long long)recs[k].tex_off +
+                                 (unsigned long long)(recs[k].tex_wh & 0xffffu) * (recs[k].tex_wh >> 16);
+    if (e > end) end = e;
+  }
+  return end;
+}
+// The layer's own eligibility condition: no supersampling (ss: log2 of the factor) and every index
+// in 16 bits.
+template <class Rec>
+bool compact_eligible(const Rec* recs, int count, int ss) {
+  return ss == 0 && compact_index_fits(compact_texel_end(recs, count));
+}
+
+// shade_rgba's channel (sphere_trace.hip) on the host: one rounding for the product -- this header
+// is compiled with -ffp-contract=off wherever the result matters, and a lone product has nothing to
+// contract with -- then v_cvt_u32_f32: towards zero, 0 for a NaN.  b in [+0, 1] or NaN.
+inline uint32_t bright_channel(uint32_t c, float b) {
+  const volatile float p = (float)c * b;  // (volatile: binary32, not an x87 temporary)
+  return p != p ? 0u : (uint32_t)p;
+}
+inline uint32_t bright_shade_rgba(uint32_t texel, float b) {
+  return (bright_channel(texel & 0xffu, b) & 0xffu) | ((bright_channel((texel >> 8) & 0xffu, b) & 0xffu) << 8) |
+         ((bright_channel((texel >> 16) & 0xffu, b) & 0xffu) << 16) | (texel & 0xff000000u);
+}
+
+// The class table, a constant of binary32 arithmetic: rep[i] is class i's smallest brightness
+// (rep[0] = +0), as bit patterns, strictly increasing.  Built once per process.
+struct BrightClasses {
+  std::vector<uint32_t> rep;
+
+  static float from_bits(uint32_t u) {
+    float v;
+    std::memcpy(&v, &u, 4);
+    return v;
+  }
+  static BrightClasses make() {
+    BrightClasses t;
+    std::vector<uint32_t> thr;
+    thr.reserve(255 * 128);
+    for (uint32_t c = 1; c <= 255; c++) {
+      for (uint32_t k = 1; k <= c; k++) {
+        // the smallest t with cvt(fl(c * t)) >= k: positive floats order as their bits do
+        uint32_t u = ray_key_bits((float)k / (float)c);
+        while (bright_channel(c, from_bits(u)) < k) u++;
+        while (bright_channel(c, from_bits(u - 1)) >= k) u--;
+        thr.push_back(u);
+      }
+    }
+    std::sort(thr.begin(), thr.end());
+    thr.erase(std::unique(thr.begin(), thr.end()), thr.end());
+    t.rep.reserve(thr.size() + 1);
+    t.rep.push_back(0u);
+    t.rep.insert(t.rep.end(), thr.begin(), thr.end());
+    return t;
+  }
+  static const BrightClasses& get() {
+    static const BrightClasses t = make();
+    return t;
+  }
+  uint32_t classes() const { return (uint32_t)rep.size(); }
+  // a record can name every class (else the layer is never filled)
+  bool fits() const { return !rep.empty() && rep.size() < kCompactClassLimit; }
+  uint32_t class_of(float b) const {
+    return bright_class_of(rep.data(), classes(), ray_key_bits(b) & ~kCompactMoving);
+  }
+};
+
 // ---- One chain's caches (DESIGN.md 5 "The chain's caches") ----
 
 // What ChainCaches::begin decided for one launch and what that launch reads: launch_trace's cache
@@ -320,39 +459,52 @@ struct TraceCaches {
   bool decided = false;  // begin() made it: end() has something to commit
   RayAction ray = RayAction::kTrace, cull = RayAction::kTrace, hit = RayAction::kTrace;
   RayAction texel = RayAction::kTrace;  // kRead implies hit == kRead; kFill rides on a hit read
+  RayAction compact = RayAction::kTrace;  // kRead implies texel == kRead; kFill rides on a texel read
   const float* dirs = nullptr;
   const TileRec* tile_recs = nullptr;
   const CullRec* cull_recs = nullptr;
   const void* cull_wins = nullptr;  // CullWin or CullWinList
   HitRec* hit_recs = nullptr;       // written by a filling launch (hit == kFill), read by a reading one
   TexelRec* texel_recs = nullptr;   // likewise (a launch that reads them still gets hit_recs, unread)
+  CompactRec* compact_recs = nullptr;  // likewise (a launch that reads them still gets texel_recs, unread)
+  // the world's class table on the device (BrightClasses::rep), set by the caller of begin() for a
+  // launch whose compact action is not kTrace; readable up to kCompactClassLimit entries
+  const uint32_t* bright_rep = nullptr;
+  uint32_t bright_classes = 0;
   bool reading() const { return hit == RayAction::kRead; }  // no march: outside the tile order
 };
 
 struct CacheSizes {  // of one launch's grid: ray_cache_bytes, tile_rec_bytes, cull_*_bytes, hit_cache_bytes
   long long dirs = 0, tile_recs = 0, cull_recs = 0, cull_wins = 0, hit_recs = 0;
   long long texel_recs = 0;  // texel_cache_bytes (0: no texel layer)
+  long long compact_recs = 0;  // compact_cache_bytes (0: no compact layer, or the launch is not eligible)
 };
 
 struct CacheCounters {  // sfrt_world_{ray,cull,hit,texel}_cache_stats
   int64_t ray_cached_frames = 0, ray_fills = 0, cull_fills = 0, cull_hits = 0, hit_fills = 0, hit_hits = 0;
   int64_t texel_fills = 0, texel_hits = 0;
+  int64_t compact_fills = 0, compact_hits = 0;
 };
 
-// The four layers and the six buffers of one tile-order chain, and the one rule between them:
+// The five layers and the seven buffers of one tile-order chain, and the one rule between them:
 // an upper cache is never valid without the one under it.  A refill below drops what is above; a
-// failed fill drops its own layer and everything above it; a failed launch drops all four.
+// failed fill drops its own layer and everything above it; a failed launch drops all five.
 // The texel layer (TexKey) has no fill kernel of its own and is not filled by a marching launch:
 // only a launch that reads the hit layer fills it (the _tf kernels), and a launch that reads it
 // counts as a read of the three layers under it.
+// The compact layer (TexKey again; eligible: begin's compact_ok) likewise one step up: only a launch
+// that reads the texel layer fills it (k_shade_texels_cf), a launch that reads it counts as a read
+// of the four under it, and whatever drops or refills the texel layer frees its buffer first, so it
+// never takes room a lower layer could have had in this chain.
 struct ChainCaches {
   CacheLayer<RayKey> ray;
   CacheLayer<CullKey> cull, hit;
-  CacheLayer<TexKey> texel;
+  CacheLayer<TexKey> texel, compact;
   CacheBuf dirs, tile_recs;  // ray_cache_bytes, tile_rec_bytes: one layer, two buffers
   CacheBuf cull_recs, cull_wins;
   CacheBuf hit_recs;
   CacheBuf texel_recs;
+  CacheBuf compact_recs;
   RayKey ray_key{};  // begin() -> end(): the launch being queued
   CullKey cull_key;
   TexKey tex_key;
@@ -364,7 +516,8 @@ struct ChainCaches {
   long long bytes_under_ray_budget() const { return dirs.bytes + cull_bytes(); }
   long long hit_bytes() const { return hit_recs.bytes; }  // the hit records alone (the stats)
   long long texel_bytes() const { return texel_recs.bytes; }
-  long long bytes_under_hit_budget() const { return hit_recs.bytes + texel_recs.bytes; }
+  long long compact_bytes() const { return compact_recs.bytes; }
+  long long bytes_under_hit_budget() const { return hit_recs.bytes + texel_recs.bytes + compact_recs.bytes; }
   long long tile_rec_bytes() const { return tile_recs.bytes; }
 
   // Before a launch that takes part.  other_ray, other_hit: what the world's other chains hold
@@ -373,10 +526,12 @@ struct ChainCaches {
   // cull_recs, cull_wins) -> bool queue the fill kernels for this launch's frame.  A fill that
   // fails is no error of the frame: the launch runs what it would run without that cache.
   // tk: the launch's TexKey (tk->cull equal to ck), or null: no texel layer for this launch.
+  // compact_ok: the launch is eligible for the compact layer (the option, no supersampling, every
+  // texel index the records can name below kCompactOutside, a class table that fits).
   template <class Dev>
   TraceCaches begin(const RayKey& rk, const CullKey& ck, const CacheSizes& n, long long other_ray,
                     long long other_hit, long long ray_budget, long long hit_budget, Dev&& dev,
-                    const TexKey* tk = nullptr) {
+                    const TexKey* tk = nullptr, bool compact_ok = false) {
     const auto free_fn = [&dev](void* p) { return dev.free(p); };
     const auto reserve = [&](CacheBuf& b, long long m) {
       return b.reserve(m, free_fn, [&dev](long long q) { return dev.alloc(q); });
@@ -391,10 +546,11 @@ struct ChainCaches {
     if (d.ray == RayAction::kFill) {
       // The tile records are rewritten: what rides on them goes first and takes no room from the
       // directions.  have_prev stays, so this very launch can go on to fill all three.
-      for (CacheBuf* b : {&cull_recs, &cull_wins, &hit_recs, &texel_recs}) b->release(free_fn);
+      for (CacheBuf* b : {&cull_recs, &cull_wins, &hit_recs, &texel_recs, &compact_recs}) b->release(free_fn);
       cull.valid = false;
       hit.valid = false;
       texel.valid = false;
+      compact.valid = false;
       if (!reserve(dirs, n.dirs) || !reserve(tile_recs, n.tile_recs) ||
           !dev.fill_rays((float*)dirs.ptr, (TileRec*)tile_recs.ptr)) {
         invalidate();  // the buffers may be gone or half written
@@ -414,6 +570,7 @@ struct ChainCaches {
       cull.invalidate();  // the tile records are whole: the launch reads them
       hit.invalidate();
       texel.invalidate();
+      compact.invalidate();
       d.cull = RayAction::kTrace;
     }
     if (d.cull != RayAction::kTrace) {
@@ -426,11 +583,14 @@ struct ChainCaches {
     // are this chain's to reuse)
     d.hit = hit.decide(ck, d.cull, n.hit_recs, bytes_under_hit_budget(), other_hit, hit_budget);
     if (d.hit == RayAction::kFill) {
+      compact_recs.release(free_fn);
+      compact.valid = false;
       texel_recs.release(free_fn);
       texel.valid = false;
       if (!reserve(hit_recs, n.hit_recs)) {
         hit.invalidate();  // no memory for it: the launch stays on the cull-cache path
         texel.invalidate();
+        compact.invalidate();
         d.hit = RayAction::kTrace;
       }
     }
@@ -441,11 +601,28 @@ struct ChainCaches {
       d.texel = texel.decide(*tk, d.hit, n.texel_recs, texel_recs.bytes, other_hit + hit_recs.bytes,
                              hit_budget);
       if (d.texel == RayAction::kFill && d.hit != RayAction::kRead) d.texel = RayAction::kTrace;
-      if (d.texel == RayAction::kFill && !reserve(texel_recs, n.texel_recs)) {
-        texel.invalidate();  // no memory for it: the launch reads the hit layer
-        d.texel = RayAction::kTrace;
+      if (d.texel == RayAction::kFill) {
+        // (the compact records were made from the ones about to be rewritten: they go first, and
+        // the decision above did not count them)
+        compact_recs.release(free_fn);
+        compact.valid = false;
+        if (!reserve(texel_recs, n.texel_recs)) {
+          texel.invalidate();  // no memory for it: the launch reads the hit layer
+          compact.invalidate();
+          d.texel = RayAction::kTrace;
+        }
       }
       if (d.texel != RayAction::kTrace) d.texel_recs = (TexelRec*)texel_recs.ptr;
+      // The compact layer, on top of the texel layer and under the same budget, after the hit and
+      // texel records have theirs.  Only a launch that reads the texel layer fills it.
+      d.compact = compact.decide(*tk, d.texel, compact_ok ? n.compact_recs : 0, compact_recs.bytes,
+                                 other_hit + hit_recs.bytes + texel_recs.bytes, hit_budget);
+      if (d.compact == RayAction::kFill && d.texel != RayAction::kRead) d.compact = RayAction::kTrace;
+      if (d.compact == RayAction::kFill && !reserve(compact_recs, n.compact_recs)) {
+        compact.invalidate();  // no memory for it: the launch reads the texel layer
+        d.compact = RayAction::kTrace;
+      }
+      if (d.compact != RayAction::kTrace) d.compact_recs = (CompactRec*)compact_recs.ptr;
     }
     return d;
   }
@@ -461,8 +638,14 @@ struct ChainCaches {
     cull.commit(cull_key, d.cull, ray_filled);
     hit.commit(cull_key, d.hit, ray_filled || cull_filled);
     const bool hit_filled = d.hit == RayAction::kFill;
-    if (have_tex_key) texel.commit(tex_key, d.texel, ray_filled || cull_filled || hit_filled);
-    else if (ray_filled || cull_filled || hit_filled) texel.valid = false;
+    if (have_tex_key) {
+      texel.commit(tex_key, d.texel, ray_filled || cull_filled || hit_filled);
+      compact.commit(tex_key, d.compact,
+                     ray_filled || cull_filled || hit_filled || d.texel == RayAction::kFill);
+    } else if (ray_filled || cull_filled || hit_filled) {
+      texel.valid = false;
+      compact.valid = false;
+    }
     n.ray_fills += ray_filled;
     n.ray_cached_frames += d.ray != RayAction::kTrace;
     n.cull_fills += cull_filled;
@@ -471,6 +654,8 @@ struct ChainCaches {
     n.hit_hits += d.hit == RayAction::kRead;
     n.texel_fills += d.texel == RayAction::kFill;
     n.texel_hits += d.texel == RayAction::kRead;
+    n.compact_fills += d.compact == RayAction::kFill;
+    n.compact_hits += d.compact == RayAction::kRead;
   }
 
   void invalidate() {
@@ -478,28 +663,42 @@ struct ChainCaches {
     cull.invalidate();
     hit.invalidate();
     texel.invalidate();
+    compact.invalidate();
   }
   void invalidate_hit() {
     hit.invalidate();
     texel.invalidate();
+    compact.invalidate();
   }
-  void invalidate_texel() { texel.invalidate(); }
+  void invalidate_texel() {
+    texel.invalidate();
+    compact.invalidate();
+  }
+  void invalidate_compact() { compact.invalidate(); }
 
   // Freed by the host once the device has drained (an option lowered, the world going away).
   template <class Free>
   void release_hit(Free&& free_fn) {
+    compact_recs.release(free_fn);
     hit_recs.release(free_fn);
     texel_recs.release(free_fn);
     invalidate_hit();
   }
   template <class Free>
   void release_texel(Free&& free_fn) {
+    compact_recs.release(free_fn);
     texel_recs.release(free_fn);
-    texel.invalidate();
+    invalidate_texel();
+  }
+  template <class Free>
+  void release_compact(Free&& free_fn) {
+    compact_recs.release(free_fn);
+    compact.invalidate();
   }
   template <class Free>
   void release_all(Free&& free_fn) {
-    for (CacheBuf* b : {&dirs, &tile_recs, &cull_recs, &cull_wins, &hit_recs, &texel_recs}) b->release(free_fn);
+    for (CacheBuf* b : {&dirs, &tile_recs, &cull_recs, &cull_wins, &hit_recs, &texel_recs, &compact_recs})
+      b->release(free_fn);
     invalidate();
   }
 };

@@ -174,6 +174,8 @@ int launch_cast_rays(const FrameRec& f, const SphereRec* host_spheres, const Ray
 // march result; with hit == kRead: no march -- one wave per tile in tile-number order shades from
 // the records.  That launch takes no part in the tile order: f's tile_order, tile_cost, prev_cost
 // and next_order are ignored (the caller links nothing), and dirs and cull_wins are not read.
+// texel_recs and compact_recs ride on such a launch in the same way: kFill, it also stores them;
+// kRead, it shades from them (compact: with bright_rep, the world's class table, never with ss > 0).
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump = nullptr, void* done_event = nullptr,
                  const TraceCaches* caches = nullptr, const AuxArgs* aux = nullptr,

@@ -137,9 +137,15 @@ struct sfrt_world {
   int ray_cache_mb = 512;  // SFRT_OPT_RAY_CACHE_MB: MiB of ray caches over all chains (0: off)
   int hit_cache_mb = 512;  // SFRT_OPT_HIT_CACHE_MB: MB (10^6 bytes) of hit caches over all chains (0: off)
   int texel_cache = 1;     // SFRT_OPT_TEXEL_CACHE: the texel layer on the hit cache, under its budget (0: off)
+  // SFRT_OPT_COMPACT_TEXELS: the compact layer on the texel cache (0: off; 1: launches at four pixels
+  // per lane whose records travel in the arguments, the shape it was proven at; 2: every eligible one)
+  int compact_texels = 1;
   // --- device resources ---
   hipStream_t stream = nullptr;
   uint32_t* d_tex = nullptr;  // texture atlas: every loaded slot, back to back
+  // the brightness classes' table (sfrt_raycache.h BrightClasses::rep), uploaded when the world is
+  // created; kCompactClassLimit entries (null: no memory for it, the compact layer is never filled)
+  uint32_t* d_bright_rep = nullptr;
   size_t d_tex_texels = 0;
   // A new texture goes into a new atlas, uploaded on `stream` from pinned staging; launches
   // queued earlier keep reading the old one (its pointer is in their arguments), launches queued
@@ -220,6 +226,7 @@ struct sfrt_world {
     scheds.release();
     dump_sched.release();
     (void)hipFree(d_tex);
+    (void)hipFree(d_bright_rep);
     for (void* p : retired_tex) (void)hipFree(p);
     tex_written.release();
     tex_stage.release();
@@ -449,20 +456,31 @@ struct sfrt_world {
       // were that to change, the layer is not filled).
       const bool texels = texel_cache != 0 && sfrt::texel_index_fits(d_tex_texels);
       if (texels) make_tex_key(tex_key, recs, f.n);
+      sfrt::ChainCaches& mine = caches[cur_chain];
       const int rays = (int)((key >> 56) & 7);
+      // The compact layer: the option (1: the shape it was proven at only, DESIGN.md 5 "Compact
+      // layer"), no supersampling, every index the records can name in 16 bits, the class table.
+      const bool compact_shape = compact_texels == 2 ||
+                                 (compact_texels == 1 && rays == 4 && f.n <= sfrt::kInlineSpheres);
+      const bool compact = texels && compact_shape && !sfrt::kDiagnosticBuild && d_bright_rep &&
+                           sfrt::compact_eligible(recs.data(), f.n, f.ss);
       const sfrt::CacheSizes sizes{sfrt::ray_cache_bytes(tiles, rays), sfrt::tile_rec_bytes(tiles),
                                    sfrt::cull_rec_bytes(tiles),
                                    sfrt::cull_win_bytes(tiles, f.n > sfrt::kInlineSpheres),
                                    sfrt::hit_cache_bytes(tiles, rays),
-                                   texels ? sfrt::texel_cache_bytes(tiles, rays) : 0};
-      sfrt::ChainCaches& mine = caches[cur_chain];
+                                   texels ? sfrt::texel_cache_bytes(tiles, rays) : 0,
+                                   compact ? sfrt::compact_cache_bytes(tiles, rays) : 0};
       // (the diagnostic builds exist to time the march: no hit cache)
       launch_caches = mine.begin(cull_key.ray, cull_key, sizes,
                                  cache_bytes_held() - mine.bytes_under_ray_budget(),
                                  hit_bytes_budgeted() - mine.bytes_under_hit_budget(),
                                  (long long)ray_cache_mb << 20,
                                  sfrt::kDiagnosticBuild ? 0 : hit_budget_bytes(), CacheDevice{s, f, recs},
-                                 texels ? &tex_key : nullptr);
+                                 texels ? &tex_key : nullptr, compact);
+      if (launch_caches.compact != sfrt::RayAction::kTrace) {
+        launch_caches.bright_rep = d_bright_rep;
+        launch_caches.bright_classes = sfrt::BrightClasses::get().classes();
+      }
       // A reading launch marches nothing and takes no part in the tile order: nothing is linked.
       if (launch_caches.reading()) {
         sfrt::TileSchedPtrs{}.link(f);
@@ -486,6 +504,23 @@ struct sfrt_world {
   // wrote them.
   static void make_tex_key(sfrt::TexKey& k, const std::vector<sfrt::SphereRec>& recs, int n) {
     k.set_textures(recs.data(), n);
+  }
+
+  // The class table on the device, at world creation (128 KiB, off the render path): the entries
+  // past the last class repeat it, so that every class a record's 15 bits can name is readable.
+  // A failure is no error of the world: the compact layer is never filled.
+  void upload_bright_rep() {
+    if (!sfrt::BrightClasses::get().fits()) return;
+    std::vector<uint32_t> rep = sfrt::BrightClasses::get().rep;
+    rep.resize(sfrt::kCompactClassLimit, rep.back());
+    void* p = nullptr;
+    if (hipMalloc(&p, rep.size() * 4) != hipSuccess ||
+        hipMemcpy(p, rep.data(), rep.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      if (p) (void)hipFree(p);
+      return;
+    }
+    d_bright_rep = (uint32_t*)p;
   }
 
   static sfrt::RayKey make_ray_key(const sfrt::FrameRec& f, long long tile_key) {
@@ -523,6 +558,9 @@ struct sfrt_world {
   long long texel_bytes_held() const {
     return held([](const sfrt::ChainCaches& c) { return c.texel_bytes(); });
   }
+  long long compact_bytes_held() const {
+    return held([](const sfrt::ChainCaches& c) { return c.compact_bytes(); });
+  }
   long long hit_bytes_budgeted() const {  // with the texel records: what the option limits
     return held([](const sfrt::ChainCaches& c) { return c.bytes_under_hit_budget(); });
   }
@@ -556,12 +594,14 @@ struct sfrt_world {
   // An option lowered below what the chains hold (hit_only: SFRT_OPT_HIT_CACHE_MB, the hit caches
   // go; else SFRT_OPT_RAY_CACHE_MB, every cache goes).  The chains' streams may be gone
   // (sfrt_sched.h), so the host waits for the device.
-  // texel_only: SFRT_OPT_TEXEL_CACHE, that layer alone.
-  int release_caches(bool hit_only, bool texel_only = false) {
+  // texel_only: SFRT_OPT_TEXEL_CACHE, that layer (and the compact one on it) alone;
+  // compact_only: SFRT_OPT_COMPACT_TEXELS, that layer alone.
+  int release_caches(bool hit_only, bool texel_only = false, bool compact_only = false) {
     HIP_TRY(hipDeviceSynchronize());
     const auto free_now = [](void* p) { return hipFree(p) == hipSuccess; };
     for (sfrt::ChainCaches& c : caches) {
-      if (texel_only) c.release_texel(free_now);
+      if (compact_only) c.release_compact(free_now);
+      else if (texel_only) c.release_texel(free_now);
       else if (hit_only) c.release_hit(free_now);
       else c.release_all(free_now);
     }
@@ -712,6 +752,7 @@ int sfrt_world_create(int hip_device, sfrt_world** out) {
     delete w;
     return SFRT_E_HIP;
   }
+  w->upload_bright_rep();
   *out = w;
   return SFRT_OK;
 }
@@ -965,6 +1006,19 @@ int sfrt_world_set_option(sfrt_world* w, int option, int value) {
     w->texel_cache = value ? 1 : 0;
     return SFRT_OK;
   }
+  if (option == SFRT_OPT_COMPACT_TEXELS) {
+    if (value < 0 || value > 2) return SFRT_E_INVALID;
+    if (value < w->compact_texels) {  // (lowered: records of a shape no longer served would stay held)
+      if (w->compact_bytes_held() > 0) {
+        sfrt::DeviceGuard g(w->device);
+        const int rc = w->release_caches(false, false, true);
+        if (rc) return rc;
+      }
+      for (sfrt::ChainCaches& c : w->caches) c.invalidate_compact();
+    }
+    w->compact_texels = value;
+    return SFRT_OK;
+  }
   return SFRT_E_INVALID;
 }
 
@@ -1005,6 +1059,15 @@ int sfrt_world_texel_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* h
   return SFRT_OK;
 }
 
+int sfrt_world_compact_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits, int64_t* bytes) {
+  if (!w || !fills || !hits || !bytes) return SFRT_E_INVALID;
+  std::lock_guard<std::mutex> lk(w->mu);
+  *fills = w->cache_stats.compact_fills;
+  *hits = w->cache_stats.compact_hits;
+  *bytes = w->compact_bytes_held();
+  return SFRT_OK;
+}
+
 int sfrt_world_tile_record_bytes(const sfrt_world* w, int64_t* bytes) {
   if (!w || !bytes) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
@@ -1023,6 +1086,7 @@ int sfrt_world_get_option(const sfrt_world* w, int option, int* value) {
     case SFRT_OPT_RAY_CACHE_MB: *value = w->ray_cache_mb; return SFRT_OK;
     case SFRT_OPT_HIT_CACHE_MB: *value = w->hit_cache_mb; return SFRT_OK;
     case SFRT_OPT_TEXEL_CACHE: *value = w->texel_cache; return SFRT_OK;
+    case SFRT_OPT_COMPACT_TEXELS: *value = w->compact_texels; return SFRT_OK;
     default: return SFRT_E_INVALID;
   }
 }
@@ -1638,7 +1702,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 15; }
+int sfrt_version(void) { return 16; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

@@ -597,6 +597,44 @@ __device__ __forceinline__ bool texel_load(const TexelRec* __restrict__ xr, int 
   return moving;
 }
 
+// The compact layer (sfrt_raycache.h CompactRec; DESIGN.md 5 "Compact layer"): a texel record in
+// one dword, [tile][lane][r] in the lane map of k_shade_compact, whose lane owns R consecutive
+// pixels of one row.  Stored once per TexKey by k_shade_texels_cf, a k_shade_texels whose lane
+// (row, i) holds columns r * 8 + i: column c of a row belongs to the reader's lane row * 8 + c / R,
+// slot c % R -- a bijection of the tile's 64 R slots, clamped duplicates included, so every record
+// the reader loads was written.  The class comes from the table's own thresholds (bright_class_of:
+// integer compares, fifteen steps a ray).
+// mw: the texel records' second dwords as stored (the moving bit per ray).
+template <int R>
+__device__ __forceinline__ void compact_store(CompactRec* __restrict__ cr, int tile, int lane,
+                                              const Shading (&sh)[R], const uint32_t (&mw)[R],
+                                              const uint32_t* __restrict__ rep, uint32_t classes) {
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int c = r * kTile + (lane & 7);
+    const uint32_t cls = bright_class_of(rep, classes, texel_bright_bits(__float_as_uint(sh[r].brightness)));
+    cr[compact_rec_at(tile, R, (lane & ~7) + c / R, c % R)].w =
+        compact_pack(sh[r].tex, sh[r].outside, cls, texel_moving(mw[r]));
+  }
+}
+// texel_load with each record's second dword as stored.
+template <int R>
+__device__ __forceinline__ bool texel_load_w(const TexelRec* __restrict__ xr, int tile, int lane,
+                                             int (&tex)[R], float (&br)[R], uint32_t (&w)[R]) {
+  uint2 v[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) v[r] = *(const uint2*)(xr + hit_rec_at(tile, R, r, lane));
+  bool moving = false;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    tex[r] = (int)v[r].x;
+    br[r] = __uint_as_float(texel_bright_bits(v[r].y));
+    w[r] = v[r].y;
+    moving = moving || texel_moving(v[r].y);
+  }
+  return moving;
+}
+
 // L = +0 for a lane's R rays at the start of a march step, two registers per
 // v_mov_b64 (left to itself the compiler copies one zero register into three
 // others and then pairs them: five moves a step for R = 4, not two).
@@ -920,12 +958,15 @@ __device__ __forceinline__ Rays<R> march_wave(const FrameRec& f, const SphereRec
 // no SphereRec is read and shade_texel is not entered, the index is the one it left; then the
 // same texel loads, shade_rgba, box filter and stores.  Status bit 0 comes from the moving bits,
 // bit 2 from the sentinel of a valid lane.
+// CF (with HIT 4, SS 0; DESIGN.md 5 "Compact layer"): k_shade_texels_cf -- 4, which also stores each
+// ray's compact record in cf (compact_store), in the lane map of k_shade_compact, the kernel that
+// reads them and is no instantiation of this function.
 // PLACE (sfrt_world_render_subset): the subset goes in place into a whole frame --
 // compact column a (output pixel a >> SS) is stored xstride elements apart, the host having put
 // the subset's first pixel into f.out and yadd frame rows into f.out_pitch (the planes' pitches
 // likewise) -- where every other launch stores it compactly.  All else is the same.
 template <int R, bool LIST, bool DUMP, class P, int SS = 0, bool CACHED = false, bool AUX = false,
-          bool PLACE = false, bool CULLED = false, int HIT = 0>
+          bool PLACE = false, bool CULLED = false, int HIT = 0, bool CF = false>
 __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
                                                     const SphereRec* __restrict__ sph,
                                                     DumpArgs dmp,
@@ -936,10 +977,14 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
                                                     [[maybe_unused]] const CullRec* cr = nullptr,
                                                     [[maybe_unused]] const CullLane<LIST>* cw = nullptr,
                                                     [[maybe_unused]] HitRec* hr = nullptr,
-                                                    [[maybe_unused]] TexelRec* xr = nullptr) {
+                                                    [[maybe_unused]] TexelRec* xr = nullptr,
+                                                    [[maybe_unused]] CompactRec* cf = nullptr,
+                                                    [[maybe_unused]] const uint32_t* rep = nullptr,
+                                                    [[maybe_unused]] uint32_t classes = 0) {
   // the launches that march nothing: 2 and 3 shade from the hit records, 4 from the texel records
   constexpr bool READS = HIT >= 2;
   static_assert(HIT >= 0 && HIT <= 4, "0, _hf, k_shade_hits, _tf, k_shade_texels");
+  static_assert(!CF || (HIT == 4 && SS == 0), "k_shade_texels_cf: the compact fill rides on a texel read");
   static_assert(!CULLED || CACHED, "the cull cache rides on the ray cache");
   static_assert(HIT == 0 || (CULLED && !DUMP && !AUX && !PLACE), "the hit cache rides on the cull cache");
   static_assert(!PLACE || (!DUMP && !CACHED), "the placing kernels compute their directions and dump nothing");
@@ -990,8 +1035,11 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
   const float l0 = f.first_l;
   Rays<R> ray;  // iters: DUMP and AUX only, the host's first trip included
   uint64_t m_end = 0;  // the wave's culling mask, for the probe's tile_end
-  [[maybe_unused]] uint32_t hit_w[(HIT == 1 || HIT == 3) ? R : 1];
-  if constexpr (HIT == 4) {
+  [[maybe_unused]] uint32_t hit_w[(HIT == 1 || HIT == 3 || CF) ? R : 1];
+  if constexpr (CF) {  // as below, with each record's moving bit kept for the compact record
+    const bool moving = texel_load_w<R>(xr, tile, lane, ray.draw, ray.pz, hit_w);
+    if (__builtin_amdgcn_ballot_w64(moving) != 0 && lane == 0) atomicOr(f.status, 1);
+  } else if constexpr (HIT == 4) {
     // ray.draw holds the records' texel indices from here on, ray.pz the brightness
     const bool moving = texel_load<R>(xr, tile, lane, ray.draw, ray.pz);
     if (__builtin_amdgcn_ballot_w64(moving) != 0 && lane == 0) atomicOr(f.status, 1);
@@ -1128,6 +1176,7 @@ __device__ __forceinline__ void trace_tile_window_r(const FrameRec& f,
     // every lane, clamped duplicates included, as the reading kernels load them
     if constexpr (HIT == 1) hit_store<R>(hr, tile, lane_s, sh, hit_w);
     if constexpr (HIT == 3) texel_store<R>(xr, tile, lane_s, sh, hit_w);
+    if constexpr (CF) compact_store<R>(cf, tile, lane_s, sh, hit_w, rep, classes);
     // AUX: ray r's plane values beside its colour store (plain vector stores)
     [[maybe_unused]] auto aux_store = [&](int r) {
       const int c = col_out(r);
@@ -1383,6 +1432,92 @@ __global__ __launch_bounds__(64, 8) void k_shade_texels(FrameRec f, const CullRe
                                                         const TexelRec* __restrict__ xr) {
   trace_tile_window_r<R, false, false, NoProbe, SS, true, false, false, true, 4>(
       f, nullptr, DumpArgs{}, nullptr, nullptr, AuxArgs{}, 1, cr, nullptr, nullptr, const_cast<TexelRec*>(xr));
+}
+
+// The compact layer's kernels (sfrt_raycache.h CompactRec, ChainCaches; DESIGN.md 5 "Compact
+// layer").  k_shade_texels_cf is k_shade_texels<R, 0> that also stores each ray's compact record
+// (compact_store; once per TexKey, its occupancy left to the compiler).
+template <int R>
+__global__ __launch_bounds__(64) void k_shade_texels_cf(FrameRec f, const CullRec* cr,
+                                                        const TexelRec* __restrict__ xr,
+                                                        CompactRec* __restrict__ cf,
+                                                        const uint32_t* __restrict__ rep, uint32_t classes) {
+  trace_tile_window_r<R, false, false, NoProbe, 0, true, false, false, true, 4, true>(
+      f, nullptr, DumpArgs{}, nullptr, nullptr, AuxArgs{}, 1, cr, nullptr, nullptr, const_cast<TexelRec*>(xr),
+      cf, rep, classes);
+}
+
+// R dwords of one lane as one access of dword alignment (a frame's base and pitch promise no
+// more).  A vector, not a struct: a struct's members become R scalar stores that the compiler may
+// sink and merge apart again (at R = 4 three dwords and one, the last shared with the edge path).
+template <int R>
+struct Dwords {
+  typedef uint32_t type __attribute__((ext_vector_type(R), aligned(4)));
+};
+
+// k_shade_compact shades a frame from the compact records.  It marches nothing, so it keeps nothing
+// of the marching kernels' lane map: a lane owns the R consecutive pixels row lane >> 3, columns
+// tile_x * 8R + (lane & 7) * R + r.  Its R records are one load (1 KiB contiguous per wave at
+// R = 4), its R pixels one store: at R = 4 a wave writes eight whole 128-byte pieces of eight rows
+// with one instruction, where the marching map needs four that each write eight 32-byte pieces.
+// Between them the R texel gathers and the R gathers of the classes' brightnesses (rep[class],
+// BrightClasses::rep) and shade_rgba.
+// A tile that crosses the right edge stores per pixel under `valid`; its edge lanes load the
+// duplicates k_shade_texels_cf stored for them and store nothing.  Status bit 0 comes from the
+// moving bits, bit 2 from the sentinel of a valid lane.
+// The frame record is the only argument.  A reading launch takes no part in the tile order, and
+// launch_trace puts what this kernel reads where that and the records would be: f.tile_order the
+// compact records, f.prev_cost the cull records, f.spheres the class table.
+template <int R>
+__global__ __launch_bounds__(64, 8) void k_shade_compact(FrameRec f) {
+  const int tile = (int)blockIdx.x;
+  const int tiles_y = (f.sub_rows + kTile - 1) / kTile;
+  if (tile >= f.tiles_x * tiles_y) return;  // (the grid is exactly the tiles)
+  const CullRec crec = cull_rec_at((const CullRec*)f.prev_cost, tile);
+  const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  using Vec = typename Dwords<R>::type;
+  const Vec recv = *(const Vec*)(f.tile_order + compact_rec_at(tile, R, lane, 0));
+  uint32_t rec[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) rec[r] = recv[r];
+  const float* __restrict__ rep = (const float*)f.spheres;
+  const int tile_x = (int)crec.tile_x;
+  const int tile_y = (int)(crec.tile_y & ~kCullRecFull);
+  const int row = tile_y * kTile + (lane >> 3);  // of the band
+  const int col0 = tile_x * R * kTile + (lane & 7) * R;
+  bool moving = false, outside[R];
+  uint32_t texel[R];
+  float bright[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    moving = moving || compact_moving(rec[r]);
+    outside[r] = compact_outside(rec[r]);
+    texel[r] = f.tex[outside[r] ? 0u : compact_tex(rec[r])];  // (some texel of the atlas; unused)
+    bright[r] = rep[compact_class(rec[r])];
+  }
+  // (the gathers are left to the compiler: one operand list that forces all 2R before the first
+  // use, k_shade_texels<4, 0>'s remedy, measured slower here -- DESIGN.md 5 "Compact layer")
+  if (__builtin_amdgcn_ballot_w64(moving) != 0 && lane == 0) atomicOr(f.status, 1);
+  if (row >= f.sub_rows) return;
+  uint32_t* const px = f.out + (long long)row * f.out_pitch + col0;
+  uint32_t rgba[R];
+  bool bad = false;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    bad = bad | (outside[r] & (col0 + r < f.sub_w));
+    rgba[r] = shade_rgba(outside[r] ? 0u : texel[r], bright[r]);
+  }
+  if (bad) atomicOr(f.status, 2);  // the reference would read outside the image
+  if (col0 + R <= f.sub_w) {
+    Vec v;
+#pragma unroll
+    for (int r = 0; r < R; r++) v[r] = rgba[r];
+    *(Vec*)px = v;
+  } else {
+#pragma unroll
+    for (int r = 0; r < R; r++)
+      if (col0 + r < f.sub_w) px[r] = rgba[r];
+  }
 }
 
 // The DUMP instantiations of both (sfrt_world_trace_points): the shipped march and
@@ -1737,6 +1872,13 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
   if (hit_mode < 0 || hit_mode > 2 || (hit_mode != 0) != (hit_recs != nullptr)) return -1;
   if ((texel_mode != 0) != (texel_recs != nullptr) || (texel_mode && hit_mode != 2)) return -1;
   if (hit_mode && (!cull_recs || dump || aux || place_xstride || kDiagnosticBuild)) return -1;
+  // the compact layer rides on a launch that reads the texel records: 1 also stores it
+  // (k_shade_texels_cf), 2 shades from it (k_shade_compact); never supersampled
+  const int compact_mode = c.compact == RayAction::kRead ? 2 : c.compact == RayAction::kFill ? 1 : 0;
+  if ((compact_mode != 0) != (c.compact_recs != nullptr)) return -1;
+  if (compact_mode && (texel_mode != 2 || f.ss != 0 || !c.bright_rep || c.bright_classes == 0 ||
+                       c.bright_classes >= kCompactClassLimit))
+    return -1;
   // (2: the caller linked nothing of the tile order into f, but the grid is the ordered one)
   const bool ordered = hit_mode == 2 || f.tile_cost != nullptr;  // linked into the tile-order chain
   const int rays = trace_rays(f, ordered);
@@ -1795,6 +1937,22 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                   : inl(k_trace_place_r<R, SS, false>, no_planes, place_xstride);
       } else if (aux) {
         list ? lst(k_trace_window_list_aux<R, SS>, *aux) : inl(k_trace_window_r_aux<R, SS>, *aux);
+      } else if (compact_mode == 2) {
+        if constexpr (SS == 0) {
+          FrameRec h = g;  // the one argument (k_shade_compact): nothing of the tile order is linked
+          h.tile_order = (const uint32_t*)c.compact_recs;
+          h.prev_cost = (const uint8_t*)cull_recs;
+          h.spheres = (const SphereRec*)c.bright_rep;
+          if (list) hipExtLaunchKernelGGL(k_shade_compact<R>, gr, b, 0, s, nullptr, ev, 0, h);
+          else hipLaunchKernelGGL(k_shade_compact<R>, gr, b, 0, s, h);
+        }
+      } else if (compact_mode == 1) {
+        if constexpr (SS == 0) {
+          list ? lst(k_shade_texels_cf<R>, cull_recs, (const TexelRec*)texel_recs, c.compact_recs, c.bright_rep,
+                     c.bright_classes)
+               : lst_no_event(k_shade_texels_cf<R>, cull_recs, (const TexelRec*)texel_recs, c.compact_recs,
+                              c.bright_rep, c.bright_classes);
+        }
       } else if (texel_mode == 2) {
         list ? lst(k_shade_texels<R, SS>, cull_recs, (const TexelRec*)texel_recs)
              : lst_no_event(k_shade_texels<R, SS>, cull_recs, (const TexelRec*)texel_recs);

@@ -4,8 +4,8 @@
 (lib@R forces R pixels per lane, SFRT_OPT_RAYS_PER_LANE; lib^O sets SFRT_OPT_TILE_ORDER=O on every
 renderer; lib#K sets SFRT_AB_KNOB=K for an
 experimental build that reads it -- r2_ab28 read it as SFRT_SPLIT; the product reads none; lib%M sets
-SFRT_OPT_HIT_CACHE_MB=M and lib~T sets SFRT_OPT_TEXEL_CACHE=T on the sphere world, where the library
-has the option)
+SFRT_OPT_HIT_CACHE_MB=M, lib~T sets SFRT_OPT_TEXEL_CACHE=T and lib+C sets SFRT_OPT_COMPACT_TEXELS=C on
+the sphere world, where the library has the option)
 
 Each round starts one process per library (SFRT_LIB=<lib>, the same sfrt.py), which
 times every case with HIP events (median kernel time, event-pair overhead subtracted;
@@ -98,6 +98,8 @@ def child(cases, reps, rays):
         w.set_option(sfrt.SFRT_OPT_HIT_CACHE_MB, int(os.environ["SFRT_AB_HIT_CACHE_MB"]))
     if os.environ.get("SFRT_AB_TEXEL_CACHE") is not None:  # "lib~T"
         w.set_option(sfrt.SFRT_OPT_TEXEL_CACHE, int(os.environ["SFRT_AB_TEXEL_CACHE"]))
+    if os.environ.get("SFRT_AB_COMPACT_TEXELS") is not None:  # "lib+C"
+        w.set_option(sfrt.SFRT_OPT_COMPACT_TEXELS, int(os.environ["SFRT_AB_COMPACT_TEXELS"]))
     pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
              for _ in range(64)]
     for a, b in pairs:
@@ -174,6 +176,7 @@ def main():
             probe = lib.endswith("!")
             spec, _, order = lib.rstrip("!").partition("^")  # "^O": 8f renderers' tile order
             spec, _, knob = spec.partition("#")  # "#K": SFRT_AB_KNOB=K for an A/B build
+            spec, _, compact = spec.partition("+")  # "+C": SFRT_OPT_COMPACT_TEXELS=C
             spec, _, texel = spec.partition("~")  # "~T": SFRT_OPT_TEXEL_CACHE=T
             spec, _, hit_mb = spec.partition("%")  # "%M": SFRT_OPT_HIT_CACHE_MB=M
             path, _, rays = spec.partition("@")
@@ -186,6 +189,8 @@ def main():
                 env["SFRT_AB_HIT_CACHE_MB"] = hit_mb
             if texel:
                 env["SFRT_AB_TEXEL_CACHE"] = texel
+            if compact:
+                env["SFRT_AB_COMPACT_TEXELS"] = compact
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--libs", lib,
                                 "--cases", a.cases, "--reps", str(a.reps), "--rays", rays or "0"],
                                capture_output=True, text=True, env=env, timeout=600)
