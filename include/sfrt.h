@@ -424,7 +424,30 @@ SFRT_API int sfrt_world_cast_rays(sfrt_world* w, const float* dirs, const float*
  * the layer never keeps a lower one from filling; between streams its bytes count like any others
  * under the limit (two 4K streams hold 2 x 232 MB of 512: a third stream's caches may find less
  * room than without the layer -- raise the limit or set this option to 0 there).  Lowering the
- * option waits for the device and frees that layer only.  See sfrt_world_compact_cache_stats. */
+ * option waits for the device and frees that layer only.  See sfrt_world_compact_cache_stats.
+ * SFRT_OPT_PIXEL_CACHE (1 = default; 0 = off; 2 = every plain sfrt_world_render_band launch; other
+ * values return SFRT_E_INVALID): the pixel layer on top of the texel cache and the compact layer.
+ * At 1 it serves the launches it was measured to pay for by the project's rule -- not supersampled,
+ * at most 64 spheres, no drawn texture ending beyond texel 65,535 of the atlas -- and at 2 also the
+ * others (more spheres, larger atlases, supersampled worlds: gains the rule did not confirm).  What a launch that shades from those still
+ * computes -- the texel, the brightness, the colour, the box filter when supersampled -- depends on
+ * their state and on the textures' contents, which change only through sfrt_world_load_texture.
+ * While that state stands still and no texture is loaded, the second consecutive
+ * sfrt_world_render_band launch that reads the topmost of those layers is followed by a copy of the
+ * band it wrote (4 bytes per output pixel, whatever the supersampling factor: 33.2 MB for a 4K
+ * frame), and later launches are one copy of those pixels into the caller's band, whatever its
+ * base and pitch: the same bytes and the same status.  Every sfrt_world_load_texture call, for any
+ * slot and whether or not a sphere draws it, makes the next launch shade again from the layer
+ * under this one -- the very next frame shows the new texels -- and the launch after it stores the
+ * pixels again; a texture loaded every frame never fills the layer.  Only plain
+ * sfrt_world_render_band launches take part (no planes, subsets, view batches or ray batches).
+ * The bytes count against SFRT_OPT_HIT_CACHE_MB after the stream's other caches have theirs; where
+ * they do not fit, launches stay on the layer under it.  Whatever drops or refills a cache under
+ * it frees the stream's pixel layer first, so within a stream it never keeps a lower one from
+ * filling; between streams its bytes count like any others under the limit.  Two 4K streams need
+ * 2 x 265 MB at the default 512: the second stream's pixel layer does not fit and that stream stays
+ * on its compact layer -- raise the limit to 531 to serve both.  Lowering the option waits for
+ * the device and frees that layer only.  See sfrt_world_pixel_cache_stats. */
 #define SFRT_OPT_CULL 1
 #define SFRT_OPT_RAYS_PER_LANE 2
 #define SFRT_OPT_TILE_ORDER 3
@@ -433,6 +456,7 @@ SFRT_API int sfrt_world_cast_rays(sfrt_world* w, const float* dirs, const float*
 #define SFRT_OPT_HIT_CACHE_MB 6
 #define SFRT_OPT_TEXEL_CACHE 7
 #define SFRT_OPT_COMPACT_TEXELS 8
+#define SFRT_OPT_PIXEL_CACHE 9
 SFRT_API int sfrt_world_set_option(sfrt_world* w, int option, int value);
 /* The current value of any of the options above (SFRT_OPT_SUPERSAMPLE: the factor 1, 2 or 4). */
 SFRT_API int sfrt_world_get_option(const sfrt_world* w, int option, int* value);
@@ -472,6 +496,12 @@ SFRT_API int sfrt_world_texel_cache_stats(const sfrt_world* w, int64_t* fills, i
  * SFRT_OPT_HIT_CACHE_MB, not part of the other caches' bytes. */
 SFRT_API int sfrt_world_compact_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits,
                                             int64_t* bytes);
+/* The pixel layer's counters since the world was created (SFRT_OPT_PIXEL_CACHE): *fills = launches
+ * whose band was copied into the layer behind them, *hits = launches that were a copy out of it
+ * (each also counts as a hit of every cache under it), *bytes = device memory the world's cached
+ * pixels hold now.  Counted against SFRT_OPT_HIT_CACHE_MB, not part of the other caches' bytes. */
+SFRT_API int sfrt_world_pixel_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits,
+                                          int64_t* bytes);
 
 /* ---- stateless helpers ---- */
 /* UpdateSpheres ordering of an array in place (SphereWorld.cpp:199-212). */

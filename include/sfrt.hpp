@@ -335,6 +335,17 @@ class SphereWorld {
     check(sfrt_world_compact_cache_stats(w_, &s.fills, &s.hits, &s.bytes), "compact_cache_stats");
     return s;
   }
+  // SFRT_OPT_PIXEL_CACHE (sfrt.h): the finished pixels of a scene at rest, copied until a texture
+  // is loaded; 0 = off, 1 = the launches it was proven at (default), 2 = every plain band.
+  void SetPixelCache(int mode) { SetOption(SFRT_OPT_PIXEL_CACHE, mode); }
+  int PixelCache() const { return GetOption(SFRT_OPT_PIXEL_CACHE); }
+  // The pixel layer's counters (sfrt.h sfrt_world_pixel_cache_stats).
+  using PixelCacheStats = CullCacheStats;  // the same three counters
+  PixelCacheStats GetPixelCacheStats() const {
+    PixelCacheStats s{};
+    check(sfrt_world_pixel_cache_stats(w_, &s.fills, &s.hits, &s.bytes), "pixel_cache_stats");
+    return s;
+  }
   sfrt_world* handle() { return w_; }
 
  private:

@@ -11,12 +11,15 @@
 // the shading is left with once the texture sizes and slots stand still too).
 // On the texel cache rides the compact layer (CompactRec: the same ray in 4 bytes while the atlas
 // is small enough, the brightness as its class in a table of binary32 constants).
-// One policy (CacheLayer) decides for each of the five; one object per chain (ChainCaches, at
-// the end) owns the layers, their seven buffers and the order in which a launch decides, fills
+// On top rides the pixel layer (PixelKey: the finished RGBA8 band itself while no texel changes
+// either, copied into the caller's frame).
+// One policy (CacheLayer) decides for each of the six; one object per chain (ChainCaches, at
+// the end) owns the layers, their eight buffers and the order in which a launch decides, fills
 // and drops them.  This header makes no HIP call -- the device is a parameter of
 // ChainCaches::begin -- so all of it is tested on the host as it ships: tests/native/
 // raycache_check.cpp (the layer), tilerec_check.cpp, cullcache_check.cpp, hitcache_check.cpp,
-// texelcache_check.cpp, compactrec_check.cpp (the chain, through counting allocators).
+// texelcache_check.cpp, compactrec_check.cpp, pixelcache_check.cpp (the chain, through counting
+// allocators).
 #pragma once
 
 #include <algorithm>
@@ -451,6 +454,30 @@ struct BrightClasses {
   }
 };
 
+// ---- The pixel layer (DESIGN.md 5 "Pixel layer") ----
+//
+// What a launch that shades from the texel or the compact records still computes of a ray every
+// frame -- the texel gather, rep[class], shade_rgba, the box filter when supersampled -- depends on
+// the records (fixed under TexKey) and on the atlas' texels, and on nothing else.  Texels reach the
+// atlas only through the library (sfrt_world_load_texture), which counts every such call in a
+// per-world generation: while the TexKey and the generation stand still (PixelKey), a plain
+// render_band launch is a copy of the band it wrote the last time.
+//
+// The band's output pixels, after the box filter: sub_w >> ss columns by sub_rows >> ss rows of
+// RGBA8, rows packed in frame order, no tiles, the buffer 16-byte aligned (an allocation's start).
+// The band's rows and width and the supersampling factor are the RayKey's (sub_row0, sub_rows,
+// sub_w, tile_key bits 59-60); the caller's base and pitch are no part of the key -- the copy
+// kernel (sphere_trace.hip k_pixels_copy) takes them from the launch.
+// The launch's status bits (the values 1, the march guard hit, and 2, a texel outside its texture) are constants of the key too: the filling
+// launch raises them in a word the layer owns, and every copy ORs that word into the world's.
+inline long long pixel_cache_bytes(long long out_w, long long out_rows) { return out_w * out_rows * 4; }
+
+struct PixelKey {
+  TexKey tex;
+  unsigned long long generation = 0;  // the world's count of atlas writes
+  bool same(const PixelKey& o) const { return generation == o.generation && tex.same(o.tex); }
+};
+
 // ---- One chain's caches (DESIGN.md 5 "The chain's caches") ----
 
 // What ChainCaches::begin decided for one launch and what that launch reads: launch_trace's cache
@@ -460,6 +487,10 @@ struct TraceCaches {
   RayAction ray = RayAction::kTrace, cull = RayAction::kTrace, hit = RayAction::kTrace;
   RayAction texel = RayAction::kTrace;  // kRead implies hit == kRead; kFill rides on a hit read
   RayAction compact = RayAction::kTrace;  // kRead implies texel == kRead; kFill rides on a texel read
+  // kRead: the launch is one copy of pixels into the caller's band (the decisions under it stay
+  // kRead: it counts as a read of theirs); kFill: the launch the layers under it decided, into the
+  // caller's band with the layer's status word for the world's, then a copy of the band into pixels
+  RayAction pixel = RayAction::kTrace;
   const float* dirs = nullptr;
   const TileRec* tile_recs = nullptr;
   const CullRec* cull_recs = nullptr;
@@ -467,6 +498,10 @@ struct TraceCaches {
   HitRec* hit_recs = nullptr;       // written by a filling launch (hit == kFill), read by a reading one
   TexelRec* texel_recs = nullptr;   // likewise (a launch that reads them still gets hit_recs, unread)
   CompactRec* compact_recs = nullptr;  // likewise (a launch that reads them still gets texel_recs, unread)
+  uint32_t* pixels = nullptr;          // set exactly when pixel != kTrace
+  // the layer's status word on the device, set by the caller of begin() for a launch whose pixel
+  // action is not kTrace: zeroed and raised by the filling launch, ORed into the world's by every copy
+  int* pixel_status = nullptr;
   // the world's class table on the device (BrightClasses::rep), set by the caller of begin() for a
   // launch whose compact action is not kTrace; readable up to kCompactClassLimit entries
   const uint32_t* bright_rep = nullptr;
@@ -478,17 +513,19 @@ struct CacheSizes {  // of one launch's grid: ray_cache_bytes, tile_rec_bytes, c
   long long dirs = 0, tile_recs = 0, cull_recs = 0, cull_wins = 0, hit_recs = 0;
   long long texel_recs = 0;  // texel_cache_bytes (0: no texel layer)
   long long compact_recs = 0;  // compact_cache_bytes (0: no compact layer, or the launch is not eligible)
+  long long pixels = 0;  // pixel_cache_bytes (0: no pixel layer)
 };
 
 struct CacheCounters {  // sfrt_world_{ray,cull,hit,texel}_cache_stats
   int64_t ray_cached_frames = 0, ray_fills = 0, cull_fills = 0, cull_hits = 0, hit_fills = 0, hit_hits = 0;
   int64_t texel_fills = 0, texel_hits = 0;
   int64_t compact_fills = 0, compact_hits = 0;
+  int64_t pixel_fills = 0, pixel_hits = 0;
 };
 
-// The five layers and the seven buffers of one tile-order chain, and the one rule between them:
+// The six layers and the eight buffers of one tile-order chain, and the one rule between them:
 // an upper cache is never valid without the one under it.  A refill below drops what is above; a
-// failed fill drops its own layer and everything above it; a failed launch drops all five.
+// failed fill drops its own layer and everything above it; a failed launch drops all six.
 // The texel layer (TexKey) has no fill kernel of its own and is not filled by a marching launch:
 // only a launch that reads the hit layer fills it (the _tf kernels), and a launch that reads it
 // counts as a read of the three layers under it.
@@ -496,19 +533,27 @@ struct CacheCounters {  // sfrt_world_{ray,cull,hit,texel}_cache_stats
 // that reads the texel layer fills it (k_shade_texels_cf), a launch that reads it counts as a read
 // of the four under it, and whatever drops or refills the texel layer frees its buffer first, so it
 // never takes room a lower layer could have had in this chain.
+// The pixel layer (PixelKey; begin's pixel_generation) rides on the topmost of those two the launch
+// has: only a launch that reads the compact layer -- or the texel layer, where no compact layer is
+// decided for it -- fills it (its band copied behind it), a launch that reads it counts as a read of
+// every layer under it, and whatever drops or refills one of them frees its buffer first.
 struct ChainCaches {
   CacheLayer<RayKey> ray;
   CacheLayer<CullKey> cull, hit;
   CacheLayer<TexKey> texel, compact;
+  CacheLayer<PixelKey> pixel;
   CacheBuf dirs, tile_recs;  // ray_cache_bytes, tile_rec_bytes: one layer, two buffers
   CacheBuf cull_recs, cull_wins;
   CacheBuf hit_recs;
   CacheBuf texel_recs;
   CacheBuf compact_recs;
+  CacheBuf pixels;
   RayKey ray_key{};  // begin() -> end(): the launch being queued
   CullKey cull_key;
   TexKey tex_key;
   bool have_tex_key = false;
+  PixelKey pixel_key;  // (its .tex assigned only for a launch with a pixel layer)
+  bool have_pixel_key = false;
 
   long long cull_bytes() const { return cull_recs.bytes + cull_wins.bytes; }
   // What SFRT_OPT_RAY_CACHE_MB limits (the tile records ride free: 0.3 to 1 % of the directions),
@@ -517,7 +562,10 @@ struct ChainCaches {
   long long hit_bytes() const { return hit_recs.bytes; }  // the hit records alone (the stats)
   long long texel_bytes() const { return texel_recs.bytes; }
   long long compact_bytes() const { return compact_recs.bytes; }
-  long long bytes_under_hit_budget() const { return hit_recs.bytes + texel_recs.bytes + compact_recs.bytes; }
+  long long pixel_bytes() const { return pixels.bytes; }
+  long long bytes_under_hit_budget() const {
+    return hit_recs.bytes + texel_recs.bytes + compact_recs.bytes + pixels.bytes;
+  }
   long long tile_rec_bytes() const { return tile_recs.bytes; }
 
   // Before a launch that takes part.  other_ray, other_hit: what the world's other chains hold
@@ -528,10 +576,13 @@ struct ChainCaches {
   // tk: the launch's TexKey (tk->cull equal to ck), or null: no texel layer for this launch.
   // compact_ok: the launch is eligible for the compact layer (the option, no supersampling, every
   // texel index the records can name below kCompactOutside, a class table that fits).
+  // pixel_generation: the world's count of atlas writes for a launch that takes part in the pixel
+  // layer (a plain render_band with the option on; n.pixels its band's bytes), or < 0: no pixel
+  // layer for this launch -- it neither reads nor fills it, and drops it only with a layer under it.
   template <class Dev>
   TraceCaches begin(const RayKey& rk, const CullKey& ck, const CacheSizes& n, long long other_ray,
                     long long other_hit, long long ray_budget, long long hit_budget, Dev&& dev,
-                    const TexKey* tk = nullptr, bool compact_ok = false) {
+                    const TexKey* tk = nullptr, bool compact_ok = false, long long pixel_generation = -1) {
     const auto free_fn = [&dev](void* p) { return dev.free(p); };
     const auto reserve = [&](CacheBuf& b, long long m) {
       return b.reserve(m, free_fn, [&dev](long long q) { return dev.alloc(q); });
@@ -540,17 +591,24 @@ struct ChainCaches {
     cull_key = ck;
     have_tex_key = tk != nullptr;
     if (tk) tex_key = *tk;
+    have_pixel_key = tk != nullptr && pixel_generation >= 0;
+    if (have_pixel_key) {
+      pixel_key.tex = *tk;
+      pixel_key.generation = (unsigned long long)pixel_generation;
+    }
     TraceCaches d;
     d.decided = true;
     d.ray = ray.decide(rk, RayAction::kRead, n.dirs, dirs.bytes, other_ray, ray_budget);
     if (d.ray == RayAction::kFill) {
       // The tile records are rewritten: what rides on them goes first and takes no room from the
       // directions.  have_prev stays, so this very launch can go on to fill all three.
-      for (CacheBuf* b : {&cull_recs, &cull_wins, &hit_recs, &texel_recs, &compact_recs}) b->release(free_fn);
+      for (CacheBuf* b : {&pixels, &cull_recs, &cull_wins, &hit_recs, &texel_recs, &compact_recs})
+        b->release(free_fn);
       cull.valid = false;
       hit.valid = false;
       texel.valid = false;
       compact.valid = false;
+      pixel.valid = false;
       if (!reserve(dirs, n.dirs) || !reserve(tile_recs, n.tile_recs) ||
           !dev.fill_rays((float*)dirs.ptr, (TileRec*)tile_recs.ptr)) {
         invalidate();  // the buffers may be gone or half written
@@ -571,6 +629,7 @@ struct ChainCaches {
       hit.invalidate();
       texel.invalidate();
       compact.invalidate();
+      pixel.invalidate();
       d.cull = RayAction::kTrace;
     }
     if (d.cull != RayAction::kTrace) {
@@ -583,6 +642,8 @@ struct ChainCaches {
     // are this chain's to reuse)
     d.hit = hit.decide(ck, d.cull, n.hit_recs, bytes_under_hit_budget(), other_hit, hit_budget);
     if (d.hit == RayAction::kFill) {
+      pixels.release(free_fn);
+      pixel.valid = false;
       compact_recs.release(free_fn);
       compact.valid = false;
       texel_recs.release(free_fn);
@@ -591,6 +652,7 @@ struct ChainCaches {
         hit.invalidate();  // no memory for it: the launch stays on the cull-cache path
         texel.invalidate();
         compact.invalidate();
+        pixel.invalidate();
         d.hit = RayAction::kTrace;
       }
     }
@@ -603,12 +665,15 @@ struct ChainCaches {
       if (d.texel == RayAction::kFill && d.hit != RayAction::kRead) d.texel = RayAction::kTrace;
       if (d.texel == RayAction::kFill) {
         // (the compact records were made from the ones about to be rewritten: they go first, and
-        // the decision above did not count them)
+        // the decision above did not count them; the pixels before them)
+        pixels.release(free_fn);
+        pixel.valid = false;
         compact_recs.release(free_fn);
         compact.valid = false;
         if (!reserve(texel_recs, n.texel_recs)) {
           texel.invalidate();  // no memory for it: the launch reads the hit layer
           compact.invalidate();
+          pixel.invalidate();
           d.texel = RayAction::kTrace;
         }
       }
@@ -618,11 +683,32 @@ struct ChainCaches {
       d.compact = compact.decide(*tk, d.texel, compact_ok ? n.compact_recs : 0, compact_recs.bytes,
                                  other_hit + hit_recs.bytes + texel_recs.bytes, hit_budget);
       if (d.compact == RayAction::kFill && d.texel != RayAction::kRead) d.compact = RayAction::kTrace;
-      if (d.compact == RayAction::kFill && !reserve(compact_recs, n.compact_recs)) {
-        compact.invalidate();  // no memory for it: the launch reads the texel layer
-        d.compact = RayAction::kTrace;
+      if (d.compact == RayAction::kFill) {
+        // (the pixels were shaded from the layer under this one: they go first, whatever their
+        // launch would have read, and the decision above did not count them)
+        pixels.release(free_fn);
+        pixel.valid = false;
+        if (!reserve(compact_recs, n.compact_recs)) {
+          compact.invalidate();  // no memory for it: the launch reads the texel layer
+          pixel.invalidate();
+          d.compact = RayAction::kTrace;
+        }
       }
       if (d.compact != RayAction::kTrace) d.compact_recs = (CompactRec*)compact_recs.ptr;
+      // The pixel layer, on top of the compact layer -- of the texel layer where the launch has no
+      // compact layer -- and under the same budget, after the chain's other layers have theirs.  Only
+      // a launch that reads the layer under it fills it, by a copy of the band it wrote.
+      if (have_pixel_key) {
+        const RayAction below = d.compact != RayAction::kTrace ? d.compact : d.texel;
+        d.pixel = pixel.decide(pixel_key, below, n.pixels, pixels.bytes,
+                               other_hit + hit_recs.bytes + texel_recs.bytes + compact_recs.bytes, hit_budget);
+        if (d.pixel == RayAction::kFill && below != RayAction::kRead) d.pixel = RayAction::kTrace;
+        if (d.pixel == RayAction::kFill && !reserve(pixels, n.pixels)) {
+          pixel.invalidate();  // no memory for it: the launch shades from the layer under it
+          d.pixel = RayAction::kTrace;
+        }
+        if (d.pixel != RayAction::kTrace) d.pixels = (uint32_t*)pixels.ptr;
+      }
     }
     return d;
   }
@@ -646,6 +732,14 @@ struct ChainCaches {
       texel.valid = false;
       compact.valid = false;
     }
+    const bool below_pixel_filled = ray_filled || cull_filled || hit_filled ||
+                                    d.texel == RayAction::kFill || d.compact == RayAction::kFill;
+    if (have_pixel_key) {
+      pixel.commit(pixel_key, d.pixel, below_pixel_filled);
+    } else {
+      if (below_pixel_filled) pixel.valid = false;
+      pixel.have_prev = false;  // a launch without the layer came between two of a key
+    }
     n.ray_fills += ray_filled;
     n.ray_cached_frames += d.ray != RayAction::kTrace;
     n.cull_fills += cull_filled;
@@ -656,29 +750,33 @@ struct ChainCaches {
     n.texel_hits += d.texel == RayAction::kRead;
     n.compact_fills += d.compact == RayAction::kFill;
     n.compact_hits += d.compact == RayAction::kRead;
+    n.pixel_fills += d.pixel == RayAction::kFill;
+    n.pixel_hits += d.pixel == RayAction::kRead;
   }
 
   void invalidate() {
     ray.invalidate();
     cull.invalidate();
-    hit.invalidate();
-    texel.invalidate();
-    compact.invalidate();
+    invalidate_hit();
   }
   void invalidate_hit() {
     hit.invalidate();
-    texel.invalidate();
-    compact.invalidate();
+    invalidate_texel();
   }
   void invalidate_texel() {
     texel.invalidate();
-    compact.invalidate();
+    invalidate_compact();
   }
-  void invalidate_compact() { compact.invalidate(); }
+  void invalidate_compact() {
+    compact.invalidate();
+    pixel.invalidate();
+  }
+  void invalidate_pixel() { pixel.invalidate(); }
 
   // Freed by the host once the device has drained (an option lowered, the world going away).
   template <class Free>
   void release_hit(Free&& free_fn) {
+    pixels.release(free_fn);
     compact_recs.release(free_fn);
     hit_recs.release(free_fn);
     texel_recs.release(free_fn);
@@ -686,18 +784,25 @@ struct ChainCaches {
   }
   template <class Free>
   void release_texel(Free&& free_fn) {
+    pixels.release(free_fn);
     compact_recs.release(free_fn);
     texel_recs.release(free_fn);
     invalidate_texel();
   }
   template <class Free>
   void release_compact(Free&& free_fn) {
+    pixels.release(free_fn);
     compact_recs.release(free_fn);
-    compact.invalidate();
+    invalidate_compact();
+  }
+  template <class Free>
+  void release_pixel(Free&& free_fn) {
+    pixels.release(free_fn);
+    pixel.invalidate();
   }
   template <class Free>
   void release_all(Free&& free_fn) {
-    for (CacheBuf* b : {&dirs, &tile_recs, &cull_recs, &cull_wins, &hit_recs, &texel_recs, &compact_recs})
+    for (CacheBuf* b : {&pixels, &dirs, &tile_recs, &cull_recs, &cull_wins, &hit_recs, &texel_recs, &compact_recs})
       b->release(free_fn);
     invalidate();
   }

@@ -176,10 +176,16 @@ int launch_cast_rays(const FrameRec& f, const SphereRec* host_spheres, const Ray
 // and next_order are ignored (the caller links nothing), and dirs and cull_wins are not read.
 // texel_recs and compact_recs ride on such a launch in the same way: kFill, it also stores them;
 // kRead, it shades from them (compact: with bright_rep, the world's class table, never with ss > 0).
+// pixels rides on a launch that reads the texel records: kFill, that launch raises its status bits in
+// pixel_status in place of f.status and its band is then copied into pixels (k_pixels_copy), which
+// also ORs that word into f.status; kRead, the launch is that copy out of pixels and nothing else.
 int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
                  const DumpArgs* dump = nullptr, void* done_event = nullptr,
                  const TraceCaches* caches = nullptr, const AuxArgs* aux = nullptr,
                  int place_xstride = 0);
+// Whether k_pixels_copy can address f's band of output pixels (its units fit the grid): a launch
+// that cannot takes no part in the pixel layer.
+bool pixel_copy_fits(const FrameRec& f);
 // Fills ray_cache (ray_cache_bytes(tiles, rays) bytes, sfrt_raycache.h, of the grid
 // trace_tile_key names) with the primary directions of f's rays, tile-major, and tile_recs
 // (tile_rec_bytes(tiles) bytes) with the tiles' records.

@@ -140,6 +140,13 @@ struct sfrt_world {
   // SFRT_OPT_COMPACT_TEXELS: the compact layer on the texel cache (0: off; 1: launches at four pixels
   // per lane whose records travel in the arguments, the shape it was proven at; 2: every eligible one)
   int compact_texels = 1;
+  // SFRT_OPT_PIXEL_CACHE: the pixel layer on top of the chain's other layers (0: off; 1: launches
+  // that are not supersampled, carry their records in the arguments and draw from an atlas the compact
+  // layer can index, the shapes it was proven at; 2: every plain render_band launch)
+  int pixel_cache = 1;
+  // Every write of the atlas (sfrt_world_load_texture, the only one) counts here: the pixel layer's
+  // key holds it (sfrt_raycache.h PixelKey), no texel's value.
+  long long tex_generation = 0;
   // --- device resources ---
   hipStream_t stream = nullptr;
   uint32_t* d_tex = nullptr;  // texture atlas: every loaded slot, back to back
@@ -157,6 +164,7 @@ struct sfrt_world {
   size_t retired_tex_bytes = 0;
   static constexpr size_t kRetiredTexBytes = 64u << 20;
   int* d_status = nullptr;
+  int* d_pixel_status = nullptr;  // the pixel layers' status words, one per chain (caches[])
   sfrt::TileChains scheds;  // adaptive tile order (sfrt_sched.h), one chain per stream
   sfrt::TileSched dump_sched;  // sfrt_world_trace_points' own chain (never the frames')
   int cur_chain = 0;        // the chain of the launch between sched_begin and sched_end
@@ -231,6 +239,7 @@ struct sfrt_world {
     tex_written.release();
     tex_stage.release();
     (void)hipFree(d_status);
+    (void)hipFree(d_pixel_status);
     (void)hipDeviceSynchronize();
     for (int k = 0; k < kRing; k++) {
       (void)hipFree(d_spheres[k]);
@@ -432,8 +441,9 @@ struct sfrt_world {
   // part in the ray cache's policy -- it neither reads, fills nor invalidates the cache, and
   // sched_end commits nothing for it.
   // recs: the launch's records (the cull cache's key holds the fields the cull reads).
+  // pixels: a plain render_band launch, the only kind that takes part in the pixel layer.
   int sched_begin(sfrt::FrameRec& f, const std::vector<sfrt::SphereRec>& recs, hipStream_t s,
-                  bool aux = false) {
+                  bool aux = false, bool pixels = false) {
     long long tiles = 0;
     const long long key = tile_order_on ? sfrt::trace_tile_key(f, &tiles) : 0;
     sfrt::TileSchedPtrs p;
@@ -464,19 +474,28 @@ struct sfrt_world {
                                  (compact_texels == 1 && rays == 4 && f.n <= sfrt::kInlineSpheres);
       const bool compact = texels && compact_shape && !sfrt::kDiagnosticBuild && d_bright_rep &&
                            sfrt::compact_eligible(recs.data(), f.n, f.ss);
+      // The pixel layer: the option, a plain band the copy kernel can address, the status words.
+      // 1: the shapes the keep rule confirmed only (DESIGN.md 5 "Pixel layer").
+      const bool pixel_shape = pixel_cache == 2 ||
+                               (pixel_cache == 1 && f.ss == 0 && f.n <= sfrt::kInlineSpheres &&
+                                sfrt::compact_eligible(recs.data(), f.n, f.ss));
+      const bool pixel_layer = pixels && texels && pixel_shape && !sfrt::kDiagnosticBuild &&
+                               d_pixel_status && sfrt::pixel_copy_fits(f);
       const sfrt::CacheSizes sizes{sfrt::ray_cache_bytes(tiles, rays), sfrt::tile_rec_bytes(tiles),
                                    sfrt::cull_rec_bytes(tiles),
                                    sfrt::cull_win_bytes(tiles, f.n > sfrt::kInlineSpheres),
                                    sfrt::hit_cache_bytes(tiles, rays),
                                    texels ? sfrt::texel_cache_bytes(tiles, rays) : 0,
-                                   compact ? sfrt::compact_cache_bytes(tiles, rays) : 0};
+                                   compact ? sfrt::compact_cache_bytes(tiles, rays) : 0,
+                                   pixel_layer ? sfrt::pixel_cache_bytes(f.sub_w >> f.ss, f.sub_rows >> f.ss) : 0};
       // (the diagnostic builds exist to time the march: no hit cache)
       launch_caches = mine.begin(cull_key.ray, cull_key, sizes,
                                  cache_bytes_held() - mine.bytes_under_ray_budget(),
                                  hit_bytes_budgeted() - mine.bytes_under_hit_budget(),
                                  (long long)ray_cache_mb << 20,
                                  sfrt::kDiagnosticBuild ? 0 : hit_budget_bytes(), CacheDevice{s, f, recs},
-                                 texels ? &tex_key : nullptr, compact);
+                                 texels ? &tex_key : nullptr, compact, pixel_layer ? tex_generation : -1);
+      if (launch_caches.pixel != sfrt::RayAction::kTrace) launch_caches.pixel_status = d_pixel_status + cur_chain;
       if (launch_caches.compact != sfrt::RayAction::kTrace) {
         launch_caches.bright_rep = d_bright_rep;
         launch_caches.bright_classes = sfrt::BrightClasses::get().classes();
@@ -561,6 +580,9 @@ struct sfrt_world {
   long long compact_bytes_held() const {
     return held([](const sfrt::ChainCaches& c) { return c.compact_bytes(); });
   }
+  long long pixel_bytes_held() const {
+    return held([](const sfrt::ChainCaches& c) { return c.pixel_bytes(); });
+  }
   long long hit_bytes_budgeted() const {  // with the texel records: what the option limits
     return held([](const sfrt::ChainCaches& c) { return c.bytes_under_hit_budget(); });
   }
@@ -595,12 +617,15 @@ struct sfrt_world {
   // go; else SFRT_OPT_RAY_CACHE_MB, every cache goes).  The chains' streams may be gone
   // (sfrt_sched.h), so the host waits for the device.
   // texel_only: SFRT_OPT_TEXEL_CACHE, that layer (and the compact one on it) alone;
-  // compact_only: SFRT_OPT_COMPACT_TEXELS, that layer alone.
-  int release_caches(bool hit_only, bool texel_only = false, bool compact_only = false) {
+  // compact_only: SFRT_OPT_COMPACT_TEXELS, that layer (and the pixel layer on it) alone;
+  // pixel_only: SFRT_OPT_PIXEL_CACHE, that layer alone.
+  int release_caches(bool hit_only, bool texel_only = false, bool compact_only = false,
+                     bool pixel_only = false) {
     HIP_TRY(hipDeviceSynchronize());
     const auto free_now = [](void* p) { return hipFree(p) == hipSuccess; };
     for (sfrt::ChainCaches& c : caches) {
-      if (compact_only) c.release_compact(free_now);
+      if (pixel_only) c.release_pixel(free_now);
+      else if (compact_only) c.release_compact(free_now);
       else if (texel_only) c.release_texel(free_now);
       else if (hit_only) c.release_hit(free_now);
       else c.release_all(free_now);
@@ -752,6 +777,13 @@ int sfrt_world_create(int hip_device, sfrt_world** out) {
     delete w;
     return SFRT_E_HIP;
   }
+  // (a failure is no error of the world: the pixel layer is never filled)
+  if (hipMalloc(&w->d_pixel_status, sizeof(int) * sfrt::TileChains::kChains) != hipSuccess ||
+      hipMemset(w->d_pixel_status, 0, sizeof(int) * sfrt::TileChains::kChains) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(w->d_pixel_status);
+    w->d_pixel_status = nullptr;
+  }
   w->upload_bright_rep();
   *out = w;
   return SFRT_OK;
@@ -800,6 +832,7 @@ int sfrt_world_load_texture(sfrt_world* w, int slot, const uint8_t* rgba, int te
     return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
   const size_t bytes = (size_t)tex_w * tex_h * 4;
+  w->tex_generation++;  // whatever becomes of this call: no cached pixel outlives it
   w->tex_host[slot].assign(rgba, rgba + bytes);
   w->tex_w[slot] = tex_w;
   w->tex_h[slot] = tex_h;
@@ -1019,6 +1052,19 @@ int sfrt_world_set_option(sfrt_world* w, int option, int value) {
     w->compact_texels = value;
     return SFRT_OK;
   }
+  if (option == SFRT_OPT_PIXEL_CACHE) {
+    if (value < 0 || value > 2) return SFRT_E_INVALID;
+    if (value < w->pixel_cache) {  // (lowered: pixels of a shape no longer served would stay held)
+      if (w->pixel_bytes_held() > 0) {
+        sfrt::DeviceGuard g(w->device);
+        const int rc = w->release_caches(false, false, false, true);
+        if (rc) return rc;
+      }
+      for (sfrt::ChainCaches& c : w->caches) c.invalidate_pixel();
+    }
+    w->pixel_cache = value;
+    return SFRT_OK;
+  }
   return SFRT_E_INVALID;
 }
 
@@ -1068,6 +1114,15 @@ int sfrt_world_compact_cache_stats(const sfrt_world* w, int64_t* fills, int64_t*
   return SFRT_OK;
 }
 
+int sfrt_world_pixel_cache_stats(const sfrt_world* w, int64_t* fills, int64_t* hits, int64_t* bytes) {
+  if (!w || !fills || !hits || !bytes) return SFRT_E_INVALID;
+  std::lock_guard<std::mutex> lk(w->mu);
+  *fills = w->cache_stats.pixel_fills;
+  *hits = w->cache_stats.pixel_hits;
+  *bytes = w->pixel_bytes_held();
+  return SFRT_OK;
+}
+
 int sfrt_world_tile_record_bytes(const sfrt_world* w, int64_t* bytes) {
   if (!w || !bytes) return SFRT_E_INVALID;
   std::lock_guard<std::mutex> lk(w->mu);
@@ -1087,6 +1142,7 @@ int sfrt_world_get_option(const sfrt_world* w, int option, int* value) {
     case SFRT_OPT_HIT_CACHE_MB: *value = w->hit_cache_mb; return SFRT_OK;
     case SFRT_OPT_TEXEL_CACHE: *value = w->texel_cache; return SFRT_OK;
     case SFRT_OPT_COMPACT_TEXELS: *value = w->compact_texels; return SFRT_OK;
+    case SFRT_OPT_PIXEL_CACHE: *value = w->pixel_cache; return SFRT_OK;
     default: return SFRT_E_INVALID;
   }
 }
@@ -1213,7 +1269,7 @@ static int render_band_body(sfrt_world* w, void* dev_pixels, int64_t pitch_bytes
   if (rc) return rc;
   // after the last texture upload (queued on w->stream, where the other launches run)
   HIP_TRY(w->tex_written.before_read(s));
-  if ((rc = w->sched_begin(f, recs, s, with_aux))) return rc;
+  if ((rc = w->sched_begin(f, recs, s, with_aux, !with_aux))) return rc;
   if ((rc = w->sched_end(f, s, sfrt::launch_trace(f, recs.data(), s, nullptr, w->ring_event(),
                                                   &w->launch_caches, with_aux ? &a : nullptr) == 0)))
     return rc;
@@ -1702,7 +1758,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 16; }
+int sfrt_version(void) { return 17; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <type_traits>
 
 #include "sfrt_device.h"
@@ -1520,6 +1521,77 @@ __global__ __launch_bounds__(64, 8) void k_shade_compact(FrameRec f) {
   }
 }
 
+// The pixel layer's one kernel (sfrt_raycache.h PixelKey, ChainCaches; DESIGN.md 5 "Pixel
+// layer"): a band of finished pixels between the caller's frame (base and pitch the launch's) and
+// the layer (rows packed), TO_FRAME from the layer, else into it.  No march, no tiles, no CullRec:
+// the geometry is the arguments'.  A row is `chunks` whole 16-byte chunks (Dwords<4>: dword
+// alignment, whatever the base, the pitch and the width) and, where width % 4 != 0, one tail unit
+// that goes per pixel; unit g of the launch is unit g % units_per_row of row g / units_per_row.  A
+// lane takes CH units WG apart, so that a wave's CH accesses are contiguous each, and issues all
+// their loads before its first store.  NT: the layer is loaded non-temporally (TO_FRAME only).
+// The launch's first lane ORs the layer's status word into the world's when it is not zero.
+struct PixelCopyArgs {
+  uint32_t* frame;     // the band's first pixel
+  uint32_t* layer;     // width * rows pixels
+  long long pitch;     // of the frame, in pixels
+  int* layer_status;
+  int* world_status;
+  uint32_t width, rows;
+  uint32_t chunks;     // width / 4
+  uint32_t units_per_row;  // chunks + (width % 4 != 0)
+  uint32_t units;      // rows * units_per_row (< 2^31: launch_trace)
+  uint32_t pad;        // 64 bytes, one cache line: the scalar loads are issued together, one wait
+};
+static_assert(sizeof(PixelCopyArgs) == 64, "one line of kernel arguments");
+
+template <bool TO_FRAME, int WG, int CH, bool NT>
+__global__ __launch_bounds__(WG) void k_pixels_copy(PixelCopyArgs a) {
+  using Vec = typename Dwords<4>::type;
+  const uint32_t tid = threadIdx.x;
+  if (blockIdx.x == 0 && tid == 0) {
+    const int st = *a.layer_status;
+    if (st != 0) atomicOr(a.world_status, st);
+  }
+  const uint32_t g0 = blockIdx.x * (uint32_t)(WG * CH) + tid;
+  const uint32_t tail = a.width - a.chunks * 4u;
+  const uint32_t* src[CH];
+  uint32_t* dst[CH];
+  uint32_t count[CH];  // 4: a whole chunk; 1..3: the row's tail; 0: past the band
+  Vec whole[CH];
+  uint32_t part[CH][3];
+#pragma unroll
+  for (int k = 0; k < CH; k++) {
+    const uint32_t g = g0 + (uint32_t)(k * WG);
+    const uint32_t row = g / a.units_per_row, unit = g - row * a.units_per_row;
+    uint32_t* const fr = a.frame + (long long)row * a.pitch + unit * 4u;
+    uint32_t* const la = a.layer + (size_t)row * a.width + unit * 4u;
+    src[k] = TO_FRAME ? la : fr;
+    dst[k] = TO_FRAME ? fr : la;
+    count[k] = g >= a.units ? 0u : unit < a.chunks ? 4u : tail;
+  }
+#pragma unroll
+  for (int k = 0; k < CH; k++) {
+    if (count[k] == 4u) {
+      if constexpr (NT && TO_FRAME) whole[k] = __builtin_nontemporal_load((const Vec*)src[k]);
+      else whole[k] = *(const Vec*)src[k];
+    } else {
+#pragma unroll
+      for (uint32_t p = 0; p < 3; p++)
+        if (p < count[k]) part[k][p] = src[k][p];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < CH; k++) {
+    if (count[k] == 4u) {
+      *(Vec*)dst[k] = whole[k];
+    } else {
+#pragma unroll
+      for (uint32_t p = 0; p < 3; p++)
+        if (p < count[k]) dst[k][p] = part[k][p];
+    }
+  }
+}
+
 // The DUMP instantiations of both (sfrt_world_trace_points): the shipped march and
 // shading, with the float intermediates of listed pixels written out (never probed).
 template <int R>
@@ -1813,6 +1885,63 @@ void with_ss(int ss, F fn) {
 
 }  // namespace
 
+namespace {
+
+// The shipped variant of k_pixels_copy (DESIGN.md 5 "Pixel layer": the A/B of the workgroup size,
+// the units per lane and the layer's load policy -- one wave per workgroup and four units per lane
+// was the fastest of the six plain variants at 4K, every non-temporal one 1.6 to 3.3 us slower).
+constexpr int kPixelCopyWg = 64, kPixelCopyUnits = 4;
+constexpr bool kPixelCopyNt = false;
+
+template <bool TO_FRAME, int WG, int CH, bool NT>
+void launch_pixels_copy_as(const PixelCopyArgs& a, hipStream_t s, hipEvent_t ev) {
+  const dim3 gr((a.units + (uint32_t)(WG * CH) - 1u) / (uint32_t)(WG * CH)), b(WG);
+  if (ev) hipExtLaunchKernelGGL((k_pixels_copy<TO_FRAME, WG, CH, NT>), gr, b, 0, s, nullptr, ev, 0, a);
+  else hipLaunchKernelGGL((k_pixels_copy<TO_FRAME, WG, CH, NT>), gr, b, 0, s, a);
+}
+
+// The band of f between the caller's frame and `layer` (pixel_cache_bytes of the band's output
+// pixels); ev (may be null): the launch's stop event.
+template <bool TO_FRAME>
+int launch_pixels_copy(const FrameRec& f, uint32_t* layer, int* layer_status, hipStream_t s, hipEvent_t ev) {
+  if (!pixel_copy_fits(f) || !layer || !layer_status || !f.out || !f.status) return -1;
+  PixelCopyArgs a{};
+  a.frame = f.out;
+  a.layer = layer;
+  a.pitch = f.out_pitch;
+  a.layer_status = layer_status;
+  a.world_status = f.status;
+  a.width = (uint32_t)(f.sub_w >> f.ss);
+  a.rows = (uint32_t)(f.sub_rows >> f.ss);
+  a.chunks = a.width / 4u;
+  a.units_per_row = a.chunks + (a.width % 4u != 0u ? 1u : 0u);
+  a.units = a.rows * a.units_per_row;
+#ifdef SFRT_PIXEL_AB  // an A/B build: SFRT_AB_KNOB = 100 * WG + 10 * units per lane + NT
+  static const int knob = std::getenv("SFRT_AB_KNOB") ? std::atoi(std::getenv("SFRT_AB_KNOB")) : 0;
+  switch (TO_FRAME ? knob : 0) {
+#define SFRT_PIXEL_VARIANT(WG, CH, NT) \
+    case 100 * WG + 10 * CH + NT: launch_pixels_copy_as<TO_FRAME, WG, CH, NT != 0>(a, s, ev); break;
+    SFRT_PIXEL_VARIANT(64, 1, 0) SFRT_PIXEL_VARIANT(64, 2, 0)
+    SFRT_PIXEL_VARIANT(256, 1, 0) SFRT_PIXEL_VARIANT(256, 2, 0) SFRT_PIXEL_VARIANT(256, 4, 0)
+    SFRT_PIXEL_VARIANT(64, 1, 1) SFRT_PIXEL_VARIANT(64, 2, 1) SFRT_PIXEL_VARIANT(64, 4, 1)
+    SFRT_PIXEL_VARIANT(256, 1, 1) SFRT_PIXEL_VARIANT(256, 2, 1) SFRT_PIXEL_VARIANT(256, 4, 1)
+#undef SFRT_PIXEL_VARIANT
+    default: launch_pixels_copy_as<TO_FRAME, kPixelCopyWg, kPixelCopyUnits, kPixelCopyNt>(a, s, ev); break;
+  }
+#else
+  launch_pixels_copy_as<TO_FRAME, kPixelCopyWg, kPixelCopyUnits, kPixelCopyNt>(a, s, ev);
+#endif
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace
+
+bool pixel_copy_fits(const FrameRec& f) {
+  if (f.ss < 0 || f.ss > 2 || f.sub_w <= 0 || f.sub_rows <= 0) return false;
+  const long long w = f.sub_w >> f.ss, rows = f.sub_rows >> f.ss;
+  return w > 0 && rows > 0 && rows * ((w + 3) / 4) <= 0x7fffffffLL - 1024;
+}
+
 int launch_ray_fill(const FrameRec& f, float* ray_cache, TileRec* tile_recs, void* stream) {
   long long tiles = 0;
   if (!ray_cache || !tile_recs || f.ss < 0 || f.ss > 2 || trace_tile_key(f, &tiles) == 0 || tiles > 0x7fffffffLL)
@@ -1879,11 +2008,24 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
   if (compact_mode && (texel_mode != 2 || f.ss != 0 || !c.bright_rep || c.bright_classes == 0 ||
                        c.bright_classes >= kCompactClassLimit))
     return -1;
+  // the pixel layer rides on a launch that reads the texel records (and the compact ones, if it has
+  // them): 1 that launch with the layer's status word, then its band copied into the layer; 2 the
+  // band copied out of it and nothing else
+  const int pixel_mode = c.pixel == RayAction::kRead ? 2 : c.pixel == RayAction::kFill ? 1 : 0;
+  if ((pixel_mode != 0) != (c.pixels != nullptr)) return -1;
+  if (pixel_mode && (texel_mode != 2 || compact_mode == 1 || !c.pixel_status || !pixel_copy_fits(f))) return -1;
+  if (pixel_mode == 2)
+    return launch_pixels_copy<true>(f, c.pixels, c.pixel_status, s,
+                                    f.n > kInlineSpheres ? (hipEvent_t)done_event : nullptr);
   // (2: the caller linked nothing of the tile order into f, but the grid is the ordered one)
   const bool ordered = hit_mode == 2 || f.tile_cost != nullptr;  // linked into the tile-order chain
   const int rays = trace_rays(f, ordered);
   FrameRec g = f;
   g.tiles_x = (f.sub_w + rays * kTile - 1) / (rays * kTile);
+  if (pixel_mode == 1) {  // the status bits this launch raises are the layer's to keep
+    if (hipMemsetAsync(c.pixel_status, 0, sizeof(int), s) != hipSuccess) return -1;
+    g.status = c.pixel_status;
+  }
   const long long tiles = tiles_y * g.tiles_x;
   long long key_tiles = 0;
   if (!ordered || trace_tile_key(f, &key_tiles) == 0 || key_tiles != tiles) {
@@ -1980,7 +2122,9 @@ int launch_trace(const FrameRec& f, const SphereRec* host_spheres, void* stream,
       }
     });
   });
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  if (hipGetLastError() != hipSuccess) return -1;
+  if (pixel_mode == 1) return launch_pixels_copy<false>(f, c.pixels, c.pixel_status, s, nullptr);
+  return 0;
 }
 
 void trace_views_grid(const FrameRec& f, int* tiles_x, long long* tiles) {

@@ -28,6 +28,7 @@ SFRT_OPT_RAY_CACHE_MB = 5  # MiB per world for cached primary ray directions (51
 SFRT_OPT_HIT_CACHE_MB = 6  # MB (10^6 B) per world for cached march results, a budget of its own (512, 0 off)
 SFRT_OPT_TEXEL_CACHE = 7  # the texel cache on the hit cache, under the hit cache's budget (1 default, 0 off)
 SFRT_OPT_COMPACT_TEXELS = 8  # the 4-byte compact layer on the texel cache (0 off, 1 default: 4 px per lane and <= 64 spheres, 2 every eligible launch)
+SFRT_OPT_PIXEL_CACHE = 9  # the finished pixels of a scene at rest, copied until a texture is loaded (0 off, 1 default: no supersampling, <= 64 spheres, an atlas the compact layer can index; 2 every plain band)
 ERRORS = {
     0: "SFRT_OK", -1: "SFRT_E_INVALID", -2: "SFRT_E_EMPTY", -3: "SFRT_E_NO_TEXTURE",
     -4: "SFRT_E_TOO_MANY", -5: "SFRT_E_HIP", -6: "SFRT_E_MARCH_LIMIT", -7: "SFRT_E_TEXEL",
@@ -77,6 +78,7 @@ ABI_SYMBOLS = (
     "sfrt_world_cull_cache_stats", "sfrt_world_hit_cache_stats",
     "sfrt_voxel_render_views", "sfrt_voxel_render_views_aux", "sfrt_voxel_sort_dynamics",
     "sfrt_world_texel_cache_stats", "sfrt_world_compact_cache_stats",
+    "sfrt_world_pixel_cache_stats",
 )
 
 SFRT_MAX_VIEWS = 1024
@@ -224,6 +226,8 @@ def lib() -> ctypes.CDLL:
                                           P(ctypes.c_int64)], c_int),
         "sfrt_world_compact_cache_stats": ([W, P(ctypes.c_int64), P(ctypes.c_int64),
                                             P(ctypes.c_int64)], c_int),
+        "sfrt_world_pixel_cache_stats": ([W, P(ctypes.c_int64), P(ctypes.c_int64),
+                                          P(ctypes.c_int64)], c_int),
         "sfrt_world_submit_frame": ([W, vp, P(ctypes.c_int64)], c_int),
         "sfrt_world_wait_frame": ([W, ctypes.c_int64], c_int),
         "sfrt_host_alloc": ([P(vp), ctypes.c_int64], c_int),
@@ -535,6 +539,15 @@ class World:
         f, h, b = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         _check(lib().sfrt_world_compact_cache_stats(self._h, ctypes.byref(f), ctypes.byref(h),
                                                     ctypes.byref(b)), "compact_cache_stats")
+        return {"fills": f.value, "hits": h.value, "bytes": b.value}
+
+    def pixel_cache_stats(self) -> dict:
+        """The pixel layer's counters (sfrt_world_pixel_cache_stats): launches whose band was copied
+        into the layer, launches that were a copy out of it, and the device bytes the cached pixels
+        hold now."""
+        f, h, b = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().sfrt_world_pixel_cache_stats(self._h, ctypes.byref(f), ctypes.byref(h),
+                                                  ctypes.byref(b)), "pixel_cache_stats")
         return {"fills": f.value, "hits": h.value, "bytes": b.value}
 
     def set_scene(self, scene, width: int, height: int) -> None:

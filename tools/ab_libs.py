@@ -4,8 +4,10 @@
 (lib@R forces R pixels per lane, SFRT_OPT_RAYS_PER_LANE; lib^O sets SFRT_OPT_TILE_ORDER=O on every
 renderer; lib#K sets SFRT_AB_KNOB=K for an
 experimental build that reads it -- r2_ab28 read it as SFRT_SPLIT; the product reads none; lib%M sets
-SFRT_OPT_HIT_CACHE_MB=M, lib~T sets SFRT_OPT_TEXEL_CACHE=T and lib+C sets SFRT_OPT_COMPACT_TEXELS=C on
-the sphere world, where the library has the option)
+SFRT_OPT_HIT_CACHE_MB=M, lib~T sets SFRT_OPT_TEXEL_CACHE=T, lib+C sets SFRT_OPT_COMPACT_TEXELS=C and
+lib=P sets SFRT_OPT_PIXEL_CACHE=P on the sphere world, where the library has the option; --supersample
+S sets SFRT_OPT_SUPERSAMPLE on it for every library.  In a -DSFRT_PIXEL_AB build lib#K picks the
+k_pixels_copy variant: K = 100 x workgroup size + 10 x units per lane + non-temporal loads)
 
 Each round starts one process per library (SFRT_LIB=<lib>, the same sfrt.py), which
 times every case with HIP events (median kernel time, event-pair overhead subtracted;
@@ -31,6 +33,8 @@ CASES = {
     "8k": (7680, 4320, "lcg64", (0.0, 0.0), False),
     "1080": (1920, 1080, "default10", (0.0, 0.0), False),
     "4k_256": (3840, 2160, "lcg256", (0.0, 0.0), False),
+    # every sphere on a texture slot of its own (the atlas too large for the compact layer)
+    "4k_alltex": (3840, 2160, "lcg64", (0.0, 0.0), "alltex"),
     # the other renderers: scene = "voxel:<x>,<y>,<z>" / "glsl", pose = rot
     "vox1080": (1920, 1080, "voxel:15.5,1.9,15.5", (0.0, 0.0), False),
     "vox4k": (3840, 2160, "voxel:15.5,1.9,15.5", (0.0, 0.0), False),
@@ -82,6 +86,13 @@ def renderer(sfrt, scenes, sname, pose, width, height, rays):
     return None, None
 
 
+def all_textures(w, scenes, sc):
+    """bench.py's all-textures extension: the five textures in slots 0-4, sphere k on slot k % 5."""
+    for slot, (tex, tw, th) in enumerate(scenes.load_all_textures()):
+        w.load_texture(tex, tw, th, slot=slot)
+    w.set_sphere_textures(scenes.all_texture_slots(sc.spheres.shape[0]))
+
+
 def child(cases, reps, rays):
     sys.path.insert(0, os.path.join(ROOT, "sfml-software-raytracer_amd"))
     import numpy as np
@@ -100,6 +111,10 @@ def child(cases, reps, rays):
         w.set_option(sfrt.SFRT_OPT_TEXEL_CACHE, int(os.environ["SFRT_AB_TEXEL_CACHE"]))
     if os.environ.get("SFRT_AB_COMPACT_TEXELS") is not None:  # "lib+C"
         w.set_option(sfrt.SFRT_OPT_COMPACT_TEXELS, int(os.environ["SFRT_AB_COMPACT_TEXELS"]))
+    if os.environ.get("SFRT_AB_PIXEL_CACHE") is not None:  # "lib=P"
+        w.set_option(sfrt.SFRT_OPT_PIXEL_CACHE, int(os.environ["SFRT_AB_PIXEL_CACHE"]))
+    if os.environ.get("SFRT_AB_SUPERSAMPLE") is not None:  # --supersample
+        w.set_option(sfrt.SFRT_OPT_SUPERSAMPLE, int(os.environ["SFRT_AB_SUPERSAMPLE"]))
     pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
              for _ in range(64)]
     for a, b in pairs:
@@ -120,6 +135,9 @@ def child(cases, reps, rays):
             sc = scenes.SCENES[sname]().posed(*pose)
             w.set_scene(sc, width, height)
         cam_pos = sc.cam_pos if sc is not None else None
+        if turn == "alltex":
+            all_textures(w, scenes, sc)
+            turn = False
 
         def move(k):  # frame k's camera
             if turn == "walk":
@@ -162,6 +180,7 @@ def main():
     ap.add_argument("--cases", default="4k,4k_rot,4k_turn,8k,1080")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--rays", type=int, default=0, help="(child) SFRT_OPT_RAYS_PER_LANE")
+    ap.add_argument("--supersample", type=int, default=0, help="SFRT_OPT_SUPERSAMPLE of the sphere world")
     a = ap.parse_args()
     cases = a.cases.split(",")
     if a.child:
@@ -176,6 +195,7 @@ def main():
             probe = lib.endswith("!")
             spec, _, order = lib.rstrip("!").partition("^")  # "^O": 8f renderers' tile order
             spec, _, knob = spec.partition("#")  # "#K": SFRT_AB_KNOB=K for an A/B build
+            spec, _, pixel = spec.partition("=")  # "=P": SFRT_OPT_PIXEL_CACHE=P
             spec, _, compact = spec.partition("+")  # "+C": SFRT_OPT_COMPACT_TEXELS=C
             spec, _, texel = spec.partition("~")  # "~T": SFRT_OPT_TEXEL_CACHE=T
             spec, _, hit_mb = spec.partition("%")  # "%M": SFRT_OPT_HIT_CACHE_MB=M
@@ -191,6 +211,10 @@ def main():
                 env["SFRT_AB_TEXEL_CACHE"] = texel
             if compact:
                 env["SFRT_AB_COMPACT_TEXELS"] = compact
+            if pixel:
+                env["SFRT_AB_PIXEL_CACHE"] = pixel
+            if a.supersample:
+                env["SFRT_AB_SUPERSAMPLE"] = str(a.supersample)
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--libs", lib,
                                 "--cases", a.cases, "--reps", str(a.reps), "--rays", rays or "0"],
                                capture_output=True, text=True, env=env, timeout=600)

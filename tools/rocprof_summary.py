@@ -1,7 +1,7 @@
 """Summarise rocprofv3 CSV output of bench.py runs into profiles/.
 
     python tools/rocprof_summary.py --trace DIR --fetch DIR --write DIR --tag r1 [--sq DIR ...]
-                                    [--kernel k_trace|k_glsl|k_voxel|k_shade_hits|k_shade_texels|k_shade_compact] [--family k_trace] [--out profiles]
+                                    [--kernel k_trace|k_glsl|k_voxel|k_shade_hits|k_shade_texels|k_shade_compact|k_pixels_copy] [--family k_trace] [--out profiles]
 
 Writes
   profiles/<tag>_kernel_stats_by_grid.csv  per (kernel, grid size): calls, avg/min/max ns
@@ -29,13 +29,18 @@ def pixels_per_thread(kernel_name: str) -> int:
     """Pixels one work-item writes: R for k_trace_window_r<R> / k_trace_window_list<R> and
     their _ss<R, SS> (samples), _rc<R, SS> (ray cache), _cc<R, SS> (cull cache) and _hf<R, SS> (hit
     cache, storing) kernels, and for k_shade_hits[_list][_tf]<R, SS> (hit cache, reading) and
-    k_shade_texels<R, SS> (texel cache, reading), k_shade_texels_cf<R> and k_shade_compact<R> (compact layer)
+    k_shade_texels<R, SS> (texel cache, reading), k_shade_texels_cf<R> and k_shade_compact<R> (compact layer);
+    4 * CH for k_pixels_copy<TO_FRAME, WG, CH, NT> (pixel layer: its grid is rounded up to whole workgroups)
     (round 1: k_trace_window_r<SLOTS, R, ...>), else 1."""
     m = re.search(r"k_trace_window_(?:r|list)<\s*(\d+)\s*>", kernel_name) or \
         re.search(r"k_trace_window_(?:r|list)_(?:ss|rc|cc|hf)<\s*(\d+)\s*,", kernel_name) or \
         re.search(r"k_shade_(?:hits(?:_list)?(?:_tf)?|texels)<\s*(\d+)\s*,", kernel_name) or \
         re.search(r"k_shade_(?:compact|texels_cf)<\s*(\d+)\s*>", kernel_name) or \
         re.search(r"k_trace_window_r<\s*\d+\s*,\s*(\d+)", kernel_name)
+    # k_pixels_copy<TO_FRAME, WG, CH, NT> (pixel layer): CH units of four pixels per work-item
+    c = re.search(r"k_pixels_copy<\s*\w+\s*,\s*\d+\s*,\s*(\d+)", kernel_name)
+    if c:
+        return 4 * int(c.group(1))
     return int(m.group(1)) if m else 1
 
 
