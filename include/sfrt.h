@@ -1045,6 +1045,45 @@ SFRT_API int sfrt_glsl_cast_rays_device(sfrt_glsl* g, const float* dev_dirs, int
 SFRT_API int sfrt_glsl_cast_rays(sfrt_glsl* g, const float* dirs, int64_t count,
                                  const sfrt_ray_hits* out);
 
+/* ---- a batch of camera views of the shader in one launch ----
+ * sfrt_world_render_views for the GLSL renderer: each view a whole width x height frame from a
+ * camera of its own into a device target of its own (sfrt_view, SFRT_MAX_VIEWS: the sphere
+ * batch's), all views in one kernel launch, with one host table build and one upload.
+ * Definition: with the shader as it stands at the call, view k receives exactly the bytes that
+ *   sfrt_glsl_set_uniform(g, "campos",   views[k].cam.pos, 3);
+ *   sfrt_glsl_set_uniform(g, "rotation", (cam.rotation, cam.hrotation), 2);
+ *   sfrt_glsl_set_uniform(g, "fov",      (cam.fov_h, cam.fov_v), 2);
+ *   sfrt_glsl_draw(g, views[k].dev_pixels, width, height, pitch_bytes, 0, height, s);
+ * would write on a copy of that shader (the aux call: sfrt_glsl_draw_aux with planes[k]), and the
+ * call writes no other byte.  The `size` uniform and every scene uniform (the counts, spheres, uvs,
+ * lights, the ground) are the shader's own for all views.  Whole frames only.  `flags` must be 0:
+ * the shader sorts nothing per camera, so no flag is defined.
+ * The shader itself is left as it was: its uniform block (sfrt_glsl_get_uniforms returns the same
+ * bytes), the tables a draw has staged and the tile chains -- a sfrt_glsl_draw after the batch with
+ * no setter in between writes the bytes it wrote before and stages nothing again.
+ * Asynchronous on `hip_stream` with sfrt_glsl_draw's stream semantics; the march-cap bit of every
+ * view goes into the shader's status word (sfrt_glsl_check).  SFRT_OPT_SUPERSAMPLE is honoured
+ * (`size` scaled by S as in a draw; planes: the first sample's, as above); the launch is row-major
+ * within a view and view-major across views, so SFRT_OPT_TILE_ORDER has no influence, no chain is
+ * joined and the recorded tile costs stay.
+ * count == 0 returns SFRT_OK with nothing queued.  SFRT_E_INVALID, with nothing queued or written:
+ * a NULL shader or `views`, count < 0 or > SFRT_MAX_VIEWS, flags != 0, a width or height
+ * sfrt_glsl_draw would refuse, pitch_bytes not a multiple of 4 or below 4*width, a NULL or not
+ * 4-byte-aligned dev_pixels in any view, a camera whose pos, rotation, hrotation, fov_h or fov_v a
+ * draw would refuse as uniforms in any view, scene uniforms a draw would refuse, (aux) NULL
+ * `planes`, an entry with all three planes NULL or with a pitch sfrt_glsl_draw_aux would refuse, or
+ * a grid the device cannot be given in one launch (more than 2^31 - 1 tiles over all views, or more
+ * than 2^26 - 1 tiles in one, counted on the sample grid when supersampled).  SFRT_E_NO_TEXTURE
+ * when there is no ground.  Calls serialise on the shader's mutex.  Targets (and planes) that
+ * overlap are the caller's responsibility. */
+SFRT_API int sfrt_glsl_render_views(sfrt_glsl* g, const sfrt_view* views, int count,
+                                    int width, int height, int64_t pitch_bytes,
+                                    int flags, void* hip_stream);
+SFRT_API int sfrt_glsl_render_views_aux(sfrt_glsl* g, const sfrt_view* views,
+                                        const sfrt_aux_planes* planes /* count entries */,
+                                        int count, int width, int height,
+                                        int64_t pitch_bytes, int flags, void* hip_stream);
+
 /* SFRT_OPT_TILE_ORDER as for sfrt_world, on (1) by default: sfrt_glsl_draw dispatches 8x8
  * tiles longest-first by the metaball-march steps of two frames back (same bytes; 1-6 % faster
  * on the round-4 kernel); 0 = row-major.  sfrt_glsl_draw_image is row-major.

@@ -701,6 +701,25 @@ class Shader {
                     int height) {
     check(sfrt_glsl_draw_image_aux(g_, pixels, depth, sphere, steps, width, height), "draw_image_aux");
   }
+  // A batch of whole frames of this shader, one camera and one device target per view, in one
+  // launch (sfrt.h sfrt_glsl_render_views): view k is the frame that setUniform("campos" /
+  // "rotation" / "fov" from views[k].cam) + draw(...) would write, and this shader's own uniforms
+  // are left as they are.  The Aux call writes planes[k] beside view k (one entry per view).
+  void drawViews(const std::vector<sfrt_view>& views, int width, int height, int64_t pitch_bytes,
+                 void* hip_stream) {
+    if (views.empty()) return;  // nothing to queue (an empty vector's data() may be null)
+    check(sfrt_glsl_render_views(g_, views.data(), (int)views.size(), width, height, pitch_bytes, 0,
+                                 hip_stream),
+          "render_views");
+  }
+  void drawViewsAux(const std::vector<sfrt_view>& views, const std::vector<sfrt_aux_planes>& planes,
+                    int width, int height, int64_t pitch_bytes, void* hip_stream) {
+    if (planes.size() != views.size()) throw Error(SFRT_E_INVALID, "render_views_aux");
+    if (views.empty()) return;
+    check(sfrt_glsl_render_views_aux(g_, views.data(), planes.data(), (int)views.size(), width,
+                                     height, pitch_bytes, 0, hip_stream),
+          "render_views_aux");
+  }
   // The shader's Raycast(campos, r->dir, 1) (rayShader.frag:63-161) for one ray: reads r->dir
   // (un-normalised), fills r->pos and r->c.  Every ray starts at the campos uniform: r->pos is
   // not read (sfrt.h sfrt_glsl_cast_rays).  One launch and one wait per call; batches go

@@ -107,6 +107,24 @@ struct GlslRays {
   uint32_t* rgba;
 };
 
+// A batch of camera views in one launch (sfrt_glsl_render_views[_aux]): view k's
+// record at dev_views[k], the per-camera part of a GlslFrame under the frame's own field names --
+// what sfrt_glsl.cpp's camera_terms derives from campos, rotation and fov (and `size`) -- with the
+// view's target and, for the plane-writing kernels, its planes.  Everything else (the counts, the
+// tables, the ground, the size, the pitch, the status word) is the launch's one GlslFrame.
+struct GlslViewRec {
+  float campos[3];
+  float fwd[3], right[3], up[3];
+  float fov_x, fov_y, hk, vk;
+  int32_t cam_negzero;
+  int32_t wall_start;
+  float wall_cull_margin;
+  int32_t pad;
+  uint32_t* out;
+  GlslAux aux;                         // all null for the plain kernels
+};
+static_assert(sizeof(GlslViewRec) == 136, "the host's table layout (sfrt_glsl.cpp)");
+
 // Tile grid of the ordered GLSL kernel for f: key (> 0) and tile count.
 long long glsl_tile_key(const GlslFrame& f, long long* tiles);
 // done_event (hipEvent_t, may be null): recorded by the launch's own completion (its stop event).
@@ -117,5 +135,14 @@ int launch_glsl(const GlslFrame& f, void* stream, void* done_event = nullptr,
 // wall pass's host terms (cam_negzero, wall_start, wall_cull_margin), the tables and the status
 // word; the ground's mip chain only when rays.rgba is set.  rays.count in [1, 2^31).
 int launch_glsl_rays(const GlslFrame& f, const GlslRays& rays, void* stream, void* done_event = nullptr);
+// Whether `count` views of f's whole frame (row0 0, rows = height) fit one launch: at most
+// 2^26 - 1 tiles a view (x) and 2^31 - 1 over all views, as the other two renderers' batches.
+bool glsl_views_grid_ok(const GlslFrame& f, int count);
+// One launch for `count` views of the frame f describes (no tile order): workgroup (x, y) is tile
+// x, row-major, of view y.  Of f the per-camera fields and out are not read; dev_views: the table,
+// staged earlier on the same stream; aux: the plane-writing kernels, every record's planes not
+// all null.
+int launch_glsl_views(const GlslFrame& f, const GlslViewRec* dev_views, int count, bool aux,
+                      void* stream, void* done_event = nullptr);
 
 }  // namespace sfrt

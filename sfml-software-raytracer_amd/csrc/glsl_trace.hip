@@ -89,7 +89,10 @@ constexpr float kThrMul = 0x1.00010ep+0f, kThrAdd = 0x1.a36ed4p-14f;
 // margin = f.wall_cull_margin (host: 1e-3 of the largest coordinate the pass can reach, + 1e-4),
 // far above the positions' drift (at most 3 sc moves, each an add and a multiply rounding within
 // 2^-24 of it: 2 * 3 * sc * 2^-24 < 2.3e-5 of it for sc <= 64) and this test's own rounding.
-__device__ __forceinline__ uint64_t wall_mask(const GlslFrame& f, float dx, float dy, float dz) {
+// v: where campos and the margin come from (fragment's VIEW, below).
+template <class VIEW>
+__device__ __forceinline__ uint64_t wall_mask(const GlslFrame& f, const VIEW& v, float dx, float dy,
+                                              float dz) {
   const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   float ax = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dx), 0)) +
              __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dx), 63));
@@ -113,9 +116,9 @@ __device__ __forceinline__ uint64_t wall_mask(const GlslFrame& f, float dx, floa
   bool keep = true;
   if (lane < f.sc) {
     const GlslWall w = f.walls[lane];
-    const float wx = w.x - f.campos[0], wy = w.y - f.campos[1], wz = w.z - f.campos[2];
+    const float wx = w.x - v.campos[0], wy = w.y - v.campos[1], wz = w.z - v.campos[2];
     const float wl = __builtin_amdgcn_sqrtf((wx * wx + wy * wy) + wz * wz);
-    const float reach = w.r + f.wall_cull_margin;
+    const float reach = w.r + v.wall_cull_margin;
     if (wl >= reach) {  // else the camera is within reach of the wall: kept
       const float iw = __builtin_amdgcn_rcpf(wl);
       const float ca = ((wx * ax + wy * ay) + wz * az) * iw;                  // cos alpha
@@ -165,22 +168,27 @@ struct GlslTap {
   uint32_t rgba;
 };
 
-template <bool CULL, int SS = 0, int MODE = kPlain>
-__device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall> walls,
-                                         const_ptr<GlslBall> balls, int i, int row,
-                                         uint32_t& work, bool store = true,
-                                         GlslTap* tap = nullptr) {
+// VIEW: where the per-camera fields are read -- campos, the basis, fov_x / fov_y / hk / vk,
+// cam_negzero, wall_start, wall_cull_margin and the target `out`.  The frame itself (v is f)
+// everywhere but in the view batches (k_glsl_views), whose waves take them from their view's
+// record (GlslViewRec); every other field is f's.  (A modified copy of the frame would not do: the
+// mip tables are indexed per lane, in the kernel's arguments that is a load, in a copy scratch.)
+template <bool CULL, int SS = 0, int MODE = kPlain, class VIEW = GlslFrame>
+__device__ __forceinline__ void fragment_v(const GlslFrame& f, const VIEW& v,
+                                           const_ptr<GlslWall> walls, const_ptr<GlslBall> balls,
+                                           int i, int row, uint32_t& work, bool store = true,
+                                           GlslTap* tap = nullptr) {
   float dx, dy, dz;
   if constexpr (MODE >= kRay) {
     dx = tap->d[0]; dy = tap->d[1]; dz = tap->d[2];
   } else {
     const float fx = (float)i + 0.5f;
     const float fy = (float)(f.height - 1 - row) + 0.5f;
-    const float ax = -f.fov_x + f.hk * fx;                                   // :172-173
-    const float ay = -f.fov_y + f.vk * fy;
-    dx = (f.fwd[0] + f.right[0] * ax) + f.up[0] * ay;                       // :175
-    dy = (f.fwd[1] + f.right[1] * ax) + f.up[1] * ay;
-    dz = (f.fwd[2] + f.right[2] * ax) + f.up[2] * ay;
+    const float ax = -v.fov_x + v.hk * fx;                                   // :172-173
+    const float ay = -v.fov_y + v.vk * fy;
+    dx = (v.fwd[0] + v.right[0] * ax) + v.up[0] * ay;                       // :175
+    dy = (v.fwd[1] + v.right[1] * ax) + v.up[1] * ay;
+    dz = (v.fwd[2] + v.right[2] * ax) + v.up[2] * ay;
   }
   {
     const float l = len3(dx, dy, dz);                                     // :65
@@ -189,7 +197,7 @@ __device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall>
     div_shared(a, l, q);  // == dx / l, ... (one seed; sfrt_device.h)
     dx = q[0]; dy = q[1]; dz = q[2];
   }
-  const float cx = f.campos[0], cy = f.campos[1], cz = f.campos[2];
+  const float cx = v.campos[0], cy = v.campos[1], cz = v.campos[2];
 
   // ---- furthest wall: 3 passes over the walls (:71-85) ----
   float px = cx, py = cy, pz = cz;
@@ -208,7 +216,7 @@ __device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall>
     const float s = (rx * rx + ry * ry) + rz * rz;
     const bool inside = s <= w.s_in;                   // step(length(rpos), r) == 1
     const uint64_t inside_mask = __builtin_amdgcn_ballot_w64(inside);  // scalar tests only
-    if ((inside_mask | (uint64_t)(uint32_t)f.cam_negzero) != 0) {
+    if ((inside_mask | (uint64_t)(uint32_t)v.cam_negzero) != 0) {
       moved |= inside_mask;
       const float cs = inside ? 1.0f : 0.0f;
       const float b = cs * 2.0f * ((rx * dx + ry * dy) + rz * dz);
@@ -221,12 +229,12 @@ __device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall>
     }
     draw = inside ? k : draw;
   };
-  if (CULL && f.sc > 0 && f.sc <= 64 && f.wall_cull_margin > 0.0f) {
+  if (CULL && f.sc > 0 && f.sc <= 64 && v.wall_cull_margin > 0.0f) {
     // only the walls the wave's rays can meet, in index order (wall_mask above): at 4K each
     // 8x8 tile's rays meet 2.4 of the default scene's 10 walls
-    const uint64_t wm = wall_mask(f, dx, dy, dz) & (f.sc == 64 ? ~0ull : ((1ull << f.sc) - 1ull));
-    int k0 = f.wall_start % f.sc;
-    for (int pass = f.wall_start / f.sc; pass < 3; pass++) {
+    const uint64_t wm = wall_mask(f, v, dx, dy, dz) & (f.sc == 64 ? ~0ull : ((1ull << f.sc) - 1ull));
+    int k0 = v.wall_start % f.sc;
+    for (int pass = v.wall_start / f.sc; pass < 3; pass++) {
       uint64_t moved = 0;
       uint64_t todo = wm & (~0ull << k0);
       while (todo) {
@@ -238,8 +246,8 @@ __device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall>
       if (!moved) break;  // uniform: a pass in which no lane moved is a fixed point
     }
   } else if (f.sc > 0) {
-    int k = f.wall_start % f.sc;
-    for (int pass = f.wall_start / f.sc; pass < 3; pass++) {
+    int k = v.wall_start % f.sc;
+    for (int pass = v.wall_start / f.sc; pass < 3; pass++) {
       uint64_t moved = 0;
       for (; k < f.sc; k++) wall_visit(k, moved);
       k = 0;
@@ -465,7 +473,7 @@ __device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall>
     tap->rgba = unorm8(cr) | (unorm8(cg) << 8) | (unorm8(cbl) << 16) | (255u << 24);
   } else if constexpr (SS == 0) {
     if (store) {
-      f.out[(long long)(row - f.row0) * f.out_pitch + i] =
+      v.out[(long long)(row - f.row0) * f.out_pitch + i] =
           unorm8(cr) | (unorm8(cg) << 8) | (unorm8(cbl) << 16) | (255u << 24);
       if constexpr (MODE == kAux) store_planes(*tap->aux, row - f.row0, i, total, draw, steps);
     }
@@ -476,11 +484,20 @@ __device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall>
         group_box_rgba8<SS>(unorm8(cr) | (unorm8(cg) << 8) | (unorm8(cbl) << 16) | (255u << 24));
     const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     if (group_leader<SS>(lane) && store) {
-      f.out[(long long)((row - f.row0) >> SS) * f.out_pitch + (i >> SS)] = px;
+      v.out[(long long)((row - f.row0) >> SS) * f.out_pitch + (i >> SS)] = px;
       if constexpr (MODE == kAux)
         store_planes(*tap->aux, (row - f.row0) >> SS, i >> SS, total, draw, steps);
     }
   }
+}
+
+// The frame's own camera: every kernel but the view batches.
+template <bool CULL, int SS = 0, int MODE = kPlain>
+__device__ __forceinline__ void fragment(const GlslFrame& f, const_ptr<GlslWall> walls,
+                                         const_ptr<GlslBall> balls, int i, int row,
+                                         uint32_t& work, bool store = true,
+                                         GlslTap* tap = nullptr) {
+  fragment_v<CULL, SS, MODE>(f, f, walls, balls, i, row, work, store, tap);
 }
 
 // Wall and ball records are read once per visit by every wave with scalar loads
@@ -606,6 +623,52 @@ __global__ __launch_bounds__(64) void k_glsl_ordered_aux(GlslFrame f, int ntiles
   }
 }
 
+// The view batches (sfrt_glsl_render_views[_aux]), one family over SS with AUX as
+// its flag on a two-dimensional grid: workgroup (x, y) holds tiles of view y, row-major.  The
+// view's record is read from the device table once, at entry, as voxel_trace.hip's
+// vox_view_rec_at reads its own: the table is written only by the staging copy that precedes the
+// launch on its stream and the address is wave-uniform, so through the constant address space the
+// fields arrive by scalar loads, as a draw's arrive from its arguments.  They stand in for the
+// per-camera fields of the argument's frame (fragment_v's VIEW); every other field is the
+// argument's, shared by all views.  A wave belongs to one view, so the wall pass's wave-uniform
+// tests (cam_negzero, wall_start, the cull's margin) stay wave-uniform.
+// CULL: one tile per one-wave workgroup with the per-wave wall cull (k_glsl_ordered's body without
+// the order, the sorter and the cost record), else four tiles per 256-thread workgroup without it
+// (k_glsl_ss's).  Edge lanes shade a clamped duplicate and store nothing at every SS; a wave past
+// the view's last tile (the four-tile workgroup's tail) retires whole.
+// SFRT_GLSL_VIEWS_CULL picks the form the library launches; DESIGN.md 27 has the measurement.
+#ifndef SFRT_GLSL_VIEWS_CULL
+#define SFRT_GLSL_VIEWS_CULL 1
+#endif
+__device__ __forceinline__ GlslViewRec glsl_view_rec_at(const GlslViewRec* p, uint32_t view) {
+  const __attribute__((address_space(4))) uint32_t* q =
+      (const __attribute__((address_space(4))) uint32_t*)(
+          (const __attribute__((address_space(4))) char*)p + (size_t)view * sizeof(GlslViewRec));
+  uint32_t w[sizeof(GlslViewRec) / 4];
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(GlslViewRec) / 4); i++) w[i] = q[i];
+  GlslViewRec r;
+  __builtin_memcpy(&r, w, sizeof r);
+  return r;
+}
+template <bool CULL, int SS, bool AUX>
+__global__ __launch_bounds__(CULL ? 64 : 256) void k_glsl_views(GlslFrame f, const GlslViewRec* views) {
+  const GlslViewRec v = glsl_view_rec_at(views, blockIdx.y);
+  const int lane = threadIdx.x & 63;
+  const int tile = CULL ? (int)blockIdx.x : (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  const int tx = tile % f.tiles_x, ty = tile / f.tiles_x;
+  if (ty * 8 >= f.rows) return;  // wave-uniform
+  const int i = tx * 8 + (lane & 7);
+  const int r = ty * 8 + (lane >> 3);
+  const bool in = i < f.width && r < f.rows;
+  uint32_t work = 0;
+  GlslTap tap;
+  tap.aux = &v.aux;
+  fragment_v<CULL, SS, AUX ? kAux : kPlain>(f, v, as_const(f.walls), as_const(f.balls),
+                                            i < f.width ? i : f.width - 1,
+                                            r < f.rows ? r : f.rows - 1, work, in, &tap);
+}
+
 // ---- Ray batches: the shader's Raycast(campos, dir, 1) for caller-supplied directions
 // (sfrt_glsl_cast_rays) ----
 //
@@ -696,6 +759,44 @@ int launch_glsl_rays(const GlslFrame& f, const GlslRays& rays, void* stream, voi
   else
     hipExtLaunchKernelGGL(k_glsl_cast_rays<false>, grid, dim3(64), 0, (hipStream_t)stream, nullptr,
                           (hipEvent_t)done_event, 0, f, rays);
+  return hipGetLastError() != hipSuccess;
+}
+
+namespace {
+template <int SS>
+void launch_views(const GlslFrame& f, const GlslViewRec* views, bool aux, long long tiles, int count,
+                  void* stream, void* done_event) {
+  constexpr bool kCull = SFRT_GLSL_VIEWS_CULL != 0;
+  const dim3 grid((unsigned)(kCull ? tiles : (tiles + 3) / 4), (unsigned)count);
+  const dim3 block(kCull ? 64 : 256);
+  if (aux)
+    hipExtLaunchKernelGGL((k_glsl_views<kCull, SS, true>), grid, block, 0, (hipStream_t)stream,
+                          nullptr, (hipEvent_t)done_event, 0, f, views);
+  else
+    hipExtLaunchKernelGGL((k_glsl_views<kCull, SS, false>), grid, block, 0, (hipStream_t)stream,
+                          nullptr, (hipEvent_t)done_event, 0, f, views);
+}
+}  // namespace
+
+bool glsl_views_grid_ok(const GlslFrame& f, int count) {
+  if (f.tiles_x <= 0 || f.rows <= 0) return false;
+  const long long tiles = (long long)f.tiles_x * ((f.rows + 7) / 8);
+  // work-items per grid dimension are 32 bits, workgroups in all at most 2^31 - 1
+  return count > 0 && tiles * 64 <= 0xffffffffLL && tiles * count <= 0x7fffffffLL;
+}
+
+int launch_glsl_views(const GlslFrame& f, const GlslViewRec* dev_views, int count, bool aux,
+                      void* stream, void* done_event) {
+  if (!glsl_views_grid_ok(f, count) || count > 65535 || !dev_views) return -1;
+  if (!f.status || !f.mip || !f.walls || !f.balls || !f.pairs || !f.mats) return -1;
+  if (f.tile_order || f.tile_cost || f.prev_cost || f.next_order) return -1;
+  if (f.ss < 0 || f.ss > 2 || f.row0 != 0 || f.rows != f.height) return -1;
+  if (f.tiles_x != (f.width + 7) / 8) return -1;
+  if (f.ss && ((f.width | f.rows) & ((1 << f.ss) - 1))) return -1;
+  const long long tiles = (long long)f.tiles_x * ((f.rows + 7) / 8);
+  if (f.ss == 0) launch_views<0>(f, dev_views, aux, tiles, count, stream, done_event);
+  else if (f.ss == 1) launch_views<1>(f, dev_views, aux, tiles, count, stream, done_event);
+  else launch_views<2>(f, dev_views, aux, tiles, count, stream, done_event);
   return hipGetLastError() != hipSuccess;
 }
 

@@ -117,10 +117,15 @@ struct sfrt_glsl {
   // with a pinned staging copy and the event of the last draw that read it,
   // so draws on different streams never overwrite tables still in use.
   // (sfrt::TableSlot, sfrt_host.h: a reuse on another stream waits for the slot's last user.)
-  static constexpr int kSlots = 4;
-  sfrt::TableSlot slots[kSlots];
+  // The view batches (sfrt_glsl_render_views) stage their block -- view records and a table block
+  // of their own -- in a ring of their own behind the draws' slots, in the same array so that
+  // set_ground waits for the batches that read the old chain too; a batch never touches the
+  // draws' slots, cur_slot or staged_version.
+  static constexpr int kSlots = 4, kViewSlots = 4;
+  sfrt::TableSlot slots[kSlots + kViewSlots];
   int next_slot = 0;
   int cur_slot = -1;
+  int next_view_slot = 0;
   // The tables depend only on the uniform block: every uniform setter bumps u_version, and a
   // draw with the uniforms unchanged since the last staging reuses that slot (no host table
   // build, no copy in front of the kernel).
@@ -157,17 +162,28 @@ struct sfrt_glsl {
     if (stream) (void)hipStreamDestroy(stream);
   }
 
-  // view: the uniforms only a frame reads (rotation, fov, size); a ray batch reads none of them
-  int validate(bool view = true) const {
+  // What validate() asks of the three camera uniforms, for values that are not (yet) uniforms:
+  // the views of a batch.
+  static bool camera_ok(const float* campos, const float* rotation, const float* fov) {
+    for (float c : {campos[0], campos[1], campos[2], rotation[0], rotation[1], fov[0], fov[1]})
+      if (!bounded(c)) return false;
+    return true;
+  }
+
+  // view: the uniforms only a frame reads (rotation, fov, size); a ray batch reads none of them.
+  // camera false: a view batch, which brings campos, rotation and fov of its own (camera_ok).
+  int validate(bool view = true, bool camera = true) const {
     const sfrt_glsl_uniforms& v = u;
     if (v.sphere_count < 0 || v.light_count < 0 || v.all_spheres_count > SFRT_GLSL_MAX_SPHERES ||
         v.sphere_count + v.light_count > v.all_spheres_count)
       return SFRT_E_INVALID;
-    for (float c : {v.campos[0], v.campos[1], v.campos[2]})
-      if (!bounded(c)) return SFRT_E_INVALID;
-    if (view) {
-      for (float c : {v.rotation[0], v.rotation[1], v.fov[0], v.fov[1]})
+    if (camera)
+      for (float c : {v.campos[0], v.campos[1], v.campos[2]})
         if (!bounded(c)) return SFRT_E_INVALID;
+    if (view) {
+      if (camera)
+        for (float c : {v.rotation[0], v.rotation[1], v.fov[0], v.fov[1]})
+          if (!bounded(c)) return SFRT_E_INVALID;
       if (!(v.size[0] > 0.0f && v.size[1] > 0.0f && bounded(v.size[0]) && bounded(v.size[1])))
         return SFRT_E_INVALID;
       // the `size` the supersampled fragments see
@@ -181,16 +197,27 @@ struct sfrt_glsl {
     return SFRT_OK;
   }
 
-  // Frame record + per-draw tables on stream s (stream-ordered reuse).  frame false: for a ray
-  // batch that reads neither the view uniforms nor (textured false) the ground.
-  int prepare(sfrt::GlslFrame& f, hipStream_t s, bool frame = true, bool textured = true) {
-    if (textured && !d_mip) return SFRT_E_NO_TEXTURE;
-    int rc = validate(frame);
-    if (rc) return rc;
-    HIP_TRY(ground.before_read(s));  // a set_ground queued on another stream lands first
-    std::memset(&f, 0, sizeof f);
+  // The wall records of the uniform block (at least one entry, for an empty table's sake).
+  std::vector<sfrt::GlslWall> wall_table() const {
+    const int sc = u.sphere_count;
+    std::vector<sfrt::GlslWall> walls(sc > 0 ? sc : 1);
+    for (int k = 0; k < sc; k++) {
+      const float* S = u.spheres[k];
+      walls[k] = {S[0], S[1], S[2], S[3], S[3] * S[3], inside_bound(S[3]), 0.0f, 0.0f};
+    }
+    return walls;
+  }
+
+  // The per-camera part of a frame record, from what the three camera uniforms hold (a draw: the
+  // shader's own; a view batch: each view's, once per view) and the `size` uniform: the basis,
+  // fov_x / fov_y / hk / vk, campos, cam_negzero, wall_start and wall_cull_margin.  CAM is the
+  // frame record itself or a view's record (sfrt::GlslViewRec: the same field names).  frame false:
+  // a ray batch, which reads neither hk nor vk.
+  template <class CAM>
+  void camera_terms(const float* campos, const float* rotation, const float* fov, bool frame,
+                    const std::vector<sfrt::GlslWall>& walls, CAM& f) const {
     const sfrt_glsl_uniforms& v = u;
-    const int sc = v.sphere_count, lc = v.light_count, all = v.all_spheres_count;
+    const int sc = v.sphere_count;
     // main(), rayShader.frag:165-173 -- VRotateX / VRotateY (:16-25) on unit axes
     auto rot_x = [](const float* a, float amount, float* o) {
       const float s = std::sin(amount), c = std::cos(amount);
@@ -206,33 +233,22 @@ struct sfrt_glsl {
     };
     const float ey[3] = {0, 1, 0}, ez[3] = {0, 0, 1}, ex[3] = {1, 0, 0};
     float up0[3], fwd0[3];
-    rot_x(ey, -v.rotation[1], up0);
-    rot_x(ez, -v.rotation[1], fwd0);
-    rot_y(ex, v.rotation[0], f.right);
-    rot_y(fwd0, v.rotation[0], f.fwd);
-    rot_y(up0, v.rotation[0], f.up);
-    for (int c = 0; c < 3; c++) f.campos[c] = v.campos[c];
-    f.fov_x = v.fov[0];
-    f.fov_y = v.fov[1];
+    rot_x(ey, -rotation[1], up0);
+    rot_x(ez, -rotation[1], fwd0);
+    rot_y(ex, rotation[0], f.right);
+    rot_y(fwd0, rotation[0], f.fwd);
+    rot_y(up0, rotation[0], f.up);
+    for (int c = 0; c < 3; c++) f.campos[c] = campos[c];
+    f.fov_x = fov[0];
+    f.fov_y = fov[1];
     // size of the S * width x S * height target when supersampled (a power of two: exact)
-    f.ss = ss;
     if (frame) {
-      f.hk = v.fov[0] / (v.size[0] * (float)(1 << ss)) * 2.0f;
-      f.vk = v.fov[1] / (v.size[1] * (float)(1 << ss)) * 2.0f;
+      f.hk = fov[0] / (v.size[0] * (float)(1 << ss)) * 2.0f;
+      f.vk = fov[1] / (v.size[1] * (float)(1 << ss)) * 2.0f;
     }
-    f.sc = sc;
-    f.lc = lc;
-    f.all = all;
-    f.cam_negzero = (std::signbit(v.campos[0]) && v.campos[0] == 0.0f) ||
-                    (std::signbit(v.campos[1]) && v.campos[1] == 0.0f) ||
-                    (std::signbit(v.campos[2]) && v.campos[2] == 0.0f);
-    // tables
-    const int nb = all - sc, ns = all - sc - lc;
-    std::vector<sfrt::GlslWall> walls(sc > 0 ? sc : 1);
-    for (int k = 0; k < sc; k++) {
-      const float* S = v.spheres[k];
-      walls[k] = {S[0], S[1], S[2], S[3], S[3] * S[3], inside_bound(S[3]), 0.0f, 0.0f};
-    }
+    f.cam_negzero = (std::signbit(campos[0]) && campos[0] == 0.0f) ||
+                    (std::signbit(campos[1]) && campos[1] == 0.0f) ||
+                    (std::signbit(campos[2]) && campos[2] == 0.0f);
     // Every lane starts at campos: the wall-pass iterations before the first
     // wall containing campos (same test as the kernel) are no-ops for all of
     // them.  With a -0.0 in campos the kernel's literal update runs from 0.
@@ -240,8 +256,8 @@ struct sfrt_glsl {
     if (!f.cam_negzero && sc > 0) {
       int j = 0;
       for (; j < sc; j++) {
-        const float rx = v.campos[0] - walls[j].x, ry = v.campos[1] - walls[j].y,
-                    rz = v.campos[2] - walls[j].z;
+        const float rx = campos[0] - walls[j].x, ry = campos[1] - walls[j].y,
+                    rz = campos[2] - walls[j].z;
         if ((rx * rx + ry * ry) + rz * rz <= walls[j].s_in) break;
       }
       f.wall_start = j < sc ? j : 3 * sc;  // inside no wall: no lane ever moves
@@ -253,19 +269,36 @@ struct sfrt_glsl {
     static_assert(2.0 * 3.0 * 64.0 * 0x1.0p-24 < 1e-3 / 8, "the margin dwarfs the drift");
     f.wall_cull_margin = 0.0f;
     if (!f.cam_negzero && sc > 0 && sc <= 64) {
-      double R = std::max({std::fabs((double)v.campos[0]), std::fabs((double)v.campos[1]),
-                           std::fabs((double)v.campos[2])});
+      double R = std::max({std::fabs((double)campos[0]), std::fabs((double)campos[1]),
+                           std::fabs((double)campos[2])});
       for (int k = 0; k < sc; k++)
         for (int c = 0; c < 3; c++)
           R = std::max(R, std::fabs((double)v.spheres[k][c]) + std::fabs((double)v.spheres[k][3]));
       const double m = 1e-3 * R + 1e-4;
       if (std::isfinite(m) && m < 1e30) f.wall_cull_margin = (float)m;
     }
-    if (staged_version == u_version && cur_slot >= 0) {  // launched() re-marks the slot
-      HIP_TRY(slots[cur_slot].use_on(s));  // staged, or last read, on another stream: wait for it
-      fill_tables(f, slots[cur_slot].d.ptr<uint8_t>(), staged_off);
-      return SFRT_OK;
-    }
+  }
+
+  // Byte offsets of balls | pairs | mats behind the walls in a table block; returns its size.
+  size_t table_layout(size_t off[3]) const {
+    const int sc = u.sphere_count, lc = u.light_count, all = u.all_spheres_count;
+    const int nb = all - sc, ns = all - sc - lc;
+    off[0] = (size_t)(sc > 0 ? sc : 1) * sizeof(sfrt::GlslWall);
+    off[1] = off[0] + (size_t)(nb > 0 ? nb : 1) * sizeof(sfrt::GlslBall);
+    off[2] = off[1] + (size_t)(lc * ns > 0 ? lc * ns : 1) * sizeof(sfrt::GlslPair);
+    return off[2] + (size_t)sfrt::kGlslMax * sizeof(sfrt::GlslMat);
+  }
+
+  // The table block walls | balls | pairs | mats at blob (table_layout's offsets) for the cameras
+  // at cams[0 .. ncams): scene terms but for GlslPair::cos_lit, whose shortcut is proved for
+  // positions near the ball and so is kept only where EVERY camera is within 1000 of it (a draw:
+  // the shader's campos alone; a view batch: all its views -- the shortcut is exact where it
+  // applies and -2 switches it off, so a pair that loses it shades the same bytes).
+  void build_tables(uint8_t* blob, const size_t off[3], const std::vector<sfrt::GlslWall>& walls,
+                    const float (*cams)[3], int ncams) const {
+    const sfrt_glsl_uniforms& v = u;
+    const int sc = v.sphere_count, lc = v.light_count, all = v.all_spheres_count;
+    const int nb = all - sc, ns = all - sc - lc;
     std::vector<sfrt::GlslBall> balls(nb > 0 ? nb : 1);
     for (int k = 0; k < nb; k++) {
       const float* S = v.spheres[sc + k];
@@ -292,9 +325,13 @@ struct sfrt_glsl {
         P.bz = B[2];
         // acos(dot) >= sanglet * (1 + 1e-3) + 1e-3 suffices for a factor of 1
         // (DESIGN.md 5c); only for balls near the camera (|pos - ball| < 2000).
-        const float cx = v.campos[0] - B[0], cy = v.campos[1] - B[1], cz = v.campos[2] - B[2];
-        const float dcam = std::sqrt((cx * cx + cy * cy) + cz * cz);
-        P.cos_lit = (P.sanglet > 0.0f && P.sanglet < 1.0f && dcam < 1000.0f)
+        bool near = true;
+        for (int q = 0; q < ncams; q++) {
+          const float cx = cams[q][0] - B[0], cy = cams[q][1] - B[1], cz = cams[q][2] - B[2];
+          const float dcam = std::sqrt((cx * cx + cy * cy) + cz * cz);
+          near = near && dcam < 1000.0f;
+        }
+        P.cos_lit = (P.sanglet > 0.0f && P.sanglet < 1.0f && near)
                         ? std::cos(P.sanglet * 1.001f + 1e-3f) : -2.0f;
       }
     std::vector<sfrt::GlslMat> mats(sfrt::kGlslMax);
@@ -307,25 +344,45 @@ struct sfrt_glsl {
       M.cz = v.spheres[k][2];
       M.pad = 0.0f;
     }
-    const size_t bw = walls.size() * sizeof walls[0], bb = balls.size() * sizeof balls[0],
-                 bp = pairs.size() * sizeof pairs[0], bm = mats.size() * sizeof mats[0];
-    const size_t bytes = bw + bb + bp + bm;
+    std::memcpy(blob, walls.data(), walls.size() * sizeof walls[0]);
+    std::memcpy(blob + off[0], balls.data(), balls.size() * sizeof balls[0]);
+    std::memcpy(blob + off[1], pairs.data(), pairs.size() * sizeof pairs[0]);
+    std::memcpy(blob + off[2], mats.data(), mats.size() * sizeof mats[0]);
+  }
+
+  // Frame record + per-draw tables on stream s (stream-ordered reuse).  frame false: for a ray
+  // batch that reads neither the view uniforms nor (textured false) the ground.
+  int prepare(sfrt::GlslFrame& f, hipStream_t s, bool frame = true, bool textured = true) {
+    if (textured && !d_mip) return SFRT_E_NO_TEXTURE;
+    int rc = validate(frame);
+    if (rc) return rc;
+    HIP_TRY(ground.before_read(s));  // a set_ground queued on another stream lands first
+    std::memset(&f, 0, sizeof f);
+    const sfrt_glsl_uniforms& v = u;
+    const std::vector<sfrt::GlslWall> walls = wall_table();
+    camera_terms(v.campos, v.rotation, v.fov, frame, walls, f);
+    f.ss = ss;
+    f.sc = v.sphere_count;
+    f.lc = v.light_count;
+    f.all = v.all_spheres_count;
+    if (staged_version == u_version && cur_slot >= 0) {  // launched() re-marks the slot
+      HIP_TRY(slots[cur_slot].use_on(s));  // staged, or last read, on another stream: wait for it
+      fill_tables(f, slots[cur_slot].d.ptr<uint8_t>(), staged_off);
+      return SFRT_OK;
+    }
+    size_t off[3];
+    const size_t bytes = table_layout(off);
     sfrt::TableSlot& t = slots[next_slot];
     HIP_TRY(t.reclaim());
     HIP_TRY(t.grow(bytes, s));  // no wait on other streams (sfrt_host.h)
     uint8_t* blob = t.h.ptr<uint8_t>();
-    std::memcpy(blob, walls.data(), bw);
-    std::memcpy(blob + bw, balls.data(), bb);
-    std::memcpy(blob + bw + bb, pairs.data(), bp);
-    std::memcpy(blob + bw + bb + bp, mats.data(), bm);
+    build_tables(blob, off, walls, &v.campos, 1);
     HIP_TRY(hipMemcpyAsync(t.d.ptr(), blob, bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(t.staged(s));
     cur_slot = next_slot;
     next_slot = (next_slot + 1) % kSlots;
     staged_version = u_version;
-    staged_off[0] = bw;
-    staged_off[1] = bw + bb;
-    staged_off[2] = bw + bb + bp;
+    for (int k = 0; k < 3; k++) staged_off[k] = off[k];
     fill_tables(f, t.d.ptr<uint8_t>(), staged_off);
     return SFRT_OK;
   }
@@ -576,6 +633,98 @@ static int draw_image_body(sfrt_glsl* g, uint8_t* pixels, void* const* planes, i
   return g->read_status(g->stream);
 }
 
+// sfrt_glsl_render_views and sfrt_glsl_render_views_aux (with_aux false for the plain call): view k
+// is the whole frame that setUniform(campos, rotation, fov of views[k].cam) + draw[_aux] would
+// write, all views in one launch of the view kernels (glsl_trace.h launch_glsl_views).  The
+// per-camera part of a draw's frame record is built per view by the function prepare() builds the
+// draw's with (camera_terms), into one pinned block
+//   count view records | walls | balls | pairs | mats
+// (the table block 16-byte aligned; its pairs keep the lit shortcut only where every view of the
+// batch may have it, build_tables), sent by one copy on the caller's stream from a slot of the view
+// ring.  Nothing of the shader is written: not its uniforms or u_version, not the draws' staged
+// slot or staged_version, not the tile chains.
+static int render_views_body(sfrt_glsl* g, const sfrt_view* views, const sfrt_aux_planes* planes,
+                             bool with_aux, int count, int width, int height, int64_t pitch_bytes,
+                             int flags, void* hip_stream) {
+  if (!g || !views || count < 0 || count > SFRT_MAX_VIEWS || flags != 0 || width <= 0 ||
+      height <= 0 || height >= (1 << 24) || width >= (1 << 24) || pitch_bytes % 4 != 0 ||
+      pitch_bytes < (int64_t)width * 4 || (with_aux && !planes))
+    return SFRT_E_INVALID;
+  std::vector<sfrt::GlslAux> aux(with_aux ? (size_t)count : 0);
+  for (int k = 0; k < count; k++) {
+    const sfrt_camera& c = views[k].cam;
+    const float rotation[2] = {c.rotation, c.hrotation}, fov[2] = {c.fov_h, c.fov_v};
+    if (!views[k].dev_pixels || !sfrt::aligned4({views[k].dev_pixels}) ||
+        !sfrt_glsl::camera_ok(c.pos, rotation, fov))
+      return SFRT_E_INVALID;
+    if (!with_aux) continue;
+    const sfrt_aux_planes& p = planes[k];
+    sfrt::GlslAux& a = aux[(size_t)k];
+    if ((!p.depth && !p.sphere && !p.steps) ||
+        !sfrt::aux_plane(p.depth, p.depth_pitch_bytes, width, a.depth, a.depth_pitch) ||
+        !sfrt::aux_plane(p.sphere, p.sphere_pitch_bytes, width, a.sphere, a.sphere_pitch) ||
+        !sfrt::aux_plane(p.steps, p.steps_pitch_bytes, width, a.steps, a.steps_pitch))
+      return SFRT_E_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(g->mu);
+  if (count == 0) return SFRT_OK;
+  const int ss = g->ss;
+  if ((height << ss) >= (1 << 24) || (width << ss) >= (1 << 24)) return SFRT_E_INVALID;
+  if (!g->d_mip) return SFRT_E_NO_TEXTURE;
+  const int rc = g->validate(true, false);  // the scene uniforms and `size`; the cameras: above
+  if (rc) return rc;
+  // The frame geometry of a whole-frame draw, the same for every view, and the grid it gives,
+  // refused before anything is queued if one launch cannot take it.
+  sfrt::GlslFrame f;
+  std::memset(&f, 0, sizeof f);
+  f.ss = ss;
+  f.sc = g->u.sphere_count;
+  f.lc = g->u.light_count;
+  f.all = g->u.all_spheres_count;
+  f.width = width << ss;
+  f.height = height << ss;
+  f.row0 = 0;
+  f.rows = f.height;
+  f.tiles_x = (f.width + 7) / 8;
+  f.out_pitch = pitch_bytes / 4;
+  if (!sfrt::glsl_views_grid_ok(f, count)) return SFRT_E_INVALID;
+  sfrt::DeviceGuard dg(g->device);
+  hipStream_t s = (hipStream_t)hip_stream;
+  HIP_TRY(g->ground.before_read(s));  // a set_ground queued on another stream lands first
+  size_t off[3];
+  const size_t at_tables = ((size_t)count * sizeof(sfrt::GlslViewRec) + 15) / 16 * 16;
+  const size_t bytes = at_tables + g->table_layout(off);
+  sfrt::TableSlot& t = g->slots[sfrt_glsl::kSlots + g->next_view_slot];
+  g->next_view_slot = (g->next_view_slot + 1) % sfrt_glsl::kViewSlots;
+  HIP_TRY(t.reclaim());  // the launch that read the slot's last block is done (no device-wide wait)
+  HIP_TRY(t.grow(bytes, s));
+  uint8_t* const h = t.h.ptr<uint8_t>();
+  uint8_t* const d = t.d.ptr<uint8_t>();
+  const std::vector<sfrt::GlslWall> walls = g->wall_table();
+  std::vector<float> cams((size_t)count * 3);
+  for (int k = 0; k < count; k++) {
+    const sfrt_camera& c = views[k].cam;
+    const float rotation[2] = {c.rotation, c.hrotation}, fov[2] = {c.fov_h, c.fov_v};
+    sfrt::GlslViewRec r;
+    std::memset(&r, 0, sizeof r);
+    g->camera_terms(c.pos, rotation, fov, true, walls, r);
+    r.out = (uint32_t*)views[k].dev_pixels;
+    if (with_aux) r.aux = aux[(size_t)k];
+    std::memcpy(h + (size_t)k * sizeof r, &r, sizeof r);
+    for (int q = 0; q < 3; q++) cams[(size_t)k * 3 + q] = c.pos[q];
+  }
+  g->build_tables(h + at_tables, off, walls, (const float(*)[3])cams.data(), count);
+  HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+  // the copy is queued: on a failure below the slot stays busy until it has run
+  g->fill_tables(f, d + at_tables, off);
+  if (sfrt::launch_glsl_views(f, (const sfrt::GlslViewRec*)d, count, with_aux, s, t.launch_event())) {
+    (void)t.staged(s);
+    return SFRT_E_HIP;
+  }
+  HIP_TRY(t.launched_with(s));
+  return SFRT_OK;
+}
+
 // ---- batched ray queries (include/sfrt.h) ----
 namespace {
 
@@ -622,6 +771,19 @@ int sfrt_glsl_draw_image_aux(sfrt_glsl* g, uint8_t* pixels, float* depth, int32_
                              int32_t* steps, int width, int height) {
   void* const planes[3] = {depth, sphere, steps};
   return draw_image_body(g, pixels, planes, width, height);
+}
+
+int sfrt_glsl_render_views(sfrt_glsl* g, const sfrt_view* views, int count, int width, int height,
+                           int64_t pitch_bytes, int flags, void* hip_stream) {
+  return render_views_body(g, views, nullptr, false, count, width, height, pitch_bytes, flags,
+                           hip_stream);
+}
+
+int sfrt_glsl_render_views_aux(sfrt_glsl* g, const sfrt_view* views, const sfrt_aux_planes* planes,
+                               int count, int width, int height, int64_t pitch_bytes, int flags,
+                               void* hip_stream) {
+  return render_views_body(g, views, planes, true, count, width, height, pitch_bytes, flags,
+                           hip_stream);
 }
 
 int sfrt_glsl_cast_rays_device(sfrt_glsl* g, const float* dev_dirs, int64_t count,

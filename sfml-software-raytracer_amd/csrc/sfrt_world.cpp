@@ -1758,7 +1758,7 @@ const char* sfrt_error_string(int code) {
   }
 }
 
-int sfrt_version(void) { return 17; }
+int sfrt_version(void) { return 18; }
 
 const char* sfrt_build_flavour(void) { return sfrt::trace_build_flavour(); }
 

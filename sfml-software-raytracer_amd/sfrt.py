@@ -79,6 +79,7 @@ ABI_SYMBOLS = (
     "sfrt_voxel_render_views", "sfrt_voxel_render_views_aux", "sfrt_voxel_sort_dynamics",
     "sfrt_world_texel_cache_stats", "sfrt_world_compact_cache_stats",
     "sfrt_world_pixel_cache_stats",
+    "sfrt_glsl_render_views", "sfrt_glsl_render_views_aux",
 )
 
 SFRT_MAX_VIEWS = 1024
@@ -280,6 +281,10 @@ def lib() -> ctypes.CDLL:
         "sfrt_glsl_draw_image_aux": ([vp, vp, vp, vp, vp, c_int, c_int], c_int),
         "sfrt_glsl_cast_rays": ([vp, vp, ctypes.c_int64, P(RayHits)], c_int),
         "sfrt_glsl_cast_rays_device": ([vp, vp, ctypes.c_int64, P(RayHits), vp], c_int),
+        "sfrt_glsl_render_views": ([vp, P(View), c_int, c_int, c_int, ctypes.c_int64, c_int, vp],
+                                   c_int),
+        "sfrt_glsl_render_views_aux": ([vp, P(View), P(AuxPlanes), c_int, c_int, c_int,
+                                        ctypes.c_int64, c_int, vp], c_int),
         "sfrt_glsl_check": ([vp, vp], c_int),
         "sfrt_glsl_set_option": ([vp, c_int, c_int], c_int),
         "sfrt_glsl_get_option": ([vp, c_int, P(c_int)], c_int),
@@ -1332,6 +1337,41 @@ class GlslShader:
         _check(lib().sfrt_glsl_draw_image_aux(self._h, res["rgba"].ctypes.data, *ptrs, int(width),
                                               int(height)), "glsl_draw_image_aux")
         return res
+
+    # --- view batches ---
+    def render_views(self, views, width: int, height: int, pitch_bytes: int,
+                     stream: int = 0) -> None:
+        """A batch of whole frames of this shader in one launch (sfrt_glsl_render_views): view k
+        is the frame set_uniform("campos" / "rotation" / "fov" from views[k].cam) + draw would
+        write at views[k].dev_pixels; the shader itself is left as it was.  views: View objects
+        or (Camera, device pointer) pairs.  Asynchronous on `stream`."""
+        arr = World._view_array(views)
+        _check(lib().sfrt_glsl_render_views(self._h, arr, len(views), int(width), int(height),
+                                            int(pitch_bytes), 0, ctypes.c_void_p(stream or None)),
+               "glsl_render_views")
+
+    def render_views_aux(self, views, planes, width: int, height: int, pitch_bytes: int,
+                         stream: int = 0) -> None:
+        """render_views plus each view's planes (sfrt_glsl_render_views_aux): planes[k] is an
+        AuxPlanes, or a dict of draw_aux's (device pointer, pitch in bytes) pairs under "depth",
+        "sphere" and "steps"."""
+        if len(planes) != len(views):
+            raise ValueError("one planes entry per view")
+        arr = World._view_array(views)
+        pl = (AuxPlanes * max(1, len(views)))()
+        for k, p in enumerate(planes):
+            if not isinstance(p, AuxPlanes):
+                q = AuxPlanes()
+                for name, plane in p.items():
+                    if plane is not None:
+                        setattr(q, name, int(plane[0]))
+                        setattr(q, name + "_pitch_bytes", int(plane[1]))
+                p = q
+            pl[k] = p
+        _check(lib().sfrt_glsl_render_views_aux(self._h, arr, pl, len(views), int(width),
+                                                int(height), int(pitch_bytes), 0,
+                                                ctypes.c_void_p(stream or None)),
+               "glsl_render_views_aux")
 
     # --- ray queries ---
     def cast_rays(self, dirs, outputs=RAY_OUTPUTS) -> dict:
