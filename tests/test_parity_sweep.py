@@ -23,6 +23,11 @@ tests use, every frame against the CPU restatement byte for byte --
   ray batches, the caches at rest and under one step -- on N sphere scenes at the short ragged
   sizes of tests/sphere_fuzz_cases.py (SFRT_PARITY_SWEEP_SIZE does not apply).
 
+* the GLSL and voxel kernel families (test_glsl_family_sweep, test_voxel_family_sweep, recorded
+  as "glsl_families" and "voxel_families"): the checks of tests/test_glsl_family_fuzz.py and
+  tests/test_voxel_family_fuzz.py on N scenes of this module's GLSL and voxel generators at the
+  short ragged sizes of tests/glsl_fuzz_cases.py and tests/voxel_fuzz_cases.py.
+
 Every fifth scene is drawn as 2-4 random row bands (global row indices, as the multi-GPU bands).
 SFRT_PARITY_SWEEP_MODE=adversarial pushes each generator to its degenerate corners;
 SFRT_PARITY_SWEEP_SIZE=WxH draws every scene at that size.  The summary (scenes, pixels and
@@ -328,6 +333,73 @@ def test_sphere_family_sweep(built):
     assert not bad, bad[:3]
 
 
+def _glsl_reports_the_cap(fam, frames):
+    """Whether the library ends every one of `frames` ((block, width, height) of the S*w x S*h
+    target the restatement capped on) in SFRT_E_MARCH_LIMIT."""
+    import sfrt
+    for u, w, h in frames:
+        with sfrt.GlslShader(0) as sh:
+            sh.set_ground(*fam.gv.floor())
+            sh.set_uniforms(u)
+            try:
+                sh.draw_image(w, h)
+            except sfrt.SfrtError as e:
+                if e.code != -6:  # SFRT_E_MARCH_LIMIT
+                    raise
+                continue
+            return False
+    return True
+
+
+def test_glsl_family_sweep(built, floor):
+    """tests/test_glsl_family_fuzz.py's family checks (planes, tile orders, supersampling, views,
+    ray batches) over N consecutive seeds of test_glsl_sweep's blocks (SFRT_PARITY_SWEEP_MODE;
+    random: every fourth the reference's own world) at the short size list of
+    tests/glsl_fuzz_cases.py, each block borrowing the next four seeds' cameras.  A scene for which
+    the restatement raises its march cap is skipped when the library reports the cap for the same
+    frames as well, and a mismatch when it does not."""
+    import functools
+    import time
+    import sfrt
+    import glsl_fuzz_cases as fuzz
+    import test_glsl_family_fuzz as fam
+    seed0 = SEED0 - (100000 if SIZE else 0)  # the frame sizes here are the short list's
+    t0 = time.time()
+    bad, pixels, skipped = [], 0, 0
+    for seed in range(seed0, seed0 + N):
+        index = seed - seed0
+        w, h = fuzz.SIZES[index % len(fuzz.SIZES)]
+        case = fuzz.make_case(MODE, str(seed), functools.partial(fuzz.generated, MODE, seed), index)
+        others = [fuzz.generated(MODE, seed + q, w, h) for q in range(1, 5)]
+        c = fam.Ctx(case, index, others)
+        capped = fuzz.capped_frames(case, others, floor, host_threads())
+        if capped:
+            frames = fuzz.asked_frames(case, others)
+            if _glsl_reports_the_cap(fam, [frames[name] for name in capped]):
+                skipped += 1
+            else:
+                bad.append({"seed": seed, "oracle": "march cap", "frames": capped, "library": "none"})
+            continue
+        for name, check in fam.FAMILIES.items():
+            try:
+                check(c)
+            except AssertionError as e:
+                bad.append({"seed": seed, "family": name, "diff": str(e)[:300]})
+            except sfrt.SfrtError as e:  # nothing more runs on a device that reported an error
+                bad.append({"seed": seed, "family": name, "error": str(e)})
+                _record("glsl_families", index + 1, pixels, bad, skipped)
+                raise
+        pixels += w * h
+        _progress("glsl families", index + 1, bad)
+    _record("glsl_families", N, pixels, bad, skipped)
+    RESULTS["glsl_families"].update(
+        families=list(fam.FAMILIES), sizes=["%dx%d" % s for s in fuzz.SIZES], first_seed=seed0,
+        share_skipped_march_cap_both_sides=skipped / N, wall_s=round(time.time() - t0, 1))
+    _record_flush()
+    assert not bad, bad[:3]
+    assert skipped <= 0.02 * N, skipped
+
+
 def test_glsl_sweep(built, floor):
     import oracle
     import sfrt
@@ -387,6 +459,44 @@ def test_glsl_sweep(built, floor):
     finally:
         s.close()
     _record("glsl", N, pixels, bad, skipped)
+    assert not bad, bad[:3]
+
+
+def test_voxel_family_sweep(built):
+    """tests/test_voxel_family_fuzz.py's family checks (planes, tile orders, supersampling, subsets
+    in place, views, ray and shadow batches) over N consecutive seeds of test_voxel_sweep's worlds
+    (SFRT_PARITY_SWEEP_MODE; random: every fourth the default world from a random empty cell) at
+    the short size list of tests/voxel_fuzz_cases.py, each world borrowing the next four seeds'
+    cameras.  No scene is excluded: a read outside a texture is compared with the stand-in texel on
+    both sides, and the library's status must say so exactly when the oracle's counter rose."""
+    import time
+    import sfrt
+    import voxel_fuzz_cases as fuzz
+    import test_voxel_family_fuzz as fam
+    seed0 = SEED0 - (100000 if SIZE else 0)  # the frame sizes here are the short list's
+    t0 = time.time()
+    bad, pixels, ub = [], 0, 0
+    for seed in range(seed0, seed0 + N):
+        index = seed - seed0
+        case = fuzz.make_case(MODE, str(seed), fuzz.generated(MODE, seed), index)
+        c = fam.Ctx(case, index, [fuzz.generated(MODE, seed + q) for q in range(1, 5)])
+        for name, check in fam.FAMILIES.items():
+            try:
+                check(c)
+            except AssertionError as e:
+                bad.append({"seed": seed, "family": name, "diff": str(e)[:300]})
+            except sfrt.SfrtError as e:  # nothing more runs on a device that reported an error
+                bad.append({"seed": seed, "family": name, "error": str(e)})
+                _record("voxel_families", index + 1, pixels, bad)
+                raise
+        ub += "texel_outside" in case.tags
+        pixels += case.width * case.height
+        _progress("voxel families", index + 1, bad)
+    _record("voxel_families", N, pixels, bad)
+    RESULTS["voxel_families"].update(
+        families=list(fam.FAMILIES), sizes=["%dx%d" % s for s in fuzz.SIZES], first_seed=seed0,
+        texel_outside_both_sides=ub, wall_s=round(time.time() - t0, 1))
+    _record_flush()
     assert not bad, bad[:3]
 
 
